@@ -7,15 +7,23 @@ Workload (config.workload): BASELINE.json configs[1] -- ViT-L/16 + DPT head + CL
 One "step" = one LSegNet.forward call on one batch, INCLUDING the CLIP text tower, which the
 reference re-runs on every forward (modules/models/lseg_net.py:183).
 
+A plain run does only what the headline needs: set-up, `--warmup` untimed and `--steps` timed forwards, the outputs of the last
+timed step if `--dump-outputs DIR` is given, and the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything else the bench measures or checks runs with `--full` only: the operand-type selection below, the other operand type,
+the dominant-kernel roofline and per-family figures, the in-run PMC traffic passes, the batch-vs-single self-check, the CPU
+baseline, the batch sweep, K = 1000, the training step, and the drop-in and multi-scale evaluator legs.
+
 MFMA operand type (`dtype`): the reference's image tower is fp32; both 16-bit operand types run at the same MFMA rate, but they
-are not equally close to the reference.  With `--dtype auto` (default) the bench measures BOTH -- argmax-mask mismatch fraction and
-max |dlogit| against the reference-run fixture tests/golden/ref_full_vitl16_480x480_k150.pt (made by /root/reference's own
+are not equally close to the reference.  With `--full --dtype auto` the bench measures BOTH -- argmax-mask mismatch fraction and
+max |dlogit| against the reference-run fixture tests/golden/ref_full_vitl16_480x480_k150.pt (made by the reference's own
 LSegNet.forward, oracle/make_ref_golden.py --full), and images/sec on the timed workload -- and times the headline on the one
 that meets <= 0.3 % mask flips at equal speed (>= 97 % of the faster one: the box-to-box spread of this bench is +-3 %, and fp16
 operands toggle more multiplier bits than bf16, which the chip's power management turns into ~2 % lower clocks on random data);
-both results are printed under `dtype_selection`.
+both results are printed under `dtype_selection`.  In a plain run `--dtype auto` is the drop-in's inference default
+(modules.models.lseg_net.DEFAULT_IMAGE_DTYPE, fp16, the type that selection picks: DESIGN.md par. 4), fixed without a
+measurement so that two runs with the same arguments time and compute the same thing.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
    or:   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
              --master-port P bench.py --gpus N --steps K --warmup W
 Multi-GPU = config 3: the image batch is sharded across ranks, weights replicated, NO data-path
@@ -64,8 +72,14 @@ def parse():
     ap.add_argument("--backbone", default="clip_vitl16_384")
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--dtype", default="auto", choices=["auto", "bf16", "fp16"],
-                    help="MFMA operand type of the image tower; auto = measure both, run the headline on the one that meets <= 0.3 %% "
-                         "argmax flips vs the reference-run fixture at equal speed")
+                    help="MFMA operand type of the image tower; auto = the drop-in's inference default (fp16) in a plain run, and with "
+                         "--full: measure both, run the headline on the one that meets <= 0.3 %% argmax flips vs the reference-run "
+                         "fixture at equal speed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits the last timed step returned to DIR/logits.npy (float32; a fixed seeded sample when the "
+                         "array exceeds 32 MB; DIR/logits_rank<r>.npy per rank when N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline (module docstring); the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-samples", type=int, default=3, help="timed CPU-baseline forwards (each ~5 s)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the batch sweep, the K=1000 leg and the training-step leg")
@@ -279,6 +293,68 @@ def time_forward(eng, x, steps, warmup, sync):
         eng.forward(x)
     sync()
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_ELEMENTS = 8 << 20          # fp32 elements written by --dump-outputs, all ranks together (32 MB)
+
+
+def dump_outputs(out_dir, logits, rank, world):
+    """--dump-outputs: the [B, K, H, W] fp32 logits the last timed step returned (what a caller of LSegNet.forward receives), as
+    DIR/logits.npy (DIR/logits_rank<r>.npy when N > 1).  Whole when they fit this rank's share of DUMP_ELEMENTS; otherwise the
+    elements at DUMP_ELEMENTS / N flat indices drawn by torch.randint from a CPU generator seeded 0 -- the same positions for every
+    build given the same arguments."""
+    import numpy as np
+    cap = DUMP_ELEMENTS // world
+    if logits.numel() > cap:
+        idx = torch.randint(0, logits.numel(), (cap,), generator=torch.Generator().manual_seed(0))
+        logits = logits.reshape(-1)[idx.to(logits.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy" if world == 1 else f"logits_rank{rank}.npy"), logits.cpu().numpy())
+
+
+def contract_line(args, K, B, world, dt, dtype, per_rank):
+    """The keys of the result line that a plain run and --full share; dt = seconds for args.steps timed steps (slowest rank)."""
+    return {
+        "metric": "images/sec at 480x480, ViT-L/16 + 150 ADE20K labels",
+        "value": round(world * B * args.steps / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[1]: {args.backbone} LSegNet.forward, {args.size}x{args.size}, "
+                               f"K={K} ADE20K labels, text tower recomputed every call",
+                   "per_gpu_batch": B, "global_batch": B * world, "labels": K,
+                   "parallelism": f"dp{world} (batch sharded, no collectives)"},
+        "per_rank_images_per_sec": [round(v, 1) for v in per_rank],
+        "commit": build_id(),
+    }
+
+
+def plain_run(args, cfg, sd, tok, x, sync, D, rank, world):
+    """The headline alone: one engine of the operand type `--dtype` names (auto = the drop-in's inference default), `--warmup` untimed
+    and `--steps` timed forwards, the last step's outputs, the line.  The engine's first forward is set-up, not warm-up: it loads the
+    code objects and sizes the caching allocator, which the --full path does in its untimed passes before the warm-up as well."""
+    from lseg_hip.engine import HipEngine
+    from modules.models.lseg_net import DEFAULT_IMAGE_DTYPE
+    dtype = DEFAULT_IMAGE_DTYPE if args.dtype == "auto" else args.dtype
+    K, B = tok.shape[0], x.shape[0]
+    eng = HipEngine(cfg, args.size, args.size, max_batch=B, max_labels=K, image_dtype=dtype)
+    eng.load_state_dict(sd)
+    eng.set_tokens(tok)
+    eng.forward(x)
+    for _ in range(args.warmup):
+        eng.forward(x)
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        out = eng.forward(x)
+    sync()
+    dt_local = time.perf_counter() - t0
+    dt = D.max_over_ranks(dt_local, device="cuda")
+    per_rank = D.gather_floats(B * args.steps / dt_local, device="cuda")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+    if rank == 0:
+        print(json.dumps(contract_line(args, K, B, world, dt, dtype, per_rank)), flush=True)
+    eng.close()
 
 
 _PARITY_SD = {}
@@ -528,6 +604,8 @@ def main():
         return launch_check(args)
     if args.pmc_child:
         return pmc_child(args)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the LSeg HIP engine has no CPU fallback")
     from lseg_hip import dist as D
@@ -560,6 +638,12 @@ def main():
         if dist is not None:
             dist.barrier()
             torch.cuda.synchronize()
+
+    if not args.full:
+        plain_run(args, cfg, sd, tok, x, sync, D, rank, world)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- MFMA operand type: parity against the reference-run fixture + a short timing probe of both, BEFORE the timed region -------
     headline = args.backbone == "clip_vitl16_384" and args.size == 480 and K == 150
@@ -630,6 +714,8 @@ def main():
     prof = {f: eng.profile(f) for f in ["forward"] + dom_fams}
     eng.set_profiling(False)
     dt = D.max_over_ranks(dt, device="cuda")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     assert torch.isfinite(out).all(), "non-finite logits"
     # Self-check outside the timed region: the tile configuration follows the problem size, so the batch the bench
     # times is checked against a single-image run of the same engine -- the configuration the oracle-parity tests
@@ -731,21 +817,12 @@ def main():
                                     for n_, v in parity_all.get(d, {}).items()}
             if e_:
                 sel[d] = e_
-        line = {
-            "metric": "images/sec at 480x480, ViT-L/16 + 150 ADE20K labels",
-            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": chosen, "data": "synthetic",
-            "config": {"workload": f"BASELINE configs[1]: {args.backbone} LSegNet.forward, {args.size}x{args.size}, "
-                                   f"K={K} ADE20K labels, text tower recomputed every call",
-                       "per_gpu_batch": B, "global_batch": B * world, "labels": K,
-                       "parallelism": f"dp{world} (batch sharded, no collectives)"},
-            "per_rank_images_per_sec": [round(v, 1) for v in per_rank],
+        line = contract_line(args, K, B, world, dt, chosen, per_rank)
+        line.update({
             "parity": parity.get(chosen),
             "miou_parity": "unavailable: no LSeg checkpoint and no ADE20K data in this environment (no network) -- parity is pinned on "
                            "reference-run fixtures with synthetic weights (tests/golden/ref_full_*.pt), mIoU itself is not measured",
             "parity_by_fixture": parity_all.get(chosen),
-            "commit": build_id(),
             "dtype_selection": sel,
             "path_tflops": round(world * gf_step / (ms * 1e-3) / 1e3, 2),
             "path_frac_of_mfma_peak": round(gf_step / (ms * 1e-3) / 1e3 / PEAK_BF16_TFLOPS, 4),
@@ -757,7 +834,7 @@ def main():
             "roofline": roof,
             "roofline_kernels": kern,
             "selfcheck_batch_vs_single_max_abs": round(selfcheck, 6),
-        }
+        })
     else:
         line = None
 

@@ -21,6 +21,13 @@ os.environ.setdefault("LSEG_DETERMINISTIC", "1")
 # this opt-in when neither `clip` nor the CLIP vocabulary is installed -- a real checkpoint must never be scored with them).
 os.environ.setdefault("LSEG_SYNTHETIC_TOKENS", "1")
 
+# The oracle fixture tests (tests/test_oracle_*golden.py) hold CPU results to within a few fp16 roundings of the stored ones, and the
+# summation order of torch's CPU kernels follows the intra-op thread count (at 4 threads tiny16_64x64_k5_arch1 misses its bar).  The
+# suite runs at the 8 threads the fixtures were made with, whatever the host's CPU count.
+import torch  # noqa: E402
+
+torch.set_num_threads(8)
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu via gpurun)")

@@ -6,7 +6,7 @@
 #   fast        pytest -m gpu_fast (~4 min: every operator test, one fixture per network family, one training fixture)
 #   full        the whole GPU suite (pytest -m gpu -x, ~11 min) + smoke
 #   smoke       __graft_entry__.smoke()
-#   bench       the default bench line (python bench.py) -> bench_line.json
+#   bench       the full bench line (python bench.py --full) -> bench_line.json
 #   profile     rocprofv3 --kernel-trace --stats of the bench command + the separate PMC passes -> rocprofv3_summary.txt, kernel_stats.csv, traffic.json
 #   train       tools/train_bench.py (20 steps), tools/train_loop_bench.py, the training kernel statistics and step table under rocprofv3
 #   asm         tools/gemm_asm_bench.py (the hand-scheduled residual GEMM against the generic kernels)
@@ -25,7 +25,7 @@ for task in "$@"; do
            ( timeout 100 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) > $O/smoke.log 2>&1
            cp gpurun_out/parity_table.txt gpurun_out/train_parity_table.txt $O/ 2>/dev/null; tail -6 $O/tests.log; cat $O/smoke.log ;;
     smoke) ( timeout 100 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) > $O/smoke.log 2>&1; cat $O/smoke.log ;;
-    bench) ( timeout 1200 python bench.py 2>$O/bench_stderr.log | grep "^{" ) > $O/bench_line.json; cut -c1-700 $O/bench_line.json ;;
+    bench) ( timeout 1200 python bench.py --full 2>$O/bench_stderr.log | grep "^{" ) > $O/bench_line.json; cut -c1-700 $O/bench_line.json ;;
     profile) bash tools/collect_profiles.sh fp16 $COMMIT > $O/collect.log 2>&1
            cp gpurun_out/profiles/traffic.json $O/traffic.json; cp gpurun_out/profiles/summary.txt $O/rocprofv3_summary.txt; cp gpurun_out/profiles/kernel_stats.csv $O/kernel_stats.csv
            head -40 $O/rocprofv3_summary.txt ;;
