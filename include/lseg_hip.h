@@ -139,7 +139,10 @@ int lseg_get_text_features(lseg_handle h, void* dev_out_f16 /* [K,out_c] fp16 */
 /* Zero-shot variant -- replaces: LSegNetZS.forward(x, class_info) (lseg_net_zs.py:177-214): every image brings
  * its OWN label set.  labels_per_image = k > 0: the K = B*k token rows are grouped per image, image b is
  * correlated with rows [b*k, (b+1)*k) only and lseg_forward writes [B,k,img_h,img_w]; 0 (default) = one
- * label set shared by the batch.  Takes effect at the next lseg_forward (which must be called with B = K/k). */
+ * label set shared by the batch.  Takes effect at the next lseg_forward (which must be called with B = K/k).
+ * Train mode (lseg_set_train) accepts k = 1..8 (larger k: LSEG_ERR_UNSUPPORTED) with arch_option 0: lseg_forward writes the
+ * [B,k,img_h,img_w] logits, lseg_train_loss / lseg_backward* take the loss over those k label planes per image (target values in
+ * [0, k), anything else ignored) and back-propagate through the per-image correlation (LSegmentationModuleZS.training_step). */
 int lseg_set_text_grouping(lseg_handle h, int labels_per_image);
 
 /* ---- forward -----------------------------------------------------------------------
@@ -378,6 +381,17 @@ int lseg_op_upsample2x_planes_backward_rows(const float* d_dout, void* d_rows, i
                                             void* stream);
 int lseg_op_l2norm_scale_backward(const void* d_da, int da_dtype, const float* d_x, void* d_dx, int dx_dtype, int M, int C, float scale,
                                   void* stream);
+/* Per-image label sets on the training path (LSegNetZS, lseg_net_zs.py:198-208; csrc/corr_group.hip), G = labels per image, 1..8.
+ * corr_group_fwd: d_low fp32 [B,G,hw] (fp16 values) = fp16(d_a16 fp16 [B*hw,C] . d_tnorm fp16 [B*G,C]^T) per image, fp32 accumulation
+ *   (the rounding points of the shared label set's correlation GEMM in the train-mode forward).
+ * corr_group_bwd: d_df [B*hw,C] (df_dtype, 16-bit) = backward of a = scale * f / ||f|| (d_feat fp32 [B*hw,C]) for
+ *   dA = rt(sum_k d_rows[row,k] T[b*G+k]) (fp32 accumulation, rt = rounding to rows_dtype); rows_dtype fp16: the gradient reaching f is
+ *   fp16(scale * dA) (the reference's half-precision head gradient), bf16: T is rounded to bf16 and the scale applied un-rounded
+ *   (lseg_config.flags bit 1).  d_rows [B*hw, ldk] 16-bit, ldk % 8 == 0, columns >= G ignored.  == lseg_op_gemm + lseg_op_l2norm_scale_backward
+ *   on the same operands, without dA in memory. */
+int lseg_op_corr_group_fwd(const void* d_a16, const void* d_tnorm, float* d_low, int B, int hw, int G, int C, void* stream);
+int lseg_op_corr_group_bwd(const void* d_rows, int rows_dtype, int ldk, const void* d_tnorm, const float* d_feat, void* d_df, int df_dtype,
+                           int B, int hw, int G, int C, float scale, void* stream);
 /* Fused backward of the loss the reference takes on the full-resolution logits -- CrossEntropyLoss(ignore_index)(output_conv(low)),
  * lsegmentation_module.py:72 on lseg_net.py:203 -- from the LOW-resolution logits d_low fp32 [B,K,h,w] and the target mask int64
  * [B,2h,2w]: the x2 bilinear, the softmax and the bilinear's transpose in registers, so the [B,K,2h,2w] logits and their gradient
@@ -399,7 +413,7 @@ int lseg_op_upsample_ce_backward_rows(const float* d_low, const int64_t* d_targe
  *                          caller's .grad tensor, typically a view into a flat bucket).  Unbound parameters get engine-owned buffers
  *                          (lseg_grad_ptr).  Trainable = pretrained.* and scratch.* tensors the forward touches; the CLIP text tower
  *                          is frozen (it is in no optimizer group of the reference) and its features are constants of the step.
- *   lseg_backward          after a train-mode lseg_forward: either dev_dlogits fp32 [B,K,H,W] (autograd hands it over), or
+ *   lseg_backward          after a train-mode lseg_forward: either dev_dlogits fp32 [B,K,H,W] ([B,k,H,W] with per-image label sets) (autograd hands it over), or
  *                          dev_target int64 [B,H,W] (then the loss is the mean CE over pixels != ignore_index and dev_loss, if not
  *                          NULL, receives double[2] = {sum of -log p[target], number of valid pixels}).  accumulate != 0 adds to the
  *                          gradient buffers (accumulate_grad_batches), 0 overwrites them.

@@ -599,4 +599,19 @@ int lseg_op_l2norm_scale_backward(const void* d_da, int da_dtype, const float* d
     return launch_l2norm_scale_backward(d_da, a, d_x, d_dx, b, M, C, scale, (hipStream_t)stream);
 }
 
+int lseg_op_corr_group_fwd(const void* d_a16, const void* d_tnorm, float* d_low, int B, int hw, int G, int C, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_a16 || !d_tnorm || !d_low) return set_error(LSEG_ERR_INVALID, "corr_group_fwd: NULL pointer");
+    return launch_corr_group_fwd(d_a16, d_tnorm, d_low, B, hw, G, C, (hipStream_t)stream);
+}
+
+int lseg_op_corr_group_bwd(const void* d_rows, int rows_dtype, int ldk, const void* d_tnorm, const float* d_feat, void* d_df, int df_dtype,
+                           int B, int hw, int G, int C, float scale, void* stream) {
+    int r = require_device(); if (r) return r;
+    int a, b;
+    if ((r = op_dt(rows_dtype, &a)) || (r = op_dt(df_dtype, &b))) return r;
+    if (!d_rows || !d_tnorm || !d_feat || !d_df) return set_error(LSEG_ERR_INVALID, "corr_group_bwd: NULL pointer");
+    return launch_corr_group_bwd(d_rows, a, ldk, d_tnorm, d_feat, d_df, b, B, hw, G, C, scale, (hipStream_t)stream);
+}
+
 }  // extern "C"

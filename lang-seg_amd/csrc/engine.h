@@ -191,6 +191,7 @@ private:
     bool train_alloc_ = false, train_fwd_valid_ = false;
     const int64_t* loss_target_ = nullptr; int loss_ignore_ = 0;      // train_loss() already ran seg_stats for this forward and this target
     int train_B_ = 0;
+    int train_G_ = 0;             // labels per image of the last train-mode forward (0: one label set shared by the batch)
     std::vector<BlockSave> sv_;
     float* xlast_ = nullptr;               // output of the last block (= xin of a virtual block `depth`)
     LevelSave lv_[4];

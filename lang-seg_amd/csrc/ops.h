@@ -58,6 +58,14 @@ int launch_bn_train_backward(const void* dy, const void* x, const float* stats, 
                              int B, int H, int W, int C, float eps, int dtype, hipStream_t st);
 int launch_relu_backward(const void* dy, const void* x, void* dx, size_t n, hipStream_t st);
 int launch_upsample2x_planes_backward_rows(const float* dout, void* rows, int B, int K, int H, int W, int ldk, int dtype, hipStream_t st);
+// corr_group.hip -- per-image label sets (LSegNetZS, lseg_net_zs.py:198-208) on the training path: G = labels per image, 1..CORR_GROUP_MAX
+constexpr int CORR_GROUP_MAX = 8;
+bool corr_group_supported(int G, int C);
+// low [B, G, hw] fp32 (fp16 values) = fp16(a16 [B*hw, C] . tnorm [B*G, C]^T per image), fp32 accumulation
+int launch_corr_group_fwd(const void* a16, const void* tnorm, float* low, int B, int hw, int G, int C, hipStream_t st);
+// df [B*hw, C] = L2-norm/scale backward (feat fp32) of dA = sum_k rows[:, k] T[b*G + k] -- the shared path's GEMM + l2norm_scale_backward
+int launch_corr_group_bwd(const void* rows, int rows_dtype, int ldk, const void* tnorm, const float* feat, void* df, int df_dtype, int B, int hw,
+                          int G, int C, float scale, hipStream_t st);
 int launch_l2norm_scale_backward(const void* da, int da_dtype, const float* x, void* dx, int dx_dtype, int M, int C, float scale, hipStream_t st);
 int launch_gelu_backward(const void* dy, const void* pre, void* dx, size_t n, int dtype, hipStream_t st, int quick = 0);
 int launch_upsample2x_nhwc_backward(const void* dout, void* din, int B, int H, int W, int C, int dtype, hipStream_t st);

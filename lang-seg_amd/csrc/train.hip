@@ -6,6 +6,7 @@
 // What the reference's autograd would traverse and what runs here:
 //   output_conv x2 bilinear, CrossEntropyLoss(ignore_index)      seg_stats (through the bilinear) + upsample_ce_bwd_rows on the low-res logits
 //   fp16 correlation, L2-norm, head1 (lseg_net.py:185-196)       two GEMMs + l2norm_scale_backward (fp16 roundings = identity)
+//   per-image correlation of LSegNetZS (lseg_net_zs.py:198-208)  corr_group.hip: grouped forward, fused dA + L2-norm backward
 //   4 x FeatureFusionBlock_custom (lseg_blocks.py:337-358)       out_conv GEMMs, x2 upsample transpose, RCU: conv dgrad = forward
 //     with ResidualConvUnit_custom in train() mode (:265-288)    conv on flipped weights, wgrad = one GEMM on transposed operands,
 //                                                                BatchNorm backward on batch statistics (SyncBatchNorm exchange hook)
@@ -295,8 +296,15 @@ int Engine::rcu_train(const uint16_t* in, const uint16_t* in_relu, Rcu& U, const
 int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t st) {
     const lseg_config& c = cfg;
     const int D = c.dim, H = c.heads, F = c.features, M = B * ntok_;
-    if (group_k > 0) return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets is not implemented");
     if (!train_alloc_) return set_error(LSEG_ERR_STATE, "train mode was not enabled (lseg_set_train)");
+    if (group_k > 0) {              // per-image label sets (LSegNetZS, lseg_net_zs.py:198-208): image b against token rows [b*k, (b+1)*k)
+        if (K_ != B * group_k)
+            return set_error(LSEG_ERR_INVALID, "grouped labels: %d token rows != B=%d x %d labels per image", K_, B, group_k);
+        if (c.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "per-image label sets have no head blocks (lseg_net_zs.py:177-214)");
+        if (!corr_group_supported(group_k, c.out_c))
+            return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
+                             CORR_GROUP_MAX, group_k);
+    }
     train_fwd_valid_ = false;
     loss_target_ = nullptr;
     last_B_ = B;
@@ -396,22 +404,29 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     g.bias = head1_.b; g.C = feat_; g.out_dtype = DT_F32; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
     TRY(launch_gemm(g, img_dt_, st));
     TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale, st));
-    gemm_args_init(g);
-    g.A = tnorm_; g.W = a16_; g.M = K_; g.N = Mp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
-    g.round_mid = 1; g.C = low_; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hw1;
-    TRY(launch_gemm(g, DT_F16, st));
-    // the text features as the dgrad operand of the correlation: bf16, transposed, K padded to the GEMM's K-step
-    const int Kp = (int)up64(K_);
-    if (cfg.flags & 2) {
-        TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
-        TRY(launch_transpose16(tn16_, tnT_, K_, c.out_c, c.out_c, Kp, st));
+    const int kout = group_k > 0 ? group_k : K_;             // label planes per image
+    if (group_k > 0) {
+        // per-image correlation (corr_group.hip): the same rounding points as the GEMM below; the grouped backward reads tnorm_ itself,
+        // so there is no transposed dgrad operand to make
+        TRY(launch_corr_group_fwd(a16_, tnorm_, low_, B, hw1, group_k, c.out_c, st));
     } else {
-        TRY(launch_transpose16(tnorm_, tnT_, K_, c.out_c, c.out_c, Kp, st));      // fp16 as it is: the reference's dgrad is a half x half product
+        gemm_args_init(g);
+        g.A = tnorm_; g.W = a16_; g.M = K_; g.N = Mp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
+        g.round_mid = 1; g.C = low_; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hw1;
+        TRY(launch_gemm(g, DT_F16, st));
+        // the text features as the dgrad operand of the correlation: bf16, transposed, K padded to the GEMM's K-step
+        const int Kp = (int)up64(K_);
+        if (cfg.flags & 2) {
+            TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
+            TRY(launch_transpose16(tn16_, tnT_, K_, c.out_c, c.out_c, Kp, st));
+        } else {
+            TRY(launch_transpose16(tnorm_, tnT_, K_, c.out_c, c.out_c, Kp, st));      // fp16 as it is: the reference's dgrad is a half x half product
+        }
     }
     // output_conv (x2 bilinear) only when the caller wants the logits: the loss and its gradient are taken on the low-resolution ones
-    if (logits) TRY(launch_upsample2x_planes(low_, logits, B * K_, h1, w1, st));
-    last_low_ = low_; last_kout_ = K_;
-    train_B_ = B;
+    if (logits) TRY(launch_upsample2x_planes(low_, logits, B * kout, h1, w1, st));
+    last_low_ = low_; last_kout_ = kout;
+    train_B_ = B; train_G_ = group_k;
     train_fwd_valid_ = true;
     TRY(zero_end(zero_fwd_));
     return 0;
@@ -705,7 +720,8 @@ int Engine::train_loss(const int64_t* target, int ignore_index, double* dev_loss
     if (!target) return set_error(LSEG_ERR_INVALID, "lseg_train_loss: target is NULL");
     LSEG_HIP_TRY(hipSetDevice(device));
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
-    TRY(launch_seg_stats_ex(low_, target, train_B_, K_, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+    const int kout = train_G_ > 0 ? train_G_ : K_;
+    TRY(launch_seg_stats_ex(low_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
     if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (dev_counts2) LSEG_HIP_TRY(hipMemcpyAsync(dev_counts2, counts_, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     loss_target_ = target; loss_ignore_ = ignore_index;
@@ -720,7 +736,9 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     LSEG_HIP_TRY(hipSetDevice(device));
     const lseg_config& c = cfg;
     const int B = train_B_, D = c.dim, F = c.features, M = B * ntok_, Mr = B * np_;
-    const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp1 = B * hw1, Kp = (int)up64(K_);
+    const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp1 = B * hw1;
+    // label planes per image and the row pitch of d(low): per-image sets (G <= 8) hand the grouped kernel one 16-byte row per pixel
+    const int G = train_G_, kout = G > 0 ? G : K_, Kp = G > 0 ? 8 : (int)up64(K_);
     const float logit_scale = expf(logf(1.0f / 0.07f));
     if (!acc) TRY(zero_begin(zero_bwd_, st));
     // The reference back-propagates through `logit_scale * image_features.half() @ text_features.t()` (lseg_net.py:194) in HALF precision:
@@ -733,20 +751,25 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     // ---- loss + x2 upsample^T: the correlation's dY rows ---------------------------------------------------------------------
     if (!dlogits) {      // CrossEntropyLoss(ignore_index) on output_conv(low): one pass for the loss and the per-pixel log-sum-exp, one for the rows
         if (!(loss_target_ == target && loss_ignore_ == ignore_index))      // else: lseg_train_loss left nll_ / lse_px_ of this forward and target
-            TRY(launch_seg_stats_ex(low_, target, B, K_, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
-        TRY(launch_upsample_ce_backward_rows(low_, target, lse_px_, nll_, drows_, B, K_, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
+            TRY(launch_seg_stats_ex(low_, target, B, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+        TRY(launch_upsample_ce_backward_rows(low_, target, lse_px_, nll_, drows_, B, kout, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
         if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     } else {             // autograd hand-over: d(logits) [B,K,2h,2w] given
         LSEG_HIP_TRY(hipMemsetAsync(drows_, 0, (size_t)Mp1 * Kp * 2, st));
-        TRY(launch_upsample2x_planes_backward_rows(dlogits, drows_, B, K_, h1, w1, Kp, hdt, st));
+        TRY(launch_upsample2x_planes_backward_rows(dlogits, drows_, B, kout, h1, w1, Kp, hdt, st));
     }
     // ---- head: correlation, L2-norm, head1 -------------------------------------------------------------------------------------
-    GemmArgs g;
-    gemm_args_init(g);
-    g.A = drows_; g.W = tnT_; g.M = Mp1; g.N = c.out_c; g.K = Kp; g.lda = Kp; g.ldw = Kp;
-    g.bias = zeros_; g.C = da_; g.out_dtype = hdt; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
-    TRY(launch_gemm(g, hdt, st));
-    TRY(launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, c.out_c, logit_scale, st));
+    if (G > 0) {
+        // per-image label sets: dA from the image's own G text rows, the scale and the L2-norm backward in one pass (corr_group.hip)
+        TRY(launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, G, c.out_c, logit_scale, st));
+    } else {
+        GemmArgs g;
+        gemm_args_init(g);
+        g.A = drows_; g.W = tnT_; g.M = Mp1; g.N = c.out_c; g.K = Kp; g.lda = Kp; g.ldw = Kp;
+        g.bias = zeros_; g.C = da_; g.out_dtype = hdt; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+        TRY(launch_gemm(g, hdt, st));
+        TRY(launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, c.out_c, logit_scale, st));
+    }
     TRY(lin_bwd(df_, Mp1, c.out_c, F, path_[0], head1_.wt, dpath0_, grad("scratch.head1.weight", (size_t)c.out_c * F),
                 grad("scratch.head1.bias", c.out_c), acc, st));
     // ---- refinenet1..4, reassemble -------------------------------------------------------------------------------------------

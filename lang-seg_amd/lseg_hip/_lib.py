@@ -109,6 +109,8 @@ SIGNATURES = {
     "lseg_op_eval_accumulate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_l2norm_scale_backward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "lseg_op_corr_group_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_corr_group_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_gelu_backward": (_i, [_vp, _vp, _vp, C.c_int64, _i, _vp]),
     "lseg_op_upsample2x_nhwc_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_softmax_ce_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -1,25 +1,23 @@
-"""LSegModuleZS -- the reference's zero-shot module surface (modules/lseg_module_zs.py:20-73), network side only.
+"""LSegModuleZS -- the reference's zero-shot module surface (modules/lseg_module_zs.py:20-73).
 
 `LSegModuleZS(data_path, dataset, batch_size, base_lr, max_epochs, **kwargs)` builds `self.net = LSegNetZS(label_list=...)`
 from `label_files/fewshot_<dataset>.txt` (get_labels, :60-71) and forwards `(x, class_info)` to it
-(lsegmentation_module_zs.py:82-83).  The few-shot episode loaders / Evaluator of lsegmentation_module_zs.py and
-fewshot_data/ are host-side data plumbing outside the hot path and are not mirrored (SURVEY.md §8 out of scope).
+(lsegmentation_module_zs.py:82-83).  Criterion, training_step and configure_optimizers come from LSegmentationModuleZS
+(modules/lsegmentation_module_zs.py), as in the reference.  The few-shot episode loaders / Evaluator of lsegmentation_module_zs.py
+and fewshot_data/ are host-side data plumbing outside the hot path and are not mirrored (SURVEY.md §8 out of scope).
 """
 import os
 
-import torch
-
+from .lsegmentation_module_zs import LSegmentationModuleZS
 from .models.lseg_net_zs import LSegNetZS, LSegRNNetZS
 
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-class LSegModuleZS(torch.nn.Module):
+class LSegModuleZS(LSegmentationModuleZS):
     def __init__(self, data_path, dataset, batch_size, base_lr, max_epochs, **kwargs):
-        super().__init__()
-        self.data_path, self.dataset = data_path, dataset
-        self.batch_size, self.base_lr, self.max_epochs = batch_size, base_lr, max_epochs
-        self.other_kwargs = kwargs
+        super().__init__(data_path, dataset, batch_size, base_lr, max_epochs, **kwargs)
+        self.max_epochs = max_epochs
         label_list = self.get_labels(dataset)
         self.len_dataloader = len(label_list)
         use_pretrained = kwargs.get("use_pretrained", True) in ("True", True)
@@ -39,5 +37,3 @@ class LSegModuleZS(torch.nn.Module):
         with open(path, "r") as f:
             return [line.strip() for line in f.readlines()]
 
-    def forward(self, x, class_info):                   # lsegmentation_module_zs.py:82-83
-        return self.net(x, class_info)

@@ -58,8 +58,9 @@ class EngineSGD(torch.optim.SGD):
     def _fusable(self, eng=None):
         """The fused lseg_sgd_step assigns the two learning rates by KEY PREFIX (pretrained.* / scratch.*): it may only replace torch's
         step when the optimizer's groups are exactly those two sets, every parameter of them trainable, equal hyper-parameters otherwise.
-        A caller who regrouped, froze or added parameters gets torch.optim.SGD."""
-        g = self.param_groups
+        A caller who regrouped, froze or added parameters gets torch.optim.SGD.  Groups without parameters count as absent
+        (the zero-shot module's `auxlayer` group, lsegmentation_module_zs.py:258-262: an Interpolate holds none)."""
+        g = self._live_groups()
         if len(g) != 2:
             return False
         same = all(g[0][k] == g[1][k] for k in ("momentum", "weight_decay", "dampening", "nesterov"))
@@ -84,6 +85,9 @@ class EngineSGD(torch.optim.SGD):
                             for k in (groups[0] | groups[1]))
             self._fusable_cache = (key, ok)
         return self._fusable_cache[1]
+
+    def _live_groups(self):
+        return [x for x in self.param_groups if len(x["params"]) > 0]
 
     @staticmethod
     def _never_has_grad(key):
@@ -142,7 +146,7 @@ class EngineSGD(torch.optim.SGD):
             self._push_momentum(eng, {params[id(p)]: st["momentum_buffer"] for p, st in self.state.items()
                                       if "momentum_buffer" in st and id(p) in params})
             self.state.clear()
-        g = self.param_groups
+        g = self._live_groups()
         eng.sgd_step(g[0]["lr"], g[1]["lr"], g[0]["momentum"], g[0]["weight_decay"])
         ts.sgd_steps += 1
         ts.fresh = False

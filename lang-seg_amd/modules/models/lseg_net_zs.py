@@ -6,6 +6,11 @@ use_pretrained=True, **kwargs)`), same module tree / state-dict keys as LSegNet,
 ['others', label_list[class_info[b]]] (`self.texts`, lseg_net_zs.py:170-176, 178).  The arithmetic runs in the HIP engine
 with per-image label grouping (include/lseg_hip.h: lseg_set_text_grouping); there is no PyTorch fallback.
 
+Training (LSegmentationModuleZS.training_step, modules/lsegmentation_module_zs.py): under net.train() with grad enabled the
+forward is the engine's train-mode step with the same grouping -- one autograd node whose backward is lseg_backward(d logits), exactly
+as LSegNet's -- and `forward_loss(x, class_info, target)` is criterion(forward(x, class_info), target) as ONE node (fused
+cross-entropy over the 2 label planes, no [B, 2, H, W] logits).
+
 Only the ViT backbones are implemented (clip_vitl16_384, clip_vitb32_384); the reference's clip_resnet101 / RN50x*
 variants (LSegRNNetZS, lseg_net_zs.py:243-363) raise.
 """
@@ -18,7 +23,7 @@ import torch.nn as nn
 from lseg_hip.config import get_config
 from lseg_hip.tokenizer import tokenize
 from .lseg_blocks import Interpolate, _make_encoder
-from .lseg_net import BaseModel, default_image_dtype, LSeg as _LSegShared, _make_fusion_block, _new_shared
+from .lseg_net import BaseModel, default_image_dtype, LSeg as _LSegShared, _make_fusion_block, _new_shared, _EngineTrainFn, _EngineLossFn
 
 
 class LSeg(_LSegShared):
@@ -59,22 +64,55 @@ class LSeg(_LSegShared):
         ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
         if not x.is_cuda:
             raise RuntimeError("LSegNetZS.forward needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
-        if self.training and torch.is_grad_enabled():
-            raise NotImplementedError("the HIP engine implements the inference forward only -- call .eval()")
         B, _, H, W = x.shape
         if len(ids) != B:
             raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
+        if self.training and torch.is_grad_enabled():                         # training_step (lsegmentation_module_zs.py:86-155)
+            eng, keys, params = self._train_inputs(x, ids)
+            return _EngineTrainFn.apply(x.float(), self, eng, keys, *params)
         text = torch.cat([self.texts[c] for c in ids], dim=0)                 # [2B, ctx]; :178
         eng = self._engine(B, H, W, text.shape[0], x.device)
+        if eng.training:
+            eng.set_train(False)
+        self._set_group_tokens(eng, text, ids)
+        out = eng.forward(x.float())                                          # [B, 2, H, W]
+        if self._range_guard(eng, x.device):
+            return self.forward(x, class_info)                                # fp16 overflowed: again on bf16 operands (loud)
+        return out
+
+
+    def _set_group_tokens(self, eng, text, ids):
         tkey = ("zs", tuple(ids))
         if eng._tok != tkey:
             eng.set_tokens(text, labels_per_image=2)
             eng._tok = tkey
         eng.set_text_cache(bool(self.cache_text))
-        out = eng.forward(x.float())                                          # [B, 2, H, W]
-        if self._range_guard(eng, x.device):
-            return self.forward(x, class_info)                                # fp16 overflowed: again on bf16 operands (loud)
-        return out
+
+    def _train_inputs(self, x, class_info):
+        """The train-mode engine of this batch shape with the per-image token pairs set (LSeg._train_inputs with class_info in place
+        of a label set): the text tower still runs per step on its side stream -- the pairs change with class_info."""
+        if not x.is_cuda:
+            raise RuntimeError("LSegNetZS needs CUDA/HIP tensors (no CPU path)")
+        ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
+        B, _, H, W = x.shape
+        if len(ids) != B:
+            raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
+        text = torch.cat([self.texts[c] for c in ids], dim=0)
+        eng = self._train_engine(B, H, W, text.shape[0], x.device)
+        self._set_group_tokens(eng, text, ids)
+        if eng._nbt:
+            torch._foreach_add_(eng._nbt, 1)             # nn.BatchNorm2d.num_batches_tracked
+        self.invalidate_engines(except_=eng)             # train-mode BatchNorm moves the running statistics through raw pointers
+        return eng, tuple(k for k, _ in eng._named), [p for _, p in eng._named]
+
+    def forward_loss(self, x, class_info, target, ignore_index=-100):
+        """`criterion(self(x, class_info), target)` of LSegmentationModuleZS (nn.CrossEntropyLoss() over [B, 2, H*W]: mean over the
+        pixels != ignore_index, torch's default -100) as ONE autograd node on the engine: no [B, 2, H, W] logits; `loss.backward()`
+        runs lseg_backward_scaled.  Leaves {correct, labeled} of the batch in `self._last_train_counts` (int64[2], device)."""
+        if not (self.training and torch.is_grad_enabled()):
+            raise RuntimeError("forward_loss is the training-step path: call it under net.train() with grad enabled")
+        eng, keys, params = self._train_inputs(x, class_info)
+        return _EngineLossFn.apply(x.float(), target, self, eng, keys, int(ignore_index), *params)
 
 
 class LSegNetZS(LSeg):
