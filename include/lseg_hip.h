@@ -96,7 +96,13 @@ typedef struct {
                                * rows summed in a fixed order instead of fp32 atomics: two runs of the same step on the same inputs
                                * give BIT-identical gradients (what torch.use_deterministic_algorithms buys the reference's
                                * training loop, modules/lsegmentation_module.py:66-81); one small extra launch per sum, no measurable cost per step (the
-                               * Python front sets it by default: lseg_hip/engine.py, LSEG_DETERMINISTIC=0 clears it) */
+                               * Python front sets it by default: lseg_hip/engine.py, LSEG_DETERMINISTIC=0 clears it)
+                               * bit 4 (training): train the arch_option 1/2 head blocks (lseg_net.py:43-79,198-201).  Without it
+                               * lseg_set_train refuses arch_option 1/2; with it the train-mode forward keeps every block's output,
+                               * n = max(block_depth - 1, 0) + 1 extra fp32 [max_batch, max_labels, h, w] plane sets (276 MB each at 8 x
+                               * 150 labels, 480x480), and lseg_backward returns the gradient of scratch.head_block.depthwise.depthwise.
+                               * {weight, bias} (bucket 0) -- always in a fixed summation order, bit 3 or not.  Not with per-image label
+                               * sets (the zero-shot network has no head blocks). */
 } lseg_config;
 
 typedef struct lseg_engine* lseg_handle;
@@ -140,7 +146,7 @@ int lseg_get_text_features(lseg_handle h, void* dev_out_f16 /* [K,out_c] fp16 */
  * its OWN label set.  labels_per_image = k > 0: the K = B*k token rows are grouped per image, image b is
  * correlated with rows [b*k, (b+1)*k) only and lseg_forward writes [B,k,img_h,img_w]; 0 (default) = one
  * label set shared by the batch.  Takes effect at the next lseg_forward (which must be called with B = K/k).
- * Train mode (lseg_set_train) accepts k = 1..8 (larger k: LSEG_ERR_UNSUPPORTED) with arch_option 0: lseg_forward writes the
+ * Train mode (lseg_set_train) accepts k = 1..8 (larger k: LSEG_ERR_UNSUPPORTED) with arch_option 0 only: lseg_forward writes the
  * [B,k,img_h,img_w] logits, lseg_train_loss / lseg_backward* take the loss over those k label planes per image (target values in
  * [0, k), anything else ignored) and back-propagate through the per-image correlation (LSegmentationModuleZS.training_step). */
 int lseg_set_text_grouping(lseg_handle h, int labels_per_image);
@@ -400,6 +406,22 @@ int lseg_op_corr_group_bwd(const void* d_rows, int rows_dtype, int ldk, const vo
  * correlation backward consumes (all ldk columns written, zeros beyond K; ldk % 8 == 0), d_lse_ws fp32 [B*2h*2w] scratch. */
 int lseg_op_upsample_ce_backward_rows(const float* d_low, const int64_t* d_target, int B, int K, int h, int w, int ignore_index,
                                       double* d_nll, float* d_lse_ws, void* d_rows, int ldk, int out_dtype, void* stream);
+/* The same gradient as fp32 PLANES d_planes [B,K,h,w] (the input of the head blocks' backward) and, if d_ksum is not NULL, its per-pixel
+ * sum over the labels d_ksum [B,h,w] (what a bottleneck block routes to its arg-max label).  Rounded to fp16 and transposed, d_planes
+ * equals the d_rows of lseg_op_upsample_ce_backward_rows. */
+int lseg_op_upsample_ce_backward_planes(const float* d_low, const int64_t* d_target, int B, int K, int h, int w, int ignore_index,
+                                        double* d_nll, float* d_lse_ws, float* d_planes, float* d_ksum, void* stream);
+/* Backward of ONE arch_option 1/2 head block (lseg_net.py:43-79; csrc/head_train.hip) on fp32 planes [B,K,H,W]:
+ *   forward  z = conv2d(in[b,k], w9 [3x3], bias) (+ max_k in[b,:,p] if bottleneck),  out = act(z) if apply_act else z
+ *   d_dy = d out; d_out_saved = out (needed when apply_act; act 0 relu, 1 leaky_relu(0.01), 2 tanh, derivative from the output).
+ *   d_dx: dx_dtype LSEG_F32 = planes [B,K,H,W]; LSEG_F16 / LSEG_BF16 = rows [B*H*W, ldk] (ldk % 8 == 0, >= K, zeros beyond K), the
+ *   layout and rounding the correlation backward reads.  The bottleneck's max routes sum_k dz[b,k,p] to the FIRST maximal k (torch.max).
+ *   d_dw [9], d_db [1]: written (accumulate 0) or added to (accumulate 1), summed in a fixed order (bit-reproducible).
+ *   d_ws (optional, ws_floats >= lseg_op_head_block_backward_ws(...) floats): scratch; NULL = allocated on the stream. */
+size_t lseg_op_head_block_backward_ws(int B, int K, int H, int W, int apply_act);
+int lseg_op_head_block_backward(const float* d_in, const float* d_out_saved, const float* d_dy, const float* d_w9, int B, int K, int H, int W,
+                                int bottleneck, int act, int apply_act, void* d_dx, int dx_dtype, int ldk, float* d_dw, float* d_db,
+                                int accumulate, float* d_ws, int64_t ws_floats, void* stream);
 
 /* ---- training step ------------------------------------------------------------------------------------------------------------
  * replaces: LSegmentationModule.training_step (modules/lsegmentation_module.py:66-81) -- `out = self(img)` in train() mode,
@@ -409,6 +431,7 @@ int lseg_op_upsample_ce_backward_rows(const float* d_low, const int64_t* d_targe
  *
  *   lseg_set_train(h, 1)   net.train(): lseg_forward keeps the activations the backward needs, the refinenets' BatchNorm uses batch
  *                          statistics and updates running_mean / running_var IN the caller's bound tensors (momentum 0.1).  bf16 only.
+ *                          arch_option 1/2 (head blocks) needs lseg_config.flags bit 4, else LSEG_ERR_UNSUPPORTED.
  *   lseg_bind_grad         where the gradient of parameter `key` is written: fp32, same shape/layout as the bound parameter (the
  *                          caller's .grad tensor, typically a view into a flat bucket).  Unbound parameters get engine-owned buffers
  *                          (lseg_grad_ptr).  Trainable = pretrained.* and scratch.* tensors the forward touches; the CLIP text tower

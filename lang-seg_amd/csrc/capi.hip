@@ -614,4 +614,51 @@ int lseg_op_corr_group_bwd(const void* d_rows, int rows_dtype, int ldk, const vo
     return launch_corr_group_bwd(d_rows, a, ldk, d_tnorm, d_feat, d_df, b, B, hw, G, C, scale, (hipStream_t)stream);
 }
 
+size_t lseg_op_head_block_backward_ws(int B, int K, int H, int W, int apply_act) {
+    if (B < 1 || K < 1 || H < 1 || W < 1) return 0;
+    return (apply_act ? (size_t)B * K * H * W : 0) + 2 * (size_t)B * H * W + 10 * head_block_bwd_partials(B, H, W);
+}
+
+int lseg_op_head_block_backward(const float* d_in, const float* d_out_saved, const float* d_dy, const float* d_w9, int B, int K, int H, int W,
+                                int bottleneck, int act, int apply_act, void* d_dx, int dx_dtype, int ldk, float* d_dw, float* d_db,
+                                int accumulate, float* d_ws, int64_t ws_floats, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dx_dtype, &dt))) return r;
+    if (!d_in || !d_dy || !d_w9 || !d_dx || !d_dw || !d_db || (apply_act && !d_out_saved))
+        return set_error(LSEG_ERR_INVALID, "head_block_backward: NULL pointer");
+    if (B < 1 || K < 1 || H < 1 || W < 1) return set_error(LSEG_ERR_INVALID, "head_block_backward: bad shape");
+    if ((bottleneck != 0 && bottleneck != 1) || act < 0 || act > 2) return set_error(LSEG_ERR_INVALID, "head_block_backward: bottleneck %d, act %d", bottleneck, act);
+    if (dt != DT_F32 && (ldk < K || (ldk & 7))) return set_error(LSEG_ERR_INVALID, "head_block_backward: ldk=%d must be a multiple of 8 and >= K=%d", ldk, K);
+    const int64_t need = (int64_t)lseg_op_head_block_backward_ws(B, K, H, W, apply_act);
+    if (d_ws && ws_floats < need) return set_error(LSEG_ERR_INVALID, "head_block_backward: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = d_ws;
+    if (!ws) LSEG_HIP_TRY(hipMallocAsync((void**)&ws, (size_t)need * sizeof(float), st));
+    const size_t n = (size_t)B * K * H * W, np = (size_t)B * H * W;
+    float* dz = apply_act ? ws : nullptr;
+    float* ksum = ws + (apply_act ? n : 0);
+    int* kstar = reinterpret_cast<int*>(ksum + np);
+    float* part = ksum + 2 * np;
+    r = launch_head_bwd_prep(d_dy, d_out_saved, d_in, dz, bottleneck ? ksum : nullptr, bottleneck ? kstar : nullptr, B, K, H * W, act, apply_act, st);
+    if (!r) r = launch_head_block_backward(apply_act ? dz : d_dy, ksum, kstar, d_in, d_w9, d_dx, dt, ldk, -1, nullptr, part, B, K, H, W, bottleneck, st);
+    if (!r) r = launch_head_dw_reduce(part, (int)head_block_bwd_partials(B, H, W), d_dw, d_db, accumulate, st);
+    if (!d_ws) (void)hipFreeAsync(ws, st);
+    return r;
+}
+
+int lseg_op_upsample_ce_backward_planes(const float* d_low, const int64_t* d_target, int B, int K, int h, int w, int ignore_index,
+                                        double* d_nll, float* d_lse_ws, float* d_planes, float* d_ksum, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_low || !d_target || !d_nll || !d_lse_ws || !d_planes) return set_error(LSEG_ERR_INVALID, "upsample_ce_backward_planes: NULL pointer");
+    if (B < 1 || K < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "upsample_ce_backward_planes: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* counts = nullptr;
+    LSEG_HIP_TRY(hipMallocAsync((void**)&counts, (size_t)(2 + 3 * K) * sizeof(unsigned long long), st));
+    r = launch_seg_stats_ex(d_low, d_target, B, K, 4 * h * w, ignore_index, counts, d_nll, nullptr, 1, h, w, st, d_lse_ws);
+    if (!r) r = launch_upsample_ce_backward_planes(d_low, d_target, d_lse_ws, d_nll, d_planes, d_ksum, B, K, h, w, ignore_index, st);
+    (void)hipFreeAsync(counts, st);
+    return r;
+}
+
 }  // extern "C"

@@ -1489,6 +1489,8 @@ __global__ void relu_backward_add_kernel(const uint16_t* __restrict__ dy, const 
 // x2 bilinear (align_corners=True) backward of the logit planes, written straight as the GEMM operand of the correlation
 // backward: d_low_rows[(b*h*w + p), k] (16-bit, leading dimension ldk >= K; padding columns must be pre-zeroed) from
 // d_out [B,K,2h,2w] fp32 -- the transpose of upsample2x_planes_kernel (output_conv) fused with the planes->rows re-layout.
+// PLANES: d_low written as fp32 planes [B,K,H,W] instead (the head blocks' backward consumes planes; `rows` is then a float*).
+template <bool PLANES>
 __global__ void upsample2x_planes_bwd_rows_kernel(const float* __restrict__ dout, uint16_t* __restrict__ rows, int B, int K, int H, int W,
                                                   int ldk, int dtype) {
     const int Ho = 2 * H, Wo = 2 * W;
@@ -1517,7 +1519,8 @@ __global__ void upsample2x_planes_bwd_rows_kernel(const float* __restrict__ dout
                 if (wx != 0.f) acc += wy * wx * plane[(size_t)yo * Wo + xo];
             }
         }
-        store_from_f32(rows, ((size_t)b * H * W + (size_t)y * W + x) * ldk + k, dtype, acc);
+        if (PLANES) reinterpret_cast<float*>(rows)[i] = acc;
+        else store_from_f32(rows, ((size_t)b * H * W + (size_t)y * W + x) * ldk + k, dtype, acc);
     }
 }
 // Fused backward of  CrossEntropyLoss(ignore_index)( output_conv(low) )  (lsegmentation_module.py:72 on lseg_net.py:203): the rows
@@ -1528,10 +1531,14 @@ __global__ void upsample2x_planes_bwd_rows_kernel(const float* __restrict__ dout
 //                    w(P -> y,x) * (exp(z_k(P) - lse(P)) - [k = t(P)]) / n_valid,     z_k(P) = the x2 bilinear of low[b,k] at P.
 // With align_corners=True and an exact x2 grid the rows touching y are Y in [2y-1, 2y+2] (checked on the host for the geometry at
 // hand), and every tap of those rows lies in the 3x3 neighbourhood of (y,x): one lane = one low-resolution pixel, 9 loads per class.
+// PLANES: d_low as fp32 planes [B,K,H,W] (`rows` is then a float*, ldk ignored) for the head blocks' backward, and ksum (optional)
+// [B,H,W] = sum over k of d_low at each pixel (what a bottleneck block routes to its max label).
+template <bool PLANES>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* __restrict__ low, const long long* __restrict__ target,
                                                                    const float* __restrict__ lse, const double* __restrict__ nll,
                                                                    uint16_t* __restrict__ rows, int B, int K, int H, int W, int ldk,
-                                                                   int ignore_index, int dtype, const float* __restrict__ gscale) {
+                                                                   int ignore_index, int dtype, const float* __restrict__ gscale,
+                                                                   float* __restrict__ ksum = nullptr) {
     const int Ho = 2 * H, Wo = 2 * W;
     const size_t npix = (size_t)B * H * W;
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -1587,7 +1594,9 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* 
     const int ro[3] = {ya * W, y * W, yb * W}, co[3] = {xa, x, xb};
     const float* plane = low + (size_t)b * K * H * W;
     uint16_t* orow = rows + i * (size_t)ldk;
-    for (int k0 = 0; k0 < ldk; k0 += 8) {
+    float* oplanes = reinterpret_cast<float*>(rows) + (size_t)b * K * H * W + (size_t)y * W + x;
+    float ks = 0.f;
+    for (int k0 = 0; k0 < (PLANES ? K : ldk); k0 += 8) {
         float out[8];
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk) {
@@ -1620,9 +1629,16 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* 
             }
             out[kk] = acc;
         }
-        *reinterpret_cast<uint4*>(orow + k0) = make_uint4(pack2_dt(out[0], out[1], dtype), pack2_dt(out[2], out[3], dtype),
-                                                          pack2_dt(out[4], out[5], dtype), pack2_dt(out[6], out[7], dtype));
+        if (PLANES) {
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+                if (k0 + kk < K) { oplanes[(size_t)(k0 + kk) * H * W] = out[kk]; ks += out[kk]; }
+        } else {
+            *reinterpret_cast<uint4*>(orow + k0) = make_uint4(pack2_dt(out[0], out[1], dtype), pack2_dt(out[2], out[3], dtype),
+                                                              pack2_dt(out[4], out[5], dtype), pack2_dt(out[6], out[7], dtype));
+        }
     }
+    if (PLANES && ksum) ksum[i] = ks;
 }
 // backward of a = scale * x / ||x||_2 (row-wise; the fp16 roundings of the forward are treated as identity):
 //   dx = (scale / ||x||) * (da - xh * (xh . da)),  xh = x / ||x||      x fp32 [M,C], da 16-bit, dx 16-bit
@@ -2430,8 +2446,14 @@ int launch_relu_backward_add(const void* dy, const void* x, const void* add, voi
 }
 int launch_upsample2x_planes_backward_rows(const float* dout, void* rows, int B, int K, int H, int W, int ldk, int dtype, hipStream_t st) {
     if (ldk < K) return set_error(LSEG_ERR_INVALID, "upsample2x_planes backward: ldk=%d < K=%d", ldk, K);
-    hipLaunchKernelGGL(upsample2x_planes_bwd_rows_kernel, dim3(grid_for((size_t)B * K * H * W)), dim3(256), 0, st, dout, (uint16_t*)rows,
+    hipLaunchKernelGGL(upsample2x_planes_bwd_rows_kernel<false>, dim3(grid_for((size_t)B * K * H * W)), dim3(256), 0, st, dout, (uint16_t*)rows,
                        B, K, H, W, ldk, dtype);
+    CHECK_LAUNCH();
+    return 0;
+}
+int launch_upsample2x_planes_backward_planes(const float* dout, float* planes, int B, int K, int H, int W, hipStream_t st) {
+    hipLaunchKernelGGL(upsample2x_planes_bwd_rows_kernel<true>, dim3(grid_for((size_t)B * K * H * W)), dim3(256), 0, st, dout, (uint16_t*)planes,
+                       B, K, H, W, 0, (int)DT_F32);
     CHECK_LAUNCH();
     return 0;
 }
@@ -2453,8 +2475,19 @@ int launch_upsample_ce_backward_rows(const float* low, const int64_t* target, co
     if (ldk < K || (ldk & 7)) return set_error(LSEG_ERR_INVALID, "fused CE backward: ldk=%d must be a multiple of 8 and >= K=%d", ldk, K);
     if (!x2_footprint_is_4(H) || !x2_footprint_is_4(W)) return set_error(LSEG_ERR_UNSUPPORTED, "fused CE backward: %dx%d map outside the 4-tap footprint", H, W);
     const size_t npix = (size_t)B * H * W;
-    hipLaunchKernelGGL(upsample_ce_bwd_rows_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, low,
-                       reinterpret_cast<const long long*>(target), lse, nll, (uint16_t*)rows, B, K, H, W, ldk, ignore_index, dtype, gscale);
+    hipLaunchKernelGGL(upsample_ce_bwd_rows_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, low,
+                       reinterpret_cast<const long long*>(target), lse, nll, (uint16_t*)rows, B, K, H, W, ldk, ignore_index, dtype, gscale,
+                       nullptr);
+    CHECK_LAUNCH();
+    return 0;
+}
+int launch_upsample_ce_backward_planes(const float* low, const int64_t* target, const float* lse, const double* nll, float* planes, float* ksum,
+                                       int B, int K, int H, int W, int ignore_index, hipStream_t st, const float* gscale) {
+    if (!x2_footprint_is_4(H) || !x2_footprint_is_4(W)) return set_error(LSEG_ERR_UNSUPPORTED, "fused CE backward: %dx%d map outside the 4-tap footprint", H, W);
+    const size_t npix = (size_t)B * H * W;
+    hipLaunchKernelGGL(upsample_ce_bwd_rows_kernel<true>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, low,
+                       reinterpret_cast<const long long*>(target), lse, nll, (uint16_t*)planes, B, K, H, W, 0, ignore_index, (int)DT_F32, gscale,
+                       ksum);
     CHECK_LAUNCH();
     return 0;
 }

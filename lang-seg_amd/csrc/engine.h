@@ -74,6 +74,8 @@ public:
     int grad_ptr(const char* key, float** out, size_t* n);
     int backward(const float* dlogits, const int64_t* target, int ignore_index, int accumulate, double* dev_loss2, hipStream_t st,
                  const float* dev_grad_scale = nullptr);
+    int head_blocks_backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
+                             const float* dev_grad_scale, int hdt, int Kp);
     int train_loss(const int64_t* target, int ignore_index, double* dev_loss2, int64_t* dev_counts2, hipStream_t st);
     int sgd_momentum(const char* key, float** out, size_t* n);
     int sgd_mark_initialized(bool on) { sgd_first_ = !on; return 0; }
@@ -198,6 +200,13 @@ private:
     uint16_t *dmapA_[4] = {}, *dmapB_[4] = {}, *dmapC_[4] = {}, *dmapD_[4] = {};   // gradient maps per pyramid level (padded NHWC, zero border)
     uint16_t *dpath_[4] = {};              // d path_{l+1}: aliases the level-(l-1) map it is produced in
     uint16_t *dpath0_ = nullptr;           // d path_1 rows [B*4*h*w, F]
+    // arch_option 1/2 head blocks in train mode (lseg_config.flags bit 4; head_train.hip): n applications of the shared block
+    int hb_n_ = 0;                         // 0: no head blocks are trained
+    std::vector<float*> hb_out_;           // saved block outputs x_1..x_n, fp32 planes [B,K,h,w] each
+    int* hb_kstar_ = nullptr;              // bottleneck: first arg-max label of each block's input, [n][B*h*w]
+    float* hb_ks_[2] = {};                 // bottleneck: per-pixel label sums of the gradient planes (ping-pong)
+    float* hb_part_ = nullptr;             // {dW, db} partial rows of the n block backwards
+    const float* train_out_ = nullptr;     // head output of the last train-mode forward (low_ without head blocks)
     uint16_t *drn_[4] = {}, *dL_[4] = {};
     uint16_t *rowsA_ = nullptr, *rowsB_ = nullptr;  // row-major 16-bit temporaries (GEMM operand views of gradient maps)
     uint16_t *ddil_ = nullptr, *dtmp_ = nullptr;    // stride-2 reassemble conv: dilated dY, d(1x1 output)

@@ -58,6 +58,23 @@ int launch_bn_train_backward(const void* dy, const void* x, const float* stats, 
                              int B, int H, int W, int C, float eps, int dtype, hipStream_t st);
 int launch_relu_backward(const void* dy, const void* x, void* dx, size_t n, hipStream_t st);
 int launch_upsample2x_planes_backward_rows(const float* dout, void* rows, int B, int K, int H, int W, int ldk, int dtype, hipStream_t st);
+// the same transpose written as fp32 planes [B,K,H,W] (the head blocks' backward input)
+int launch_upsample2x_planes_backward_planes(const float* dout, float* planes, int B, int K, int H, int W, hipStream_t st);
+// head_train.hip -- arch_option 1/2 head blocks on the training path (lseg_net.py:43-79,198-201)
+// forward of one block = launch_head_block's arithmetic, plus kstar [B,H,W] = first arg-max label of `in` (bottleneck; may be NULL)
+int launch_head_block_train(const float* in, float* out, int* kstar, const float* w9, const float* bias, int B, int K, int H, int W,
+                            int bottleneck, int act, int apply_act, hipStream_t st);
+// per pixel: dz = act'(y) dy (apply_act) or dy (dz optional, may alias dy), ksum = sum_k dz, kstar = first arg-max of x (each optional)
+int launch_head_bwd_prep(const float* dy, const float* y, const float* x, float* dz, float* ksum, int* kstar, int B, int K, int HW, int act,
+                         int apply_act, hipStream_t st);
+// partial rows of 10 floats one launch_head_block_backward writes
+size_t head_block_bwd_partials(int B, int H, int W);
+// backward of one block from dz (its pre-activation gradient): dx -> fp32 planes (out_dtype DT_F32; times act'(x) when lower_act >= 0,
+// label sums in ksum_out) or 16-bit rows [B*H*W, ldk]; {dW, db} partial rows -> partial
+int launch_head_block_backward(const float* dz, const float* ksum, const int* kstar, const float* x, const float* w9, void* out, int out_dtype,
+                               int ldk, int lower_act, float* ksum_out, float* partial, int B, int K, int H, int W, int bottleneck, hipStream_t st);
+// dW[9], db[1] (+)= fixed-order sum of nrows partial rows
+int launch_head_dw_reduce(const float* partial, int nrows, float* dW, float* db, int accumulate, hipStream_t st);
 // corr_group.hip -- per-image label sets (LSegNetZS, lseg_net_zs.py:198-208) on the training path: G = labels per image, 1..CORR_GROUP_MAX
 constexpr int CORR_GROUP_MAX = 8;
 bool corr_group_supported(int G, int C);
@@ -80,6 +97,9 @@ int launch_seg_stats_ex(const float* scores, const int64_t* target, int B, int K
                         double* nll, uint8_t* argmax_out, int up, int h, int w, hipStream_t st, float* lse_out = nullptr);
 int launch_upsample_ce_backward_rows(const float* low, const int64_t* target, const float* lse, const double* nll, void* rows, int B, int K,
                                      int H, int W, int ldk, int ignore_index, int dtype, hipStream_t st, const float* gscale = nullptr);
+// the same gradient as fp32 planes [B,K,H,W] and (ksum, optional) its per-pixel sum over the labels
+int launch_upsample_ce_backward_planes(const float* low, const int64_t* target, const float* lse, const double* nll, float* planes, float* ksum,
+                                       int B, int K, int H, int W, int ignore_index, hipStream_t st, const float* gscale = nullptr);
 int launch_seg_stats(const float* scores, const int64_t* target, int B, int K, int HW, int ignore_index,
                      unsigned long long* counts, double* nll, hipStream_t st);
 

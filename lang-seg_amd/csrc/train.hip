@@ -43,7 +43,10 @@ static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 int Engine::set_train(bool on) {
     if (on) {
         if (img_dt_ != DT_BF16) return set_error(LSEG_ERR_UNSUPPORTED, "training needs bf16 image-tower operands (fp16 gradients underflow)");
-        if (cfg.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "training with arch_option %d head blocks is not implemented", cfg.arch_option);
+        // the head blocks keep n extra [B,K,h,w] fp32 plane sets for their backward: only callers that ask for it (flags bit 4) pay for them
+        if (cfg.arch_option != 0 && !(cfg.flags & 16))
+            return set_error(LSEG_ERR_UNSUPPORTED, "training with arch_option %d head blocks needs lseg_config.flags bit 4 (train the head blocks)",
+                             cfg.arch_option);
         TRY(train_alloc());
         if (finalized_) TRY(finalize_train(nullptr));
     }
@@ -199,6 +202,16 @@ int Engine::train_alloc() {
     TALLOC(drows_, uint16_t, B * hw1 * Kp); TALLOC(da_, uint16_t, B * hw1 * c.out_c); TALLOC(df_, uint16_t, B * hw1 * c.out_c);
     TALLOC(tnT_, uint16_t, (size_t)c.out_c * Kp); TALLOC(tn16_, uint16_t, (size_t)c.max_labels * c.out_c);
     TALLOC(counts_, unsigned long long, 2 + 3 * (size_t)c.max_labels); TALLOC(nll_, double, 2);
+    if (c.arch_option == 1 || c.arch_option == 2) {          // head blocks (flags bit 4, checked by set_train): their saved outputs
+        hb_n_ = std::max(c.block_depth - 1, 0) + 1;           // lseg_net.py:198-201: block_depth 0 and 1 both mean one block
+        hb_out_.assign(hb_n_, nullptr);
+        for (int j = 0; j < hb_n_; ++j) TALLOC(hb_out_[j], float, B * c.max_labels * hw1);
+        if (c.arch_option == 1) {
+            TALLOC(hb_kstar_, int, (size_t)hb_n_ * B * hw1);
+            TALLOC(hb_ks_[0], float, B * hw1); TALLOC(hb_ks_[1], float, B * hw1);
+        }
+        TALLOC(hb_part_, float, (size_t)hb_n_ * head_block_bwd_partials((int)B, 2 * lh_[0], 2 * lw_[0]) * 10);
+    }
     LSEG_HIP_TRY(hipDeviceSynchronize());
     train_alloc_ = true;
     return 0;
@@ -423,9 +436,18 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
             TRY(launch_transpose16(tnorm_, tnT_, K_, c.out_c, c.out_c, Kp, st));      // fp16 as it is: the reference's dgrad is a half x half product
         }
     }
+    // arch_option 1/2 head blocks (lseg_net.py:198-201) with every block's output and the bottleneck's arg-max labels kept
+    const float* out = low_;
+    for (int j = 0; j < hb_n_; ++j) {
+        const int bott = c.arch_option == 1;
+        TRY(launch_head_block_train(out, hb_out_[j], bott ? hb_kstar_ + (size_t)j * B * hw1 : nullptr, hb_w_, hb_b_, B, kout, h1, w1, bott,
+                                    c.activation, j + 1 < hb_n_ ? 1 : 0, st));
+        out = hb_out_[j];
+    }
     // output_conv (x2 bilinear) only when the caller wants the logits: the loss and its gradient are taken on the low-resolution ones
-    if (logits) TRY(launch_upsample2x_planes(low_, logits, B * kout, h1, w1, st));
-    last_low_ = low_; last_kout_ = kout;
+    if (logits) TRY(launch_upsample2x_planes(out, logits, B * kout, h1, w1, st));
+    last_low_ = out; last_kout_ = kout;
+    train_out_ = out;
     train_B_ = B; train_G_ = group_k;
     train_fwd_valid_ = true;
     TRY(zero_end(zero_fwd_));
@@ -721,11 +743,50 @@ int Engine::train_loss(const int64_t* target, int ignore_index, double* dev_loss
     LSEG_HIP_TRY(hipSetDevice(device));
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
     const int kout = train_G_ > 0 ? train_G_ : K_;
-    TRY(launch_seg_stats_ex(low_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+    TRY(launch_seg_stats_ex(train_out_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
     if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (dev_counts2) LSEG_HIP_TRY(hipMemcpyAsync(dev_counts2, counts_, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     loss_target_ = target; loss_ignore_ = ignore_index;
     return 0;
+}
+
+// arch_option 1/2 head blocks (head_train.hip): the loss gradient as fp32 planes d(out) (fused CE or the d(logits) hand-over), then the
+// blocks from the last to the first; block 0 writes d(correlation output) as the fp16 (flags bit 1: bf16) rows the correlation backward
+// reads -- the `.float()` of lseg_net.py:196 under autograd.  The shared weight / bias gradients sum over the n blocks.
+int Engine::head_blocks_backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
+                                 const float* dev_grad_scale, int hdt, int Kp) {
+    const lseg_config& c = cfg;
+    const int B = train_B_, K = K_, h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
+    const int bott = c.arch_option == 1;
+    float* gbuf[2] = {low2_, low3_};          // the inference path's head-block temporaries serve as gradient planes
+    float* dW = grad("scratch.head_block.depthwise.depthwise.weight", 9);
+    float* db = grad("scratch.head_block.depthwise.depthwise.bias", 1);
+    if (!dW || !db) return LSEG_ERR_INVALID;
+    if (!dlogits) {
+        if (!(loss_target_ == target && loss_ignore_ == ignore_index))
+            TRY(launch_seg_stats_ex(train_out_, target, B, K, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+        TRY(launch_upsample_ce_backward_planes(train_out_, target, lse_px_, nll_, gbuf[0], bott ? hb_ks_[0] : nullptr, B, K, h1, w1, ignore_index,
+                                               st, dev_grad_scale));
+        if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else {
+        TRY(launch_upsample2x_planes_backward_planes(dlogits, gbuf[0], B, K, h1, w1, st));
+        if (bott) TRY(launch_head_bwd_prep(gbuf[0], nullptr, nullptr, nullptr, hb_ks_[0], nullptr, B, K, hw1, c.activation, 0, st));
+    }
+    const size_t rows = head_block_bwd_partials(B, h1, w1);
+    int cur = 0;
+    for (int j = hb_n_ - 1; j >= 0; --j) {
+        const float* x = j > 0 ? hb_out_[j - 1] : low_;
+        const int* ks = bott ? hb_kstar_ + (size_t)j * B * hw1 : nullptr;
+        float* part = hb_part_ + (size_t)j * rows * 10;
+        if (j > 0)
+            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, gbuf[cur ^ 1], DT_F32, 0, c.activation,
+                                           bott ? hb_ks_[cur ^ 1] : nullptr, part, B, K, h1, w1, bott, st));
+        else
+            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, drows_, hdt, Kp, -1, nullptr, part, B, K, h1, w1,
+                                           bott, st));
+        cur ^= 1;
+    }
+    return launch_head_dw_reduce(hb_part_, (int)(rows * hb_n_), dW, db, acc, st);
 }
 
 int Engine::backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
@@ -749,9 +810,10 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     // for the un-rounded gradient.
     const int hdt = (cfg.flags & 2) ? img_dt_ : DT_F16;
     // ---- loss + x2 upsample^T: the correlation's dY rows ---------------------------------------------------------------------
-    if (!dlogits) {      // CrossEntropyLoss(ignore_index) on output_conv(low): one pass for the loss and the per-pixel log-sum-exp, one for the rows
+    if (hb_n_ > 0) TRY(head_blocks_backward(dlogits, target, ignore_index, acc, dev_loss2, st, dev_grad_scale, hdt, Kp));
+    else if (!dlogits) {      // CrossEntropyLoss(ignore_index) on output_conv(low): one pass for the loss and the per-pixel log-sum-exp, one for the rows
         if (!(loss_target_ == target && loss_ignore_ == ignore_index))      // else: lseg_train_loss left nll_ / lse_px_ of this forward and target
-            TRY(launch_seg_stats_ex(low_, target, B, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+            TRY(launch_seg_stats_ex(train_out_, target, B, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
         TRY(launch_upsample_ce_backward_rows(low_, target, lse_px_, nll_, drows_, B, kout, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
         if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     } else {             // autograd hand-over: d(logits) [B,K,2h,2w] given

@@ -224,7 +224,8 @@ class LSeg(BaseModel):
                                 max_labels=max(K, eng.max_labels if eng else 1), device=device,
                                 image_dtype="bf16" if train else self.image_dtype,
                                 exact_head_grad=bool(getattr(self, "exact_head_grad", False)),
-                                batch_invariant=bool(getattr(self, "batch_invariant", False)))
+                                batch_invariant=bool(getattr(self, "batch_invariant", False)),
+                                head_block_training=self.cfg.arch_option in (1, 2))
                 eng._stamp = None
                 eng._tok = None
                 eng._ts = None
