@@ -102,7 +102,15 @@ typedef struct {
                                * n = max(block_depth - 1, 0) + 1 extra fp32 [max_batch, max_labels, h, w] plane sets (276 MB each at 8 x
                                * 150 labels, 480x480), and lseg_backward returns the gradient of scratch.head_block.depthwise.depthwise.
                                * {weight, bias} (bucket 0) -- always in a fixed summation order, bit 3 or not.  Not with per-image label
-                               * sets (the zero-shot network has no head blocks). */
+                               * sets (the zero-shot network has no head blocks).
+                               * bit 5: the image tower is torchvision's ResNet-101 (the zero-shot CLIP-ResNet-101 network,
+                               * LSegRNNetZS, lseg_net_zs.py:243-363): stem 7x7/2 + max-pool, layer1..4 (3, 4, 23, 3 Bottleneck v1.5
+                               * blocks, every BatchNorm folded from its running statistics) feed scratch.layer1..4_rn with 256 / 512 /
+                               * 1024 / 2048 channels at img/4 .. img/32; the neck, head and text tower are the ViT networks' own.
+                               * Parameters under the reference's keys pretrained.layer1.{0,1,4.*}, pretrained.layer{2,3,4}.*.  The ViT
+                               * fields (patch, dim, depth, heads, hooks, pos_grid, reassemble_*, resample_*) are ignored.  Refused:
+                               * img_h / img_w not a multiple of 32 (LSEG_ERR_INVALID), image_dtype LSEG_F16_SPLIT, arch_option != 0 and
+                               * lseg_set_train (LSEG_ERR_UNSUPPORTED).  Inference only. */
 } lseg_config;
 
 typedef struct lseg_engine* lseg_handle;
@@ -253,6 +261,20 @@ int lseg_op_attention_prescaled(const void* d_q, const void* d_k, const void* d_
 int lseg_op_conv3x3(const void* d_in, const void* d_w_packed, const float* d_bias,
                     const void* d_residual, void* d_out, int B, int H, int W, int Cin, int Cout,
                     int stride, int relu_in, int relu_out, void* stream);
+/* ResNet-101 tower operators (lseg_config.flags bit 5), dtype LSEG_BF16 | LSEG_F16 for every 16-bit map:
+ *   lseg_op_rn_stem     conv1 7x7 / 2, pad 3, 3 -> 64 channels, + bias + ReLU, fp32 accumulation: d_x fp32 NCHW [B,3,H,W] (H, W even) ->
+ *                       d_out padded NHWC [B,H/2+2,W/2+2,64] (interior written).  d_w fp32 [147][64] (tap k = (ci*7 + ky)*7 + kx, the
+ *                       BatchNorm folded in), d_bias fp32 [64].
+ *   lseg_op_rn_maxpool  max-pool 3x3 / 2, pad 1 of a padded NHWC map of NON-NEGATIVE values [B,H+2,W+2,C] (zero border) ->
+ *                       [B,H/2+2,W/2+2,C] interior; bit-exact (C % 8 == 0).
+ *   lseg_op_conv        1x1 (ksize 1, pad 0, w_packed [Cout, Cin]) or 3x3 (ksize 3, pad 1, w_packed [Cout, 9*Cin] tap-major) conv,
+ *                       stride 1|2, on padded NHWC maps as lseg_op_conv3x3, bias fp32 [Cout] or NULL, residual (geometry of out) or
+ *                       NULL; relu_out applies ReLU, BEFORE the residual add (relu_after_res = 0, the DPT units' order) or AFTER it
+ *                       (relu_after_res = 1: relu(conv + bias + residual), the bottleneck's).  Cin % 64 == 0. */
+int lseg_op_rn_stem(const float* d_x, const float* d_w, const float* d_bias, void* d_out, int B, int H, int W, int dtype, void* stream);
+int lseg_op_rn_maxpool(const void* d_in, void* d_out, int B, int H, int W, int C, int dtype, void* stream);
+int lseg_op_conv(const void* d_in, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_out, int B, int H, int W,
+                 int Cin, int Cout, int ksize, int stride, int relu_out, int relu_after_res, int dtype, void* stream);
 /* bilinear x2, align_corners=True, NHWC bf16: in [B,H+2,W+2,C] (padded) -> out [B,2H,2W,C] */
 int lseg_op_upsample2x_nhwc(const void* d_in, void* d_out, int B, int H, int W, int C, void* stream);
 /* bilinear x2, align_corners=True, NCHW fp32 planes: in [P,H,W] -> out [P,2H,2W]

@@ -292,6 +292,40 @@ int lseg_op_conv3x3(const void* in, const void* w_packed, const float* bias, con
     return launch_gemm(g, DT_BF16, (hipStream_t)stream);
 }
 
+int lseg_op_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dtype, &dt))) return r;
+    return launch_rn_stem(x, w, bias, out, B, H, W, dt, (hipStream_t)stream);
+}
+
+int lseg_op_rn_maxpool(const void* in, void* out, int B, int H, int W, int C, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dtype, &dt))) return r;
+    return launch_rn_maxpool(in, out, B, H, W, C, dt, (hipStream_t)stream);
+}
+
+int lseg_op_conv(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B, int H, int W, int Cin,
+                 int Cout, int ksize, int stride, int relu_out, int relu_after_res, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: 16-bit maps only");
+    if (ksize != 1 && ksize != 3) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: ksize %d (1 or 3)", ksize);
+    if (stride != 1 && stride != 2) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: stride %d (1 or 2)", stride);
+    GemmArgs g;
+    gemm_args_init(g);
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1, taps = ksize == 1 ? 1 : 9;
+    g.A = (const uint16_t*)in; g.W = (const uint16_t*)w_packed; g.M = B * Ho * Wo; g.N = Cout; g.K = taps * Cin;
+    g.lda = Cin; g.ldw = taps * Cin;
+    g.conv = 1; g.ksize = ksize; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride;
+    g.bias = bias; g.act = relu_out ? ACT_RELU : ACT_NONE;
+    if (residual) { g.res_mode = RES_DEST; g.res = residual; g.res_dtype = dt; g.relu_after_res = relu_after_res; }
+    g.C = out; g.out_dtype = dt; g.ldc = Cout; g.map_mode = MAP_PADDED;
+    return launch_gemm(g, dt, (hipStream_t)stream);
+}
+
 int lseg_op_upsample2x_nhwc(const void* in, void* out, int B, int H, int W, int C, void* stream) {
     int r = require_device(); if (r) return r;
     return launch_upsample2x_nhwc(in, out, B, H, W, C, DT_BF16, (hipStream_t)stream);

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void layernorm_reduce_kernel(float* __restrict
 // ReLU, optional skip inputs (padded NHWC, like the output), write the padded-NHWC map and optionally its ReLU copy.  8 channels per thread.
 __global__ void conv_reduce_pad_kernel(const float* __restrict__ part, int ns, size_t stride, const float* __restrict__ bias,
                                        const uint16_t* __restrict__ res, const uint16_t* __restrict__ res2, uint16_t* __restrict__ out,
-                                       uint16_t* __restrict__ out_relu, int B, int Ho, int Wo, int C, int relu, int dtype) {
+                                       uint16_t* __restrict__ out_relu, int B, int Ho, int Wo, int C, int relu, int dtype, int relu_after_res) {
     const int c8n = C >> 3;
     const size_t total = (size_t)B * Ho * Wo * c8n;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -178,7 +178,7 @@ __global__ void conv_reduce_pad_kernel(const float* __restrict__ part, int ns, s
             const float4 d = *reinterpret_cast<const float4*>(part + (size_t)sp * stride + m * C + c + 4);
             v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += d.x; v[5] += d.y; v[6] += d.z; v[7] += d.w;
         }
-        if (relu) {
+        if (relu && !relu_after_res) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
         }
@@ -194,6 +194,10 @@ __global__ void conv_reduce_pad_kernel(const float* __restrict__ part, int ns, s
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] += load_as_f32(e2, k, dtype);
             }
+        }
+        if (relu && relu_after_res) {         // ResNet bottleneck: relu(acc + bias + identity)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
         }
         const uint4 pk = make_uint4(pack2_dt(v[0], v[1], dtype), pack2_dt(v[2], v[3], dtype), pack2_dt(v[4], v[5], dtype), pack2_dt(v[6], v[7], dtype));
         *reinterpret_cast<uint4*>(out + o) = pk;
@@ -2134,10 +2138,10 @@ int launch_layernorm(const void* in, int in_dtype, const float* gamma, const flo
     return 0;
 }
 int launch_conv_reduce_pad(const float* part, int ns, size_t stride, const float* bias, const void* res, const void* res2, void* out, void* out_relu,
-                           int B, int Ho, int Wo, int C, int relu, int dtype, hipStream_t st) {
+                           int B, int Ho, int Wo, int C, int relu, int dtype, hipStream_t st, int relu_after_res) {
     if (C % 8) return set_error(LSEG_ERR_UNSUPPORTED, "conv_reduce_pad: C=%d must be a multiple of 8", C);
     hipLaunchKernelGGL(conv_reduce_pad_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 8))), dim3(256), 0, st, part, ns, stride, bias,
-                       (const uint16_t*)res, (const uint16_t*)res2, (uint16_t*)out, (uint16_t*)out_relu, B, Ho, Wo, C, relu, dtype);
+                       (const uint16_t*)res, (const uint16_t*)res2, (uint16_t*)out, (uint16_t*)out_relu, B, Ho, Wo, C, relu, dtype, relu_after_res);
     CHECK_LAUNCH();
     return 0;
 }

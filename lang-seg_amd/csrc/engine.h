@@ -99,8 +99,13 @@ private:
     int pack_f32(const std::string& key, size_t n, float*& out, hipStream_t st);
     int pack_conv3(const std::string& wkey, const std::string& bn_prefix, const std::string& bias_key, int co, int ci,
                    int cop, int cip, Lin& out, hipStream_t st);
+    // ksize 1: a 1x1 conv (w.k = Cin) on the padded map; relu_after_res: relu(conv + res) (ResNet bottleneck) instead of relu(conv) + res
     int conv3x3(const void* in, const Lin& w, const void* res, const void* res2, void* out, int B, int H, int W,
-                int stride, int relu_in, int relu_out, hipStream_t st, void* out_relu = nullptr, bool* relu_written = nullptr);
+                int stride, int relu_in, int relu_out, hipStream_t st, void* out_relu = nullptr, bool* relu_written = nullptr,
+                int ksize = 3, int relu_after_res = 0);
+    int pack_conv1(const std::string& wkey, const std::string& bn_prefix, int co, int ci, Lin& out, hipStream_t st);
+    int pack_resnet(hipStream_t st);
+    int resnet_forward(const float* x, int B, hipStream_t st);
     int refine(int r, int B, hipStream_t st, bool stop_before_upsample = false);
     int flush_events();
     int materialize_low(hipStream_t st);
@@ -143,7 +148,7 @@ private:
     size_t pl(const void* p) const { auto it = plane_.find(p); return it == plane_.end() ? 0 : it->second; }
     int igemm(GemmArgs& g, hipStream_t st);     // image-tower GEMM: fills the split-precision planes when strict_
     int split_residual(GemmArgs& g, int M, int N, int K);
-    float* ws_split_ = nullptr; size_t ws_split_rows_ = 0;
+    float* ws_split_ = nullptr; size_t ws_split_rows_ = 0, ws_split_n_ = 0;      // ws_split_n_: floats in ws_split_
     float* pack_tmp_ = nullptr; size_t pack_tmp_n_ = 0;
     uint16_t* relu_tmp_ = nullptr;
     int pack_tmp(size_t n, hipStream_t st);
@@ -165,6 +170,17 @@ private:
     float *tok_emb_ = nullptr, *tpos_ = nullptr, *tlnf_g_ = nullptr, *tlnf_b_ = nullptr;
     std::vector<TextBlock> tblocks_;
     Lin tproj_;
+
+    // ---- torchvision ResNet-101 image tower (lseg_config.flags bit 5; resnet.hip, Engine::resnet_forward) ------------------------
+    // c1 / c3 / ds: BN-folded 1x1 convs, c2: BN-folded 3x3 conv (stride on it: Bottleneck v1.5)
+    struct RnBlock { Lin c1, c2, c3, ds; int width = 0, stride = 1; bool has_ds = false; };
+    bool resnet_ = false;
+    float *rs_stem_w_ = nullptr, *rs_stem_b_ = nullptr;      // stem conv1 + bn1 folded: fp32 [147][64], [64]
+    std::vector<RnBlock> rs_blocks_[4];
+    uint16_t *rs_stem_ = nullptr, *rs_pool_ = nullptr;     // stem output (H/2, zero border: the max-pool reads it), max-pool output (H/4)
+    uint16_t *rs_t1_[4] = {}, *rs_t1in_[4] = {};             // conv1 outputs (zero border: conv2 reads them with 3x3 taps) at the stage's
+                                                             // resolution / at the previous stage's (block 0 of layer2..4, whose conv2 has stride 2)
+    uint16_t *rs_t2_ = nullptr, *rs_ds_ = nullptr;           // conv2 output, downsample output: read only at the centre (1x1 conv, residual)
 
     // ---- workspace -----------------------------------------------------------------------------
     float* x_ = nullptr;

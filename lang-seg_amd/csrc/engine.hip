@@ -79,10 +79,23 @@ void* Engine::dalloc(size_t bytes, bool zero) {
 int Engine::init() {
     const lseg_config& c = cfg;
     if (c.abi_version != LSEG_ABI_VERSION) return set_error(LSEG_ERR_INVALID, "config abi_version %d != %d", c.abi_version, LSEG_ABI_VERSION);
-    if (c.dim % c.heads || c.dim / c.heads != 64) return set_error(LSEG_ERR_UNSUPPORTED, "image head_dim must be 64 (dim %d / heads %d)", c.dim, c.heads);
+    resnet_ = (c.flags & 32) != 0;
+    if (resnet_) {
+        // torchvision ResNet-101 tower: the ViT fields are ignored; the stages feed scratch.layerN_rn with 256 / 512 / 1024 / 2048 channels
+        if (c.image_dtype == LSEG_F16_SPLIT)
+            return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower has no split-precision (strict) mode: use LSEG_BF16 or LSEG_F16");
+        if (c.img_h % 32 || c.img_w % 32)
+            return set_error(LSEG_ERR_INVALID, "ResNet-101 tower: image size %dx%d must be a multiple of 32 (the fusion adds need the exact x2 ladder)",
+                             c.img_h, c.img_w);
+        if (c.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "ResNet-101 tower: the zero-shot network has no head blocks (arch_option 0)");
+        for (int l = 0; l < 4; ++l) cfg.reassemble_ch[l] = 256 << l;
+    } else {
+        if (c.dim % c.heads || c.dim / c.heads != 64) return set_error(LSEG_ERR_UNSUPPORTED, "image head_dim must be 64 (dim %d / heads %d)", c.dim, c.heads);
+        if (c.img_h % c.patch || c.img_w % c.patch) return set_error(LSEG_ERR_INVALID, "image size %dx%d must be a multiple of the patch size %d", c.img_h, c.img_w, c.patch);
+        if (c.dim % 64 || (3 * c.patch * c.patch) % 64) return set_error(LSEG_ERR_UNSUPPORTED, "dim/features/out_c/text_width must be multiples of 64");
+    }
     if (c.text_width % c.text_heads || c.text_width / c.text_heads != 64) return set_error(LSEG_ERR_UNSUPPORTED, "text head_dim must be 64");
-    if (c.img_h % c.patch || c.img_w % c.patch) return set_error(LSEG_ERR_INVALID, "image size %dx%d must be a multiple of the patch size %d", c.img_h, c.img_w, c.patch);
-    if (c.dim % 64 || c.features % 64 || c.out_c % 64 || c.text_width % 64 || (3 * c.patch * c.patch) % 64)
+    if (c.features % 64 || c.out_c % 64 || c.text_width % 64)
         return set_error(LSEG_ERR_UNSUPPORTED, "dim/features/out_c/text_width must be multiples of 64");
     for (int l = 0; l < 4; ++l) {
         if (c.reassemble_ch[l] % 8) return set_error(LSEG_ERR_UNSUPPORTED, "reassemble channels %d (level %d) must be a multiple of 8", c.reassemble_ch[l], l + 1);
@@ -93,11 +106,12 @@ int Engine::init() {
 
     strict_ = c.image_dtype == LSEG_F16_SPLIT;
     img_dt_ = strict_ ? DT_F16 : T_code(c.image_dtype);
-    gh_ = c.img_h / c.patch; gw_ = c.img_w / c.patch; np_ = gh_ * gw_; ntok_ = np_ + 1;
+    gh_ = resnet_ ? 0 : c.img_h / c.patch; gw_ = resnet_ ? 0 : c.img_w / c.patch; np_ = gh_ * gw_; ntok_ = resnet_ ? 0 : np_ + 1;
     npad_ = ((ntok_ + 127) / 128) * 128;
     tnpad_ = ((c.text_ctx + 127) / 128) * 128;
     for (int l = 0; l < 4; ++l) {
-        if (c.resample_kind[l] == LSEG_RS_CONVT) { lh_[l] = gh_ * c.resample_k[l]; lw_[l] = gw_ * c.resample_k[l]; }
+        if (resnet_) { lh_[l] = c.img_h >> (2 + l); lw_[l] = c.img_w >> (2 + l); }      // layer1..4 at H/4 .. H/32
+        else if (c.resample_kind[l] == LSEG_RS_CONVT) { lh_[l] = gh_ * c.resample_k[l]; lw_[l] = gw_ * c.resample_k[l]; }
         else if (c.resample_kind[l] == LSEG_RS_IDENTITY) { lh_[l] = gh_; lw_[l] = gw_; }
         else { lh_[l] = (gh_ - 1) / 2 + 1; lw_[l] = (gw_ - 1) / 2 + 1; }
     }
@@ -121,7 +135,23 @@ int Engine::init() {
     // rounds): B = 4 633 -> 654 img/s, B = 6 721 -> 718, B = 2 / 8 / 12 unchanged.  LSEG_SPLIT_ROWS: A/B switch (tools)
     static const long split_rows_env = getenv("LSEG_SPLIT_ROWS") ? atol(getenv("LSEG_SPLIT_ROWS")) : 0;
     ws_split_rows_ = split_rows_env > 0 ? (size_t)split_rows_env : 16384;
-    ALLOC(ws_split_, float, ws_split_rows_ * D);
+    ws_split_n_ = ws_split_rows_ * (resnet_ ? 1024 : D);          // the ResNet tower's split-K convs: the same 64 MB as ViT-L/16's slabs
+    ALLOC(ws_split_, float, ws_split_n_);
+    if (resnet_) {
+        const int H2 = c.img_h / 2, W2 = c.img_w / 2;
+        ALLOC16(rs_stem_, B * (H2 + 2) * (W2 + 2) * 64);
+        ALLOC16(rs_pool_, B * (lh_[0] + 2) * (lw_[0] + 2) * 64);
+        size_t t2max = 0, dsmax = 0;
+        for (int l = 0; l < 4; ++l) {
+            const size_t wd = (size_t)64 << l, pp = B * (lh_[l] + 2) * (lw_[l] + 2);
+            ALLOC16(rs_t1_[l], pp * wd);
+            if (l > 0) ALLOC16(rs_t1in_[l], B * (lh_[l - 1] + 2) * (lw_[l - 1] + 2) * wd);
+            t2max = std::max(t2max, pp * wd);
+            dsmax = std::max(dsmax, pp * 4 * wd);
+        }
+        ALLOC16(rs_t2_, t2max);
+        ALLOC16(rs_ds_, dsmax);
+    } else {
     ALLOC16(ln_, Mp * D);
     ALLOC16(q_, B * c.heads * npad_ * 64);
     ALLOC16(k_, B * c.heads * npad_ * 64);
@@ -135,6 +165,7 @@ int Engine::init() {
     for (int l = 0; l < 4; ++l) r1max = std::max(r1max, (size_t)cp_[l]);
     ALLOC16(r1_, B * np_ * r1max);
     ALLOC16(tmp_pad_, B * (gh_ + 2) * (gw_ + 2) * r1max);
+    }
     for (int l = 0; l < 4; ++l) {
         const size_t pp = B * (lh_[l] + 2) * (lw_[l] + 2);
         ALLOC16(L_[l], pp * cp_[l]);
@@ -301,6 +332,86 @@ int Engine::pack_conv3(const std::string& wkey, const std::string& bnp, const st
     return launch_pack_conv3x3((const float*)w.ptr, bw, bb, bm, bv, 1e-5f, cb, out.w, has_bias ? out.b : nullptr, co, ci, cip, img_dt_, st);
 }
 
+// 1x1 conv [co, ci, 1, 1] + BatchNorm (eval: running statistics, eps 1e-5) folded -> [co, ci] 16-bit + fp32 bias (ResNet bottlenecks)
+int Engine::pack_conv1(const std::string& wkey, const std::string& bnp, int co, int ci, Lin& out, hipStream_t st) {
+    BoundParam w, a, b, m, v;
+    TRY(need(wkey, w, {co, ci, 1, 1}));
+    TRY(need(bnp + ".weight", a, {co})); TRY(need(bnp + ".bias", b, {co}));
+    TRY(need(bnp + ".running_mean", m, {co})); TRY(need(bnp + ".running_var", v, {co}));
+    if (w.dtype != LSEG_F32 || a.dtype != LSEG_F32 || b.dtype != LSEG_F32 || m.dtype != LSEG_F32 || v.dtype != LSEG_F32)
+        return set_error(LSEG_ERR_UNSUPPORTED, "'%s' and BatchNorm '%s' must be fp32", wkey.c_str(), bnp.c_str());
+    if (!out.w) ALLOC(out.w, uint16_t, (size_t)co * ci);
+    if (!out.b) ALLOC(out.b, float, co);
+    out.n = co; out.k = ci;
+    return launch_pack_conv1x1((const float*)w.ptr, (const float*)a.ptr, (const float*)b.ptr, (const float*)m.ptr, (const float*)v.ptr, 1e-5f,
+                               out.w, out.b, co, ci, img_dt_, st);
+}
+
+// torchvision ResNet-101 as lseg_vit_zs.py _make_resnet_backbone keeps it: pretrained.layer1 = Sequential(conv1, bn1, relu, maxpool,
+// layer1) -> keys pretrained.layer1.{0,1,4.*}; pretrained.layer2..4 = the stages.  Bottleneck v1.5: the stride sits on conv2.
+int Engine::pack_resnet(hipStream_t st) {
+    {
+        BoundParam w, a, b, m, v;
+        const std::string bnp = "pretrained.layer1.1";
+        TRY(need("pretrained.layer1.0.weight", w, {64, 3, 7, 7}));
+        TRY(need(bnp + ".weight", a, {64})); TRY(need(bnp + ".bias", b, {64}));
+        TRY(need(bnp + ".running_mean", m, {64})); TRY(need(bnp + ".running_var", v, {64}));
+        if (w.dtype != LSEG_F32 || a.dtype != LSEG_F32 || b.dtype != LSEG_F32 || m.dtype != LSEG_F32 || v.dtype != LSEG_F32)
+            return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet stem (pretrained.layer1.0 / .1) must be fp32");
+        if (!rs_stem_w_) ALLOC(rs_stem_w_, float, 147 * 64);
+        if (!rs_stem_b_) ALLOC(rs_stem_b_, float, 64);
+        TRY(launch_pack_rn_stem((const float*)w.ptr, (const float*)a.ptr, (const float*)b.ptr, (const float*)m.ptr, (const float*)v.ptr, 1e-5f,
+                                rs_stem_w_, rs_stem_b_, st));
+    }
+    static const int nblocks[4] = {3, 4, 23, 3};
+    char buf[128];
+    int cin = 64;
+    for (int l = 0; l < 4; ++l) {
+        const int wd = 64 << l;
+        rs_blocks_[l].resize(nblocks[l]);
+        for (int j = 0; j < nblocks[l]; ++j) {
+            if (l == 0) snprintf(buf, sizeof(buf), "pretrained.layer1.4.%d.", j);
+            else snprintf(buf, sizeof(buf), "pretrained.layer%d.%d.", l + 1, j);
+            const std::string p = buf;
+            RnBlock& k = rs_blocks_[l][j];
+            k.width = wd; k.stride = (j == 0 && l > 0) ? 2 : 1; k.has_ds = j == 0;
+            TRY(pack_conv1(p + "conv1.weight", p + "bn1", wd, cin, k.c1, st));
+            TRY(pack_conv3(p + "conv2.weight", p + "bn2", "", wd, wd, wd, wd, k.c2, st));
+            TRY(pack_conv1(p + "conv3.weight", p + "bn3", 4 * wd, wd, k.c3, st));
+            if (k.has_ds) TRY(pack_conv1(p + "downsample.0.weight", p + "downsample.1", 4 * wd, cin, k.ds, st));
+            cin = 4 * wd;
+        }
+    }
+    return 0;
+}
+
+// stem -> max-pool -> 33 bottlenecks; the last block of stage l leaves its output in L_[l] (padded NHWC, 256 << l channels at H / (4 << l)),
+// where the DPT neck reads it.  Every block of a stage writes L_[l]: block 0 from its downsample branch, blocks 1.. IN PLACE
+// (relu(bn3(conv3(t)) + x) with x = L_[l] itself -- each output element is read as the residual by the lane that then overwrites it;
+// the conv1 that reads x ran before).  No host synchronisation, no layout copies.
+int Engine::resnet_forward(const float* x, int B, hipStream_t st) {
+    TRY(launch_rn_stem(x, rs_stem_w_, rs_stem_b_, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, st));
+    TRY(launch_rn_maxpool(rs_stem_, rs_pool_, B, cfg.img_h / 2, cfg.img_w / 2, 64, img_dt_, st));
+    const uint16_t* in = rs_pool_;
+    int h = lh_[0], w = lw_[0];
+    for (int l = 0; l < 4; ++l) {
+        for (size_t j = 0; j < rs_blocks_[l].size(); ++j) {
+            RnBlock& k = rs_blocks_[l][j];
+            uint16_t* t1 = (j == 0 && l > 0) ? rs_t1in_[l] : rs_t1_[l];            // conv1 runs at the block input's resolution
+            TRY(conv3x3(in, k.c1, nullptr, nullptr, t1, B, h, w, 1, 0, 1, st, nullptr, nullptr, 1, 0));               // relu(bn1(conv1 x))
+            TRY(conv3x3(t1, k.c2, nullptr, nullptr, rs_t2_, B, h, w, k.stride, 0, 1, st));                            // relu(bn2(conv2 .)), stride
+            const void* idn = in;
+            if (k.has_ds) {                                                                                           // bn(downsample.0 x)
+                TRY(conv3x3(in, k.ds, nullptr, nullptr, rs_ds_, B, h, w, k.stride, 0, 0, st, nullptr, nullptr, 1, 0));
+                idn = rs_ds_;
+            }
+            TRY(conv3x3(rs_t2_, k.c3, idn, nullptr, L_[l], B, lh_[l], lw_[l], 1, 0, 1, st, nullptr, nullptr, 1, 1));     // relu(bn3(conv3 .) + id)
+            in = L_[l]; h = lh_[l]; w = lw_[l];
+        }
+    }
+    return 0;
+}
+
 int Engine::finalize(hipStream_t st) {
     if (!inited_) return set_error(LSEG_ERR_STATE, "engine not initialised");
     LSEG_HIP_TRY(hipSetDevice(device));
@@ -308,61 +419,66 @@ int Engine::finalize(hipStream_t st) {
     const int D = c.dim, F = c.features, P = c.patch;
     char buf[256];
     const std::string vm = "pretrained.model.";
-    // ---- ViT --------------------------------------------------------------------------------------------
-    TRY(pack_linear(vm + "patch_embed.proj.weight", vm + "patch_embed.proj.bias", D, 3 * P * P, img_dt_, patch_, st, true));
-    TRY(pack_f32(vm + "cls_token", D, cls_, st));
-    TRY(pack_f32(vm + "pos_embed", (size_t)(1 + c.pos_grid * c.pos_grid) * D, pos_raw_, st));
-    if (!pos_) ALLOC(pos_, float, (size_t)ntok_ * D);
-    TRY(launch_pos_resize(pos_raw_, pos_, c.pos_grid, gh_, gw_, D, st));     // lseg_vit.py:149-163, once
-    blocks_.resize(c.depth);
-    for (int i = 0; i < c.depth; ++i) {
-        snprintf(buf, sizeof(buf), "%sblocks.%d.", vm.c_str(), i);
-        const std::string b = buf;
-        VitBlock& k = blocks_[i];
-        TRY(pack_f32(b + "norm1.weight", D, k.g1, st)); TRY(pack_f32(b + "norm1.bias", D, k.b1, st));
-        TRY(pack_f32(b + "norm2.weight", D, k.g2, st)); TRY(pack_f32(b + "norm2.bias", D, k.b2, st));
-        TRY(pack_linear(b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, img_dt_, k.qkv, st, true));
-        TRY(pack_linear(b + "attn.proj.weight", b + "attn.proj.bias", D, D, img_dt_, k.proj, st, true));
-        TRY(pack_linear(b + "mlp.fc1.weight", b + "mlp.fc1.bias", 4 * D, D, img_dt_, k.fc1, st, true));
-        TRY(pack_linear(b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, 4 * D, img_dt_, k.fc2, st, true));
+    if (resnet_) TRY(pack_resnet(st));
+    else {
+        // ---- ViT --------------------------------------------------------------------------------------------
+        TRY(pack_linear(vm + "patch_embed.proj.weight", vm + "patch_embed.proj.bias", D, 3 * P * P, img_dt_, patch_, st, true));
+        TRY(pack_f32(vm + "cls_token", D, cls_, st));
+        TRY(pack_f32(vm + "pos_embed", (size_t)(1 + c.pos_grid * c.pos_grid) * D, pos_raw_, st));
+        if (!pos_) ALLOC(pos_, float, (size_t)ntok_ * D);
+        TRY(launch_pos_resize(pos_raw_, pos_, c.pos_grid, gh_, gw_, D, st));     // lseg_vit.py:149-163, once
+        blocks_.resize(c.depth);
+        for (int i = 0; i < c.depth; ++i) {
+            snprintf(buf, sizeof(buf), "%sblocks.%d.", vm.c_str(), i);
+            const std::string b = buf;
+            VitBlock& k = blocks_[i];
+            TRY(pack_f32(b + "norm1.weight", D, k.g1, st)); TRY(pack_f32(b + "norm1.bias", D, k.b1, st));
+            TRY(pack_f32(b + "norm2.weight", D, k.g2, st)); TRY(pack_f32(b + "norm2.bias", D, k.b2, st));
+            TRY(pack_linear(b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, img_dt_, k.qkv, st, true));
+            TRY(pack_linear(b + "attn.proj.weight", b + "attn.proj.bias", D, D, img_dt_, k.proj, st, true));
+            TRY(pack_linear(b + "mlp.fc1.weight", b + "mlp.fc1.bias", 4 * D, D, img_dt_, k.fc1, st, true));
+            TRY(pack_linear(b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, 4 * D, img_dt_, k.fc2, st, true));
+        }
     }
     // ---- readout / reassemble / layer_rn -------------------------------------------------------------
     for (int l = 0; l < 4; ++l) {
-        snprintf(buf, sizeof(buf), "pretrained.act_postprocess%d.", l + 1);
-        const std::string a = buf;
         const int C = c.reassemble_ch[l], Cp = cp_[l];
-        TRY(pack_linear(a + "0.project.0.weight", a + "0.project.0.bias", D, 2 * D, img_dt_, readout_[l], st, true));
-        {   // 1x1 conv [C, D] -> [Cp, D] (rows >= C are zero: the padded channels stay exactly 0)
-            BoundParam w, b;
-            TRY(need(a + "3.weight", w, {C, D}));
-            TRY(need(a + "3.bias", b, {C}));
-            if (!r1x1_[l].w) { ALLOC(r1x1_[l].w, uint16_t, (size_t)Cp * D * (strict_ ? 2 : 1)); if (strict_) plane_[r1x1_[l].w] = (size_t)Cp * D; }
-            if (!r1x1_[l].b) ALLOC(r1x1_[l].b, float, Cp);
-            r1x1_[l].n = Cp; r1x1_[l].k = D;
-            if (strict_) TRY(launch_convert_split(w.ptr, w.dtype, r1x1_[l].w, (size_t)C * D, (size_t)Cp * D, st));
-            else TRY(launch_convert(w.ptr, w.dtype, r1x1_[l].w, img_dt_, (size_t)C * D, st));
-            TRY(launch_convert(b.ptr, b.dtype, r1x1_[l].b, DT_F32, C, st));
-        }
-        if (c.resample_kind[l] == LSEG_RS_CONVT) {
-            const int s = c.resample_k[l];
-            BoundParam w, b;
-            TRY(need(a + "4.weight", w, {C, C, s, s}));
-            TRY(need(a + "4.bias", b, {C}));
-            if (w.dtype != LSEG_F32) return set_error(LSEG_ERR_UNSUPPORTED, "'%s4.weight' must be fp32", a.c_str());
-            const size_t nwt = (size_t)s * s * Cp * Cp;
-            if (!rsmp_[l].w) { ALLOC(rsmp_[l].w, uint16_t, nwt * (strict_ ? 2 : 1)); if (strict_) plane_[rsmp_[l].w] = nwt; }
-            if (!rsmp_[l].b) ALLOC(rsmp_[l].b, float, Cp);
-            rsmp_[l].n = s * s * Cp; rsmp_[l].k = Cp;
-            if (strict_) {
-                TRY(pack_tmp(nwt, st));
-                TRY(launch_pack_convT((const float*)w.ptr, pack_tmp_, C, C, Cp, s, DT_F32, st));
-                TRY(launch_convert_split(pack_tmp_, DT_F32, rsmp_[l].w, nwt, nwt, st));
-            } else {
-                TRY(launch_pack_convT((const float*)w.ptr, rsmp_[l].w, C, C, Cp, s, img_dt_, st));
+        if (!resnet_) {
+            snprintf(buf, sizeof(buf), "pretrained.act_postprocess%d.", l + 1);
+            const std::string a = buf;
+            TRY(pack_linear(a + "0.project.0.weight", a + "0.project.0.bias", D, 2 * D, img_dt_, readout_[l], st, true));
+            {   // 1x1 conv [C, D] -> [Cp, D] (rows >= C are zero: the padded channels stay exactly 0)
+                BoundParam w, b;
+                TRY(need(a + "3.weight", w, {C, D}));
+                TRY(need(a + "3.bias", b, {C}));
+                if (!r1x1_[l].w) { ALLOC(r1x1_[l].w, uint16_t, (size_t)Cp * D * (strict_ ? 2 : 1)); if (strict_) plane_[r1x1_[l].w] = (size_t)Cp * D; }
+                if (!r1x1_[l].b) ALLOC(r1x1_[l].b, float, Cp);
+                r1x1_[l].n = Cp; r1x1_[l].k = D;
+                if (strict_) TRY(launch_convert_split(w.ptr, w.dtype, r1x1_[l].w, (size_t)C * D, (size_t)Cp * D, st));
+                else TRY(launch_convert(w.ptr, w.dtype, r1x1_[l].w, img_dt_, (size_t)C * D, st));
+                TRY(launch_convert(b.ptr, b.dtype, r1x1_[l].b, DT_F32, C, st));
             }
-            TRY(launch_convert(b.ptr, b.dtype, rsmp_[l].b, DT_F32, C, st));
-        } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
-            TRY(pack_conv3(a + "4.weight", "", a + "4.bias", C, C, Cp, Cp, rsmp_[l], st));
+            if (c.resample_kind[l] == LSEG_RS_CONVT) {
+                const int s = c.resample_k[l];
+                BoundParam w, b;
+                TRY(need(a + "4.weight", w, {C, C, s, s}));
+                TRY(need(a + "4.bias", b, {C}));
+                if (w.dtype != LSEG_F32) return set_error(LSEG_ERR_UNSUPPORTED, "'%s4.weight' must be fp32", a.c_str());
+                const size_t nwt = (size_t)s * s * Cp * Cp;
+                if (!rsmp_[l].w) { ALLOC(rsmp_[l].w, uint16_t, nwt * (strict_ ? 2 : 1)); if (strict_) plane_[rsmp_[l].w] = nwt; }
+                if (!rsmp_[l].b) ALLOC(rsmp_[l].b, float, Cp);
+                rsmp_[l].n = s * s * Cp; rsmp_[l].k = Cp;
+                if (strict_) {
+                    TRY(pack_tmp(nwt, st));
+                    TRY(launch_pack_convT((const float*)w.ptr, pack_tmp_, C, C, Cp, s, DT_F32, st));
+                    TRY(launch_convert_split(pack_tmp_, DT_F32, rsmp_[l].w, nwt, nwt, st));
+                } else {
+                    TRY(launch_pack_convT((const float*)w.ptr, rsmp_[l].w, C, C, Cp, s, img_dt_, st));
+                }
+                TRY(launch_convert(b.ptr, b.dtype, rsmp_[l].b, DT_F32, C, st));
+            } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
+                TRY(pack_conv3(a + "4.weight", "", a + "4.bias", C, C, Cp, Cp, rsmp_[l], st));
+            }
         }
         snprintf(buf, sizeof(buf), "scratch.layer%d_rn.weight", l + 1);
         TRY(pack_conv3(buf, "", "", F, C, F, Cp, layer_rn_[l], st));
@@ -540,19 +656,19 @@ int Engine::encode_text(hipStream_t st) {
 }
 
 int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* res2, void* out, int B, int H, int W,
-                    int stride, int relu_in, int relu_out, hipStream_t st, void* out_relu, bool* relu_written) {
+                    int stride, int relu_in, int relu_out, hipStream_t st, void* out_relu, bool* relu_written, int ksize, int relu_after_res) {
     // in: padded NHWC [B,H+2,W+2,Cin]; out: padded NHWC [B,Ho+2,Wo+2,Cout]
     GemmArgs g;
     gemm_args_init(g);
-    const int Cin = w.k / 9, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const int Cin = w.k / (ksize == 1 ? 1 : 9), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     if (strict_ && relu_in) {        // the ReLU-ed input is materialised: a sign test on the hi fragments alone cannot zero the lo plane
         TRY(launch_relu_split(in, pl(in), relu_tmp_, pl(relu_tmp_), (size_t)B * (H + 2) * (W + 2) * Cin, st));
         in = relu_tmp_; relu_in = 0;
     }
     g.A = (const uint16_t*)in; g.W = w.w; g.M = B * Ho * Wo; g.N = w.n; g.K = w.k; g.lda = Cin; g.ldw = w.k;
-    g.conv = 1; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride; g.relu_in = relu_in;
+    g.conv = 1; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride; g.relu_in = relu_in; g.ksize = ksize;
     g.bias = w.b; g.act = relu_out ? ACT_RELU : ACT_NONE;
-    if (res) { g.res_mode = RES_DEST; g.res = res; g.res_dtype = img_dt_; g.res2 = res2; }
+    if (res) { g.res_mode = RES_DEST; g.res = res; g.res_dtype = img_dt_; g.res2 = res2; g.relu_after_res = relu_after_res; }
     g.C = out; g.out_dtype = img_dt_; g.ldc = w.n; g.map_mode = MAP_PADDED;
     if (relu_written) *relu_written = false;
     // Small batches: the deep levels of the pyramid are a handful of tiles with a 36..144-step contraction (layer3_rn at B = 1: 60 tiles of
@@ -564,18 +680,19 @@ int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* r
         long ns = 512 / tiles;
         if (ns > nk / 8) ns = nk / 8;
         if (ns > 8) ns = 8;
-        while (ns > 1 && (size_t)ns * g.M * w.n > ws_split_rows_ * (size_t)cfg.dim) --ns;
+        while (ns > 1 && (size_t)ns * g.M * w.n > ws_split_n_) --ns;
         if (ns >= 2) {
             const int steps = (int)((nk + ns - 1) / ns);
             ns = (nk + steps - 1) / steps;
         }
         if (ns >= 2) {
             GemmArgs p = g;
-            p.bias = nullptr; p.act = ACT_NONE; p.res_mode = RES_NONE; p.res = nullptr; p.res2 = nullptr;
+            p.bias = nullptr; p.act = ACT_NONE; p.res_mode = RES_NONE; p.res = nullptr; p.res2 = nullptr; p.relu_after_res = 0;
             p.C = ws_split_; p.out_dtype = DT_F32; p.ldc = w.n; p.map_mode = MAP_LINEAR;
             p.nsplit = (int)ns; p.split_steps = (nk + (int)ns - 1) / (int)ns; p.c_split_stride = (size_t)g.M * w.n;
             TRY(launch_gemm(p, img_dt_, st));
-            TRY(launch_conv_reduce_pad(ws_split_, (int)ns, p.c_split_stride, w.b, res, res2, out, out_relu, B, Ho, Wo, w.n, relu_out, img_dt_, st));
+            TRY(launch_conv_reduce_pad(ws_split_, (int)ns, p.c_split_stride, w.b, res, res2, out, out_relu, B, Ho, Wo, w.n, relu_out, img_dt_, st,
+                                       res ? relu_after_res : 0));
             if (relu_written) *relu_written = out_relu != nullptr;
             return 0;
         }
@@ -782,120 +899,128 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         LSEG_HIP_TRY(hipEventRecord(ev_join_, text_stream_));
     }
 
-    // ---- forward_flex (lseg_vit.py:166-201): patch embed + cls + pos -------------------------------------
-    if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
-    else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
     GemmArgs g;
-    gemm_args_init(g);
-    g.A = patchA_; g.W = patch_.w; g.M = B * np_; g.N = D; g.K = patch_.k; g.lda = patch_.k; g.ldw = patch_.k;
-    g.bias = patch_.b; g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = D;
-    g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
-    TRY(igemm(g, st));
-    TRY(launch_cls_rows(cls_, pos_, x_, B, ntok_, D, st));
-
-    // ---- 24 x timm Block; hooks feed readout/reassemble/layer_rn immediately ------------------------------
-    int pend_ns = 0;                    // > 0: x_ still lacks `pend_bias` + the pend_ns split-K slabs in ws_split_ (see split_residual)
-    const float* pend_bias = nullptr;
-    for (int i = 0; i < c.depth; ++i) {
-        VitBlock& b = blocks_[i];
-        hipEvent_t pe = prof_begin(PF_LN, st);
-        if (strict_) TRY(launch_ln_split(x_, b.g1, b.b1, ln_, pl(ln_), M, D, 1e-6f, st));
-        else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
-        else TRY(launch_layernorm(x_, DT_F32, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st));
-        prof_end(PF_LN, pe, 0.0, st);
-        gemm_args_init(g);
-        g.A = ln_; g.W = b.qkv.w; g.M = M; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.qkv.b; g.out_dtype = img_dt_; g.map_mode = MAP_QKV;
-        g.C = q_; g.Ck = k_; g.Cv = vt_; g.qkv_dim = D; g.qkv_ntok = ntok_; g.qkv_npad = npad_; g.qkv_heads = H;
-        // the softmax scale (head_dim^-0.5 = 0.125 for 64) * log2(e) rides on q through the QKV epilogue's single rounding: the attention
-        // kernel's matrix pipe then delivers exp2 arguments (attention.hip PRE)
-        g.qkv_qscale = 0.125f * 1.4426950408889634f;
-        // fp16 operands only: with bf16 the pre-scaled body moved the mask flips at configs[1] from 1.57 % to 2.64 % (max |dlogit| 0.204 ->
-        // 0.241; fp16 0.264 % vs 0.274 %: unchanged) -- lease J, profiles/r04_attention_experiments.txt.  LSEG_ATTN_PRE=0 / 1 (tools) forces a body.
-        static const int pre_env = getenv("LSEG_ATTN_PRE") ? atoi(getenv("LSEG_ATTN_PRE")) : -1;
-        const bool prescaled = !strict_ && gemm_qkv_scales_q(g, img_dt_) && (pre_env < 0 ? img_dt_ == DT_F16 : pre_env != 0);
-        if (!prescaled) g.qkv_qscale = 0.f;
-        pe = prof_begin(PF_QKV, st);
-        TRY(igemm(g, st));
-        prof_end(PF_QKV, pe, 2.0 * M * 3.0 * D * D, st);
-        pe = prof_begin(PF_ATTN, st);
-        if (strict_) TRY(launch_attention_strict(q_, k_, vt_, att_, pl(q_), pl(vt_), pl(att_), B, H, ntok_, npad_, 0.125f, st));
-        else TRY(launch_attention_ex(q_, k_, vt_, att_, nullptr, B, H, ntok_, npad_, img_dt_, 0, 0.125f, prescaled ? 1 : 0, st));
-        prof_end(PF_ATTN, pe, 4.0 * B * ntok2 * D, st);          // QK^T + PV, SURVEY 8(d): 4 N^2 D per image and block
-        gemm_args_init(g);
-        g.A = att_; g.W = b.proj.w; g.M = M; g.N = D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.proj.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
-        g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
-        pend_ns = split_residual(g, M, D, D);                 // small batches: partial slabs, summed into x_ by the LayerNorm that follows
-        pend_bias = b.proj.b;
-        pe = prof_begin(PF_PROJ, st);
-        TRY(igemm(g, st));
-        prof_end(PF_PROJ, pe, 2.0 * M * (double)D * D, st);
-        pe = prof_begin(PF_LN, st);
-        if (strict_) TRY(launch_ln_split(x_, b.g2, b.b2, ln_, pl(ln_), M, D, 1e-6f, st));
-        else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
-        else TRY(launch_layernorm(x_, DT_F32, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st));
-        prof_end(PF_LN, pe, 0.0, st);
-        gemm_args_init(g);
-        g.A = ln_; g.W = b.fc1.w; g.M = M; g.N = 4 * D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.fc1.b; g.act = ACT_GELU; g.C = mlp_; g.out_dtype = img_dt_; g.ldc = 4 * D; g.map_mode = MAP_LINEAR;
-        g.tag = 1;
-        pe = prof_begin(PF_FC1, st);
-        TRY(igemm(g, st));
-        prof_end(PF_FC1, pe, 2.0 * M * 4.0 * D * D, st);
-        gemm_args_init(g);
-        g.A = mlp_; g.W = b.fc2.w; g.M = M; g.N = D; g.K = 4 * D; g.lda = 4 * D; g.ldw = 4 * D;
-        g.bias = b.fc2.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
-        g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
-        pend_ns = split_residual(g, M, D, 4 * D);
-        pend_bias = b.fc2.b;
-        pe = prof_begin(PF_FC2, st);
-        TRY(igemm(g, st));
-        prof_end(PF_FC2, pe, 2.0 * M * 4.0 * D * D, st);
-        // the slabs are normally summed by the next block's LayerNorm; a hooked block (the readout reads x_) and the last one need x_ now
-        bool hooked = i + 1 == c.depth;
-        for (int l = 0; l < 4; ++l) hooked = hooked || c.hooks[l] == i;
-        if (pend_ns && hooked) {
-            TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, nullptr, nullptr, ln_, img_dt_, M, D, 1e-6f, st));
-            pend_ns = 0;
-        }
-
-        for (int l = 0; l < 4; ++l) {
-            if (c.hooks[l] != i) continue;
-            if (debug) {
-                if (!acts_[l]) ALLOC(acts_[l], float, (size_t)c.max_batch * ntok_ * D);
-                LSEG_HIP_TRY(hipMemcpyAsync(acts_[l], x_, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-            }
-            const int C = cp_[l];                 // padded channel count (== reassemble_ch unless ViT-B/32 level 1)
-            // ProjectReadout (lseg_vit.py:86-90)
-            if (strict_) TRY(launch_readout_cat_split(x_, catA_, pl(catA_), B, ntok_, D, st));
-            else TRY(launch_readout_cat(x_, catA_, B, ntok_, D, img_dt_, st));
-            gemm_args_init(g);
-            g.A = catA_; g.W = readout_[l].w; g.M = B * np_; g.N = D; g.K = 2 * D; g.lda = 2 * D; g.ldw = 2 * D;
-            g.bias = readout_[l].b; g.act = ACT_GELU; g.C = ro_; g.out_dtype = img_dt_; g.ldc = D; g.map_mode = MAP_LINEAR;
-            TRY(igemm(g, st));
-            // act_postprocess[3]: 1x1 conv (token-major rows == NHWC pixels, the Transpose/Unflatten are free)
-            gemm_args_init(g);
-            g.A = ro_; g.W = r1x1_[l].w; g.M = B * np_; g.N = C; g.K = D; g.lda = D; g.ldw = D;
-            g.bias = r1x1_[l].b; g.out_dtype = img_dt_; g.ldc = C;
-            if (c.resample_kind[l] == LSEG_RS_CONVT) { g.C = r1_; g.map_mode = MAP_LINEAR; }
-            else if (c.resample_kind[l] == LSEG_RS_IDENTITY) { g.C = L_[l]; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-            else { g.C = tmp_pad_; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-            TRY(igemm(g, st));
-            if (c.resample_kind[l] == LSEG_RS_CONVT) {
-                // ConvTranspose2d(k = s = stride) as a GEMM with a pixel-shuffle scatter epilogue
-                const int s = c.resample_k[l];
-                gemm_args_init(g);
-                g.A = r1_; g.W = rsmp_[l].w; g.M = B * np_; g.N = s * s * C; g.K = C; g.lda = C; g.ldw = C;
-                g.bias = rsmp_[l].b; g.bias_mod = C; g.C = L_[l]; g.out_dtype = img_dt_; g.ldc = C;
-                g.map_mode = MAP_PIXSHUF; g.ho = gh_; g.wo = gw_; g.ps_s = s; g.ps_C = C;
-                TRY(igemm(g, st));
-            } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
-                TRY(conv3x3(tmp_pad_, rsmp_[l], nullptr, nullptr, L_[l], B, gh_, gw_, 2, 0, 0, st));
-            }
-            // scratch.layerN_rn (lseg_net.py:171-174)
+    if (resnet_) {
+        // ---- torchvision ResNet-101 layer1..4 (lseg_net_zs.py:325-333) straight into L_[0..3], then scratch.layerN_rn ---------------
+        TRY(resnet_forward(x_in, B, st));
+        for (int l = 0; l < 4; ++l)
             TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
+    } else {
+        // ---- forward_flex (lseg_vit.py:166-201): patch embed + cls + pos -------------------------------------
+        if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
+        else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
+        gemm_args_init(g);
+        g.A = patchA_; g.W = patch_.w; g.M = B * np_; g.N = D; g.K = patch_.k; g.lda = patch_.k; g.ldw = patch_.k;
+        g.bias = patch_.b; g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = D;
+        g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
+        TRY(igemm(g, st));
+        TRY(launch_cls_rows(cls_, pos_, x_, B, ntok_, D, st));
+
+        // ---- 24 x timm Block; hooks feed readout/reassemble/layer_rn immediately ------------------------------
+        int pend_ns = 0;                    // > 0: x_ still lacks `pend_bias` + the pend_ns split-K slabs in ws_split_ (see split_residual)
+        const float* pend_bias = nullptr;
+        for (int i = 0; i < c.depth; ++i) {
+            VitBlock& b = blocks_[i];
+            hipEvent_t pe = prof_begin(PF_LN, st);
+            if (strict_) TRY(launch_ln_split(x_, b.g1, b.b1, ln_, pl(ln_), M, D, 1e-6f, st));
+            else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
+            else TRY(launch_layernorm(x_, DT_F32, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st));
+            prof_end(PF_LN, pe, 0.0, st);
+            gemm_args_init(g);
+            g.A = ln_; g.W = b.qkv.w; g.M = M; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D;
+            g.bias = b.qkv.b; g.out_dtype = img_dt_; g.map_mode = MAP_QKV;
+            g.C = q_; g.Ck = k_; g.Cv = vt_; g.qkv_dim = D; g.qkv_ntok = ntok_; g.qkv_npad = npad_; g.qkv_heads = H;
+            // the softmax scale (head_dim^-0.5 = 0.125 for 64) * log2(e) rides on q through the QKV epilogue's single rounding: the attention
+            // kernel's matrix pipe then delivers exp2 arguments (attention.hip PRE)
+            g.qkv_qscale = 0.125f * 1.4426950408889634f;
+            // fp16 operands only: with bf16 the pre-scaled body moved the mask flips at configs[1] from 1.57 % to 2.64 % (max |dlogit| 0.204 ->
+            // 0.241; fp16 0.264 % vs 0.274 %: unchanged) -- lease J, profiles/r04_attention_experiments.txt.  LSEG_ATTN_PRE=0 / 1 (tools) forces a body.
+            static const int pre_env = getenv("LSEG_ATTN_PRE") ? atoi(getenv("LSEG_ATTN_PRE")) : -1;
+            const bool prescaled = !strict_ && gemm_qkv_scales_q(g, img_dt_) && (pre_env < 0 ? img_dt_ == DT_F16 : pre_env != 0);
+            if (!prescaled) g.qkv_qscale = 0.f;
+            pe = prof_begin(PF_QKV, st);
+            TRY(igemm(g, st));
+            prof_end(PF_QKV, pe, 2.0 * M * 3.0 * D * D, st);
+            pe = prof_begin(PF_ATTN, st);
+            if (strict_) TRY(launch_attention_strict(q_, k_, vt_, att_, pl(q_), pl(vt_), pl(att_), B, H, ntok_, npad_, 0.125f, st));
+            else TRY(launch_attention_ex(q_, k_, vt_, att_, nullptr, B, H, ntok_, npad_, img_dt_, 0, 0.125f, prescaled ? 1 : 0, st));
+            prof_end(PF_ATTN, pe, 4.0 * B * ntok2 * D, st);          // QK^T + PV, SURVEY 8(d): 4 N^2 D per image and block
+            gemm_args_init(g);
+            g.A = att_; g.W = b.proj.w; g.M = M; g.N = D; g.K = D; g.lda = D; g.ldw = D;
+            g.bias = b.proj.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
+            g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
+            pend_ns = split_residual(g, M, D, D);                 // small batches: partial slabs, summed into x_ by the LayerNorm that follows
+            pend_bias = b.proj.b;
+            pe = prof_begin(PF_PROJ, st);
+            TRY(igemm(g, st));
+            prof_end(PF_PROJ, pe, 2.0 * M * (double)D * D, st);
+            pe = prof_begin(PF_LN, st);
+            if (strict_) TRY(launch_ln_split(x_, b.g2, b.b2, ln_, pl(ln_), M, D, 1e-6f, st));
+            else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
+            else TRY(launch_layernorm(x_, DT_F32, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st));
+            prof_end(PF_LN, pe, 0.0, st);
+            gemm_args_init(g);
+            g.A = ln_; g.W = b.fc1.w; g.M = M; g.N = 4 * D; g.K = D; g.lda = D; g.ldw = D;
+            g.bias = b.fc1.b; g.act = ACT_GELU; g.C = mlp_; g.out_dtype = img_dt_; g.ldc = 4 * D; g.map_mode = MAP_LINEAR;
+            g.tag = 1;
+            pe = prof_begin(PF_FC1, st);
+            TRY(igemm(g, st));
+            prof_end(PF_FC1, pe, 2.0 * M * 4.0 * D * D, st);
+            gemm_args_init(g);
+            g.A = mlp_; g.W = b.fc2.w; g.M = M; g.N = D; g.K = 4 * D; g.lda = 4 * D; g.ldw = 4 * D;
+            g.bias = b.fc2.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
+            g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
+            pend_ns = split_residual(g, M, D, 4 * D);
+            pend_bias = b.fc2.b;
+            pe = prof_begin(PF_FC2, st);
+            TRY(igemm(g, st));
+            prof_end(PF_FC2, pe, 2.0 * M * 4.0 * D * D, st);
+            // the slabs are normally summed by the next block's LayerNorm; a hooked block (the readout reads x_) and the last one need x_ now
+            bool hooked = i + 1 == c.depth;
+            for (int l = 0; l < 4; ++l) hooked = hooked || c.hooks[l] == i;
+            if (pend_ns && hooked) {
+                TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, nullptr, nullptr, ln_, img_dt_, M, D, 1e-6f, st));
+                pend_ns = 0;
+            }
+
+            for (int l = 0; l < 4; ++l) {
+                if (c.hooks[l] != i) continue;
+                if (debug) {
+                    if (!acts_[l]) ALLOC(acts_[l], float, (size_t)c.max_batch * ntok_ * D);
+                    LSEG_HIP_TRY(hipMemcpyAsync(acts_[l], x_, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+                }
+                const int C = cp_[l];                 // padded channel count (== reassemble_ch unless ViT-B/32 level 1)
+                // ProjectReadout (lseg_vit.py:86-90)
+                if (strict_) TRY(launch_readout_cat_split(x_, catA_, pl(catA_), B, ntok_, D, st));
+                else TRY(launch_readout_cat(x_, catA_, B, ntok_, D, img_dt_, st));
+                gemm_args_init(g);
+                g.A = catA_; g.W = readout_[l].w; g.M = B * np_; g.N = D; g.K = 2 * D; g.lda = 2 * D; g.ldw = 2 * D;
+                g.bias = readout_[l].b; g.act = ACT_GELU; g.C = ro_; g.out_dtype = img_dt_; g.ldc = D; g.map_mode = MAP_LINEAR;
+                TRY(igemm(g, st));
+                // act_postprocess[3]: 1x1 conv (token-major rows == NHWC pixels, the Transpose/Unflatten are free)
+                gemm_args_init(g);
+                g.A = ro_; g.W = r1x1_[l].w; g.M = B * np_; g.N = C; g.K = D; g.lda = D; g.ldw = D;
+                g.bias = r1x1_[l].b; g.out_dtype = img_dt_; g.ldc = C;
+                if (c.resample_kind[l] == LSEG_RS_CONVT) { g.C = r1_; g.map_mode = MAP_LINEAR; }
+                else if (c.resample_kind[l] == LSEG_RS_IDENTITY) { g.C = L_[l]; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
+                else { g.C = tmp_pad_; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
+                TRY(igemm(g, st));
+                if (c.resample_kind[l] == LSEG_RS_CONVT) {
+                    // ConvTranspose2d(k = s = stride) as a GEMM with a pixel-shuffle scatter epilogue
+                    const int s = c.resample_k[l];
+                    gemm_args_init(g);
+                    g.A = r1_; g.W = rsmp_[l].w; g.M = B * np_; g.N = s * s * C; g.K = C; g.lda = C; g.ldw = C;
+                    g.bias = rsmp_[l].b; g.bias_mod = C; g.C = L_[l]; g.out_dtype = img_dt_; g.ldc = C;
+                    g.map_mode = MAP_PIXSHUF; g.ho = gh_; g.wo = gw_; g.ps_s = s; g.ps_C = C;
+                    TRY(igemm(g, st));
+                } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
+                    TRY(conv3x3(tmp_pad_, rsmp_[l], nullptr, nullptr, L_[l], B, gh_, gw_, 2, 0, 0, st));
+                }
+                // scratch.layerN_rn (lseg_net.py:171-174)
+                TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
+            }
         }
+
     }
 
     // ---- refinenet4..1 (lseg_net.py:176-179) ---------------------------------------------------------------

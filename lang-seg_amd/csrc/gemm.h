@@ -87,6 +87,10 @@ struct GemmArgs {
                                 // multiple of 256 rows lets the residual GEMMs run on the hand-scheduled kernel (gemm_asm.hip), which computes
                                 // whole 256-row tiles and never masks: rows >= M are garbage in, garbage out, nobody reads them
     int tile_hint;              // 0: the launcher's cost model picks the tile; 2 = 128x128, 6 = 256x256 (callers that plan tile and split-K together)
+    // ---- ResNet bottlenecks (resnet.hip, Engine::rn_conv).  Both default to the behaviour above when zero.
+    int ksize;                  // implicit conv kernel: 1 = 1x1 conv, pad 0 (K = cin; reads the centre of the padded input); 0 / 3 = 3x3, pad 1
+    int relu_after_res;         // with act = ACT_RELU and a residual: C = T(relu(acc + bias + res [+ res2])) -- the bottleneck's
+                                // relu(bn3(conv3(x)) + identity); 0: T(relu(acc + bias) + res [+ res2]) as the DPT units need
 };
 
 void gemm_args_init(GemmArgs& g);

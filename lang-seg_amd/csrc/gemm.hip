@@ -317,9 +317,10 @@ __device__ __forceinline__ void epilogue_row(const GemmArgs& g, int m, const int
         }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            apply_act<T>(g, v[i]);
+            if (!g.relu_after_res) apply_act<T>(g, v[i]);
             v[i][0] += rv[i].x + rv2[i].x; v[i][1] += rv[i].y + rv2[i].y;
             v[i][2] += rv[i].z + rv2[i].z; v[i][3] += rv[i].w + rv2[i].w;
+            if (g.relu_after_res) apply_act<T>(g, v[i]);
         }
     }
     if ((g.dbg & 3) == 1) {   // ablation: keep the values live, skip the stores
@@ -627,7 +628,9 @@ __device__ __forceinline__ void fast_epilogue(const GemmArgs& g, const GemmArgs&
     } else if constexpr (EPI == EPI_PAD16) {
         // m = (b, y, x) on the (ho, wo) output grid -> row of the padded NHWC map; columns are contiguous channels.
         // Residuals (the RCU skip input and, for the fusion add, the other path) live at the destination offsets.
-        const bool relu = g.act == ACT_RELU, has_res = g.res_mode == RES_DEST, has_res2 = has_res && g.res2 != nullptr;
+        const bool has_res = g.res_mode == RES_DEST, has_res2 = has_res && g.res2 != nullptr;
+        const bool relu_post = g.act == ACT_RELU && g.relu_after_res && has_res;     // relu(acc + bias + res): ResNet bottleneck
+        const bool relu = g.act == ACT_RELU && !relu_post;
         const int hw = g.ho * g.wo;
         static_for<0, MI>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
@@ -666,6 +669,10 @@ __device__ __forceinline__ void fast_epilogue(const GemmArgs& g, const GemmArgs&
                             x4[q][0] += to_f32<T>((uint16_t)u2.x); x4[q][1] += to_f32<T>((uint16_t)(u2.x >> 16));
                             x4[q][2] += to_f32<T>((uint16_t)u2.y); x4[q][3] += to_f32<T>((uint16_t)(u2.y >> 16));
                         }
+                    }
+                    if (relu_post) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) x4[q][r] = x4[q][r] > 0.f ? x4[q][r] : 0.f;
                     }
                 }
                 const uint4 o = widen16<T>(x4[0], x4[1]);
@@ -1007,7 +1014,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::MINW) void lseg_gemm_kernel(cons
         int koff_a;
         if (CONV) {
             const int tap = akt / cpt, ci0 = (akt - tap * cpt) << 6;
-            const int ky = tap / 3, kx = tap - ky * 3;
+            const int ky = g.ksize == 1 ? 1 : tap / 3, kx = g.ksize == 1 ? 1 : tap - ky * 3;     // 1x1: the centre tap only
             koff_a = (ky * g.wp + kx) * g.cin + ci0;
         } else {
             koff_a = akt << 6;
@@ -1563,6 +1570,11 @@ int launch_gemm(const GemmArgs& g_in, int ab_dtype, hipStream_t stream) {
     if (g.C_relu && !gemm_epilogue_is_pad16(g, ab_dtype)) return set_error(LSEG_ERR_UNSUPPORTED, "gemm: C_relu needs the padded-NHWC specialised epilogue");
     if (g.K % 64 != 0) return set_error(LSEG_ERR_UNSUPPORTED, "gemm: K=%d must be a multiple of 64", g.K);
     if (g.conv && (g.cin % 64 != 0)) return set_error(LSEG_ERR_UNSUPPORTED, "conv: Cin=%d must be a multiple of 64", g.cin);
+    if (g.ksize != 0 && g.ksize != 1 && g.ksize != 3) return set_error(LSEG_ERR_INVALID, "conv: ksize %d (1 or 3)", g.ksize);
+    if (g.conv && g.K != (g.ksize == 1 ? 1 : 9) * g.cin) return set_error(LSEG_ERR_INVALID, "conv: K=%d != taps x Cin=%d", g.K, g.cin);
+    if (g.ksize == 1 && (!g.conv || g.split)) return set_error(LSEG_ERR_UNSUPPORTED, "ksize 1 needs the (non-split) implicit conv");
+    if (g.relu_after_res && (g.split || g.res_mode != RES_DEST || g.act != ACT_RELU || g.round_mid || g.map_mode != MAP_PADDED))
+        return set_error(LSEG_ERR_UNSUPPORTED, "relu_after_res: needs a RES_DEST residual, ACT_RELU and the padded-NHWC map");
     if (g.nsplit > 1 && (g.bias || g.res_mode != RES_NONE || g.map_mode != MAP_LINEAR || g.split || g.split_steps < 1 ||
                          (long)g.nsplit * g.split_steps < (g.K >> 6) || (long)(g.nsplit - 1) * g.split_steps >= (g.K >> 6)))
         return set_error(LSEG_ERR_INVALID, "split-K: needs a plain MAP_LINEAR GEMM without bias / residual and ranges that tile K exactly");

@@ -13,9 +13,10 @@ int launch_layernorm(const void* in, int in_dtype, const float* gamma, const flo
 // x += bias + sum of `nsplit` split-K partial slabs (`stride` floats apart), then LayerNorm of the updated rows (gamma NULL: update only)
 int launch_layernorm_reduce(float* x, const float* part, int nsplit, size_t stride, const float* bias, const float* gamma, const float* beta,
                             void* out, int out_dtype, int M, int D, float eps, hipStream_t st);
-// epilogue of a split-K 3x3 conv: sum of `ns` fp32 slabs [B*Ho*Wo, C] + bias, ReLU, skip inputs -> padded NHWC map (+ its ReLU copy)
+// epilogue of a split-K 3x3 conv: sum of `ns` fp32 slabs [B*Ho*Wo, C] + bias, ReLU, skip inputs -> padded NHWC map (+ its ReLU copy);
+// relu_after_res: the ReLU after the skip add (ResNet bottleneck) instead of before it
 int launch_conv_reduce_pad(const float* part, int ns, size_t stride, const float* bias, const void* res, const void* res2, void* out, void* out_relu,
-                           int B, int Ho, int Wo, int C, int relu, int dtype, hipStream_t st);
+                           int B, int Ho, int Wo, int C, int relu, int dtype, hipStream_t st, int relu_after_res = 0);
 int launch_im2col_patch(const float* x, void* A, int B, int H, int W, int P, int dtype, hipStream_t st);
 int launch_pos_resize(const float* pos, float* out, int g_old, int gh, int gw, int D, hipStream_t st);
 int launch_cls_rows(const float* cls, const float* pos, float* x, int B, int ntok, int D, hipStream_t st);
@@ -181,5 +182,17 @@ int launch_eval_make_crops(const float* img, float* crops, int C, int height, in
 int launch_eval_accumulate(const float* outs, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
                            int w_grids, int flip, hipStream_t st);
 int launch_eval_resize(const float* src, float* dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, hipStream_t st);
+
+// ---- resnet.hip: the torchvision ResNet-101 image tower (lseg_config.flags bit 5) ----
+// stem: conv1 7x7/2 pad 3 (3 -> 64) + folded BN + ReLU, fp32 NCHW [B,3,H,W] -> padded NHWC 16-bit [B, Ho+2, Wo+2, 64]; w: fp32 [147][64]
+// (BN-folded, k = (ci*7 + ky)*7 + kx), bias fp32 [64]
+int launch_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, hipStream_t st);
+// max-pool 3x3/2 pad 1 on a padded NHWC 16-bit map of NON-NEGATIVE values [B, H+2, W+2, C] -> padded [B, Ho+2, Wo+2, C]
+int launch_rn_maxpool(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t st);
+// BN-folding packers: 1x1 conv weight [Co, Ci] (+ BN) -> [Co, Ci] 16-bit + fp32 bias; stem 7x7 [64, 3, 7, 7] (+ BN) -> fp32 [147][64] + bias
+int launch_pack_conv1x1(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float bn_eps,
+                        void* wp, float* bias_out, int Co, int Ci, int dtype, hipStream_t st);
+int launch_pack_rn_stem(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float bn_eps,
+                        float* wp, float* bias_out, hipStream_t st);
 
 }  // namespace lseg

@@ -42,6 +42,7 @@ static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 int Engine::set_train(bool on) {
     if (on) {
+        if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only (no train-mode BatchNorm / bottleneck backward)");
         if (img_dt_ != DT_BF16) return set_error(LSEG_ERR_UNSUPPORTED, "training needs bf16 image-tower operands (fp16 gradients underflow)");
         // the head blocks keep n extra [B,K,h,w] fp32 plane sets for their backward: only callers that ask for it (flags bit 4) pay for them
         if (cfg.arch_option != 0 && !(cfg.flags & 16))

@@ -42,6 +42,9 @@ class LSegConfig:
     arch_option: int = 0
     block_depth: int = 0
     activation: str = "lrelu"
+    # image tower: "vit" (the timm ViT + reassemble stacks above) or "resnet101" (torchvision ResNet-101 layer1..4, whose four stage
+    # outputs feed scratch.layerN_rn directly; the ViT fields are then placeholders the engine ignores: lseg_config.flags bit 5)
+    tower: str = "vit"
 
     @property
     def head_dim(self) -> int:
@@ -76,6 +79,15 @@ _CONFIGS = {
         hooks=(2, 5, 8, 11), pos_grid=12,
         reassemble=(96, 192, 384, 768),
         resample=(("convT", 8), ("convT", 4), ("convT", 2), ("id", 0)),
+    ),
+    # lseg_vit_zs.py:742-760 + lseg_blocks_zs.py:44-50: torchvision ResNet-101 (stages at H/4 .. H/32, 256 .. 2048 channels) + the
+    # text tower of CLIP ViT-B/32; zero-shot only (LSegRNNetZS, lseg_net_zs.py:243-363)
+    "clip_resnet101": LSegConfig(
+        name="clip_resnet101", patch=32, dim=0, depth=0, heads=1,
+        hooks=(0, 0, 0, 0), pos_grid=0,
+        reassemble=(256, 512, 1024, 2048),
+        resample=(("id", 0), ("id", 0), ("id", 0), ("id", 0)),
+        tower="resnet101",
     ),
     # reduced twins for tests (NOT reference variants)
     "tiny16": LSegConfig(

@@ -66,7 +66,8 @@ def to_c_config(cfg: LSegConfig, img_h: int, img_w: int, max_batch: int, max_lab
     # "strict": split-precision validation mode ((hi, lo) fp16 operand pairs, ~21 mantissa bits; include/lseg_hip.h)
     c.image_dtype = {"bf16": _lib.LSEG_BF16, "fp16": _lib.LSEG_F16, "strict": _lib.LSEG_F16_SPLIT}[image_dtype]
     c.flags = ((1 if full_text_context else 0) | (2 if exact_head_grad else 0) | (4 if batch_invariant else 0)
-               | (8 if deterministic else 0) | (16 if head_block_training else 0))
+               | (8 if deterministic else 0) | (16 if head_block_training else 0)
+               | (32 if cfg.tower == "resnet101" else 0))          # torchvision ResNet-101 image tower (the ViT fields are ignored)
     return c
 
 

@@ -40,11 +40,57 @@ def synthetic_state_dict(cfg: LSegConfig, seed: int = 0, clip_fp16: bool = True,
     """
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
-    D, P = cfg.dim, cfg.patch
 
     def put(k, t):
         sd[with_prefix + k] = t.contiguous()
 
+    if cfg.tower == "resnet101":
+        _resnet101_params(g, put)
+    else:
+        _vit_params(g, put, cfg)
+    _scratch_and_text_params(g, put, cfg, clip_fp16)
+    return sd
+
+
+# torchvision ResNet-101 stages (blocks, width, first stride) as lseg_vit_zs.py:_make_resnet_backbone keeps them
+RESNET101_STAGES = ((3, 64, 1), (4, 128, 2), (23, 256, 2), (3, 512, 2))
+
+
+def resnet101_stage_prefixes():
+    """State-dict prefix of block j of stage l (0-based): layer1 is Sequential(conv1, bn1, relu, maxpool, layer1) in the reference."""
+    return [[(f"pretrained.layer1.4.{j}." if l == 0 else f"pretrained.layer{l + 1}.{j}.") for j in range(n)]
+            for l, (n, _, _) in enumerate(RESNET101_STAGES)]
+
+
+def _resnet101_params(g, put):
+    """Bottleneck v1.5 weights.  He-scaled convs keep every branch O(1); bn3.weight ~ 0.2 keeps the residual stream of the 23-block
+    stage O(1-10) (each block adds a fifth of an O(1) branch), so fp16 operands never come near their range on the fixtures."""
+    def bn(p, c, gain=1.0):
+        put(p + "weight", gain * (1.0 + _randn(g, (c,), 0.1)))
+        put(p + "bias", _randn(g, (c,), 0.05))
+        put(p + "running_mean", _randn(g, (c,), 0.1))
+        put(p + "running_var", 0.5 + torch.rand((c,), generator=g, dtype=torch.float32))
+        put(p + "num_batches_tracked", torch.tensor(100, dtype=torch.int64))
+
+    put("pretrained.layer1.0.weight", _randn(g, (64, 3, 7, 7), math.sqrt(2.0 / 147)))
+    bn("pretrained.layer1.1.", 64)
+    cin = 64
+    for (n, w, _), prefixes in zip(RESNET101_STAGES, resnet101_stage_prefixes()):
+        for j, p in enumerate(prefixes):
+            put(p + "conv1.weight", _randn(g, (w, cin, 1, 1), math.sqrt(2.0 / cin)))
+            bn(p + "bn1.", w)
+            put(p + "conv2.weight", _randn(g, (w, w, 3, 3), math.sqrt(2.0 / (9 * w))))
+            bn(p + "bn2.", w)
+            put(p + "conv3.weight", _randn(g, (4 * w, w, 1, 1), math.sqrt(1.0 / w)))
+            bn(p + "bn3.", 4 * w, gain=0.2)
+            if j == 0:
+                put(p + "downsample.0.weight", _randn(g, (4 * w, cin, 1, 1), math.sqrt(1.0 / cin)))
+                bn(p + "downsample.1.", 4 * w)
+            cin = 4 * w
+
+
+def _vit_params(g, put, cfg):
+    D, P = cfg.dim, cfg.patch
     # ---- timm VisionTransformer (pretrained.model.*) -------------------------------
     vm = "pretrained.model."
     put(vm + "cls_token", _randn(g, (1, 1, D), 0.02))
@@ -85,6 +131,8 @@ def synthetic_state_dict(cfg: LSegConfig, seed: int = 0, clip_fp16: bool = True,
             put(a + "4.weight", _randn(g, (C, C, 3, 3), 1.0 / math.sqrt(9 * C)))
             put(a + "4.bias", _randn(g, (C,), 0.02))
 
+
+def _scratch_and_text_params(g, put, cfg, clip_fp16):
     # ---- scratch (DPT head) ---------------------------------------------------------
     F_ = cfg.features
     for lvl in range(4):
@@ -134,7 +182,6 @@ def synthetic_state_dict(cfg: LSegConfig, seed: int = 0, clip_fp16: bool = True,
     put(cp + "ln_final.bias", _randn(g, (W,), 0.05))
     put(cp + "text_projection", _randn(g, (W, t.embed_dim), 1.0 / math.sqrt(W)).to(lin_dt))
     put(cp + "logit_scale", torch.tensor(math.log(1 / 0.07), dtype=torch.float32))
-    return sd
 
 
 def synthetic_tokens(labels: List[str], vocab: int = 49408, ctx: int = 77) -> torch.Tensor:

@@ -1,6 +1,7 @@
 """LSegModuleZS -- the reference's zero-shot module surface (modules/lseg_module_zs.py:20-73).
 
 `LSegModuleZS(data_path, dataset, batch_size, base_lr, max_epochs, **kwargs)` builds `self.net = LSegNetZS(label_list=...)`
+(`LSegRNNetZS` for backbone="clip_resnet101")
 from `label_files/fewshot_<dataset>.txt` (get_labels, :60-71) and forwards `(x, class_info)` to it
 (lsegmentation_module_zs.py:82-83).  Criterion, training_step and configure_optimizers come from LSegmentationModuleZS
 (modules/lsegmentation_module_zs.py), as in the reference.  The few-shot episode loaders / Evaluator of lsegmentation_module_zs.py
@@ -21,8 +22,10 @@ class LSegModuleZS(LSegmentationModuleZS):
         label_list = self.get_labels(dataset)
         self.len_dataloader = len(label_list)
         use_pretrained = kwargs.get("use_pretrained", True) in ("True", True)
-        if kwargs.get("backbone", "clip_vitl16_384") in ["clip_resnet101"]:
-            self.net = LSegRNNetZS()
+        if kwargs.get("backbone", "clip_vitl16_384") in ["clip_resnet101"]:         # :33-43
+            self.net = LSegRNNetZS(label_list=label_list, backbone=kwargs["backbone"], features=kwargs.get("num_features", 256),
+                                   aux=kwargs.get("aux", False), use_pretrained=use_pretrained, arch_option=kwargs.get("arch_option", 0),
+                                   block_depth=kwargs.get("block_depth", 0), activation=kwargs.get("activation", "lrelu"))
         else:
             self.net = LSegNetZS(label_list=label_list, backbone=kwargs.get("backbone", "clip_vitl16_384"),
                                  features=kwargs.get("num_features", 256), aux=kwargs.get("aux", False),

@@ -3,14 +3,15 @@ modules/models/lseg_blocks.py:60-110 (_make_scratch), :113-147 (Interpolate), :2
 (ResidualConvUnit_custom), :293-358 (FeatureFusionBlock_custom).  No PyTorch compute here."""
 import torch.nn as nn
 
+from .lseg_resnet import make_resnet101_backbone
 from .lseg_vit import _NoForward, make_backbone, make_clip_text
 
 
 def _make_encoder(cfg):
-    """(clip_pretrained, pretrained, scratch) like lseg_blocks.py:12-57; unknown backbones are
-    rejected earlier by lseg_hip.config.get_config the way the reference does (print + assert)."""
+    """(clip_pretrained, pretrained, scratch) like lseg_blocks.py:12-57 (lseg_blocks_zs.py:44-50 for clip_resnet101); unknown
+    backbones are rejected earlier by lseg_hip.config.get_config the way the reference does (print + assert)."""
     clip_pretrained = make_clip_text(cfg.text)
-    pretrained = make_backbone(cfg)
+    pretrained = make_resnet101_backbone() if cfg.tower == "resnet101" else make_backbone(cfg)
     scratch = _make_scratch(list(cfg.reassemble), cfg.features)
     return clip_pretrained, pretrained, scratch
 

@@ -11,8 +11,9 @@ forward is the engine's train-mode step with the same grouping -- one autograd n
 as LSegNet's -- and `forward_loss(x, class_info, target)` is criterion(forward(x, class_info), target) as ONE node (fused
 cross-entropy over the 2 label planes, no [B, 2, H, W] logits).
 
-Only the ViT backbones are implemented (clip_vitl16_384, clip_vitb32_384); the reference's clip_resnet101 / RN50x*
-variants (LSegRNNetZS, lseg_net_zs.py:243-363) raise.
+LSegRNNetZS (lseg_net_zs.py:243-363) is the same network on the clip_resnet101 backbone: torchvision's ResNet-101 as the image
+tower (lseg_config.flags bit 5, csrc/resnet.hip), the neck, head and CLIP ViT-B/32 text tower as above.  Inference only: its
+train-mode forward raises.
 """
 import numpy as np
 from collections import OrderedDict
@@ -133,6 +134,34 @@ class LSegNetZS(LSeg):
             self.load(path)
 
 
-class LSegRNNetZS(BaseModel):                         # lseg_net_zs.py:243-363 (clip_resnet101 backbone)
-    def __init__(self, *a, **k):
-        raise NotImplementedError("the CLIP-ResNet101 zero-shot backbone is outside the HIP engine's scope (ViT backbones only)")
+class LSegRNNetZS(LSeg):
+    """Zero-shot network on the CLIP-ResNet-101 backbone (lseg_net_zs.py:243-363): the reference's LSegRN module tree
+    (clip_pretrained = CLIP ViT-B/32, pretrained.layer1..4 = torchvision ResNet-101, scratch with BN refinenets, head1, output_conv)
+    and `forward(x, class_info) -> float32 [B, 2, H, W]` through the HIP engine.  Inference only."""
+
+    def __init__(self, label_list=None, path=None, scale_factor=0.5, aux=False, use_relabeled=False, use_pretrained=True, **kwargs):
+        if label_list is None:
+            raise NotImplementedError("LSegRNNetZS needs a label_list (one ['others', label] token pair per class)")
+        features = kwargs["features"] if "features" in kwargs else 256
+        kwargs["use_bn"] = True
+        kwargs["backbone"] = kwargs.get("backbone", "clip_resnet101")
+        if kwargs["backbone"] != "clip_resnet101":
+            raise NotImplementedError(f"LSegRNNetZS implements backbone='clip_resnet101' (got {kwargs['backbone']!r})")
+        self.scale_factor = scale_factor
+        self.aux = aux
+        self.use_relabeled = use_relabeled
+        self.label_list = label_list
+        self.use_pretrained = use_pretrained
+        head = nn.Sequential(Interpolate(scale_factor=2, mode="bilinear", align_corners=True))
+        super().__init__(head, **kwargs)
+        if path is not None:
+            self.load(path)
+
+    def forward(self, x, class_info):
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError("LSegRNNetZS is inference only (the ResNet-101 tower has no train-mode BatchNorm / backward): "
+                                      "call net.eval() or run under torch.no_grad()")
+        return super().forward(x, class_info)
+
+    def forward_loss(self, x, class_info, target, ignore_index=-100):
+        raise NotImplementedError("LSegRNNetZS is inference only")
