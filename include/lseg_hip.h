@@ -171,6 +171,20 @@ int lseg_set_text_grouping(lseg_handle h, int labels_per_image);
 int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out,
                  uint8_t* dev_argmax_out, void* stream);
 
+/* Masks for any K <= 32767 without the logits in memory.
+ * replaces: LSeg.forward (lseg_net.py:160-205) through the correlation of lseg_net.py:194-203 AND the caller's torch.max(pred, 1)
+ *   (lsegmentation_module.py:114-117) -- the [B,K,img_h,img_w] logits (922 MB per image at K = 1000) are neither written nor read.
+ *   dev_label_out int16 [B,img_h,img_w]: arg-max over the labels of exactly the logits lseg_forward would have written (first maximum
+ *                  wins); with per-image label sets the index within the image's own k labels
+ *   dev_score_out  fp32 [B,img_h,img_w]: the winning logit; optional, may be NULL
+ * On the commuted schedule with one shared label set, out_c = 512 and arch_option 0 the labels are STREAMED (csrc/corr_argmax.hip: text
+ * panels through LDS, a running (best, label) pair per output pixel).  Every other configuration (other widths, head blocks, per-image
+ * label sets, the split-precision mode, LSEG_CORR_GENERIC) forms the low-resolution logits as lseg_forward does and takes the arg-max
+ * through the x2 bilinear on the fly, like dev_argmax_out.  Text cache / external text features, the overflow sentinel and flags bit 2
+ * behave as in lseg_forward.  After a STREAMED forward no low-resolution logits exist: lseg_forward_stats and the "lowres" tap return
+ * LSEG_ERR_STATE until another forward has run.  K > 32767, train mode: LSEG_ERR_UNSUPPORTED. */
+int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, void* stream);
+
 /* The metric / loss step after the path, without the full-resolution logits: statistics of the LAST lseg_forward's output against a
  * target mask -- replaces batch_pix_accuracy + batch_intersection_union on `pred` (lsegmentation_module.py:49-50,59-60) and the value
  * of the criterion (:72).  dev_target int64 [B,img_h,img_w]; dev_counts / dev_nll as in lseg_op_seg_stats. */
@@ -325,6 +339,20 @@ int lseg_op_seg_stats_lowres(const float* d_low, const int64_t* d_target, int B,
  * g(x+1).g(y+1)} or NULL (planes only).  LSEG_ERR_UNSUPPORTED for other C / larger K (the engine then takes its generic GEMM). */
 int lseg_op_corr_planes(const void* d_g16pad, const void* d_text16, float* d_planes, float* d_gram, int B, int K, int H, int W, int C,
                         void* stream);
+/* The streamed-panel correlation + arg-max behind lseg_forward_labels, bare (csrc/corr_argmax.hip).
+ * replaces: lseg_net.py:194-203 (correlation, the two x2 bilinears with the per-pixel scale and the fp16 rounding between them) followed by
+ *   torch.max(pred, 1) (lsegmentation_module.py:114-117), for any K: d_label[b, y, x] = first arg-max over k of the value
+ *   lseg_op_upsample4x_planes_scaled would write to out[b, k, y, x] from lseg_op_corr_planes' planes; d_score = that value.
+ * d_g16pad fp16 [B, H+2, W+2, C] (C = 512); d_text16 fp16 [K, C]; d_scale fp32 [B, 2H, 2W]; d_label int16 [B, 4H, 4W]; d_score fp32
+ * [B, 4H, 4W] or NULL.  H, W >= 2.  d_ws / ws_bytes: optional workspace -- with 96 B H W bytes per part the labels of a tile are split over
+ * up to 8 workgroups and merged (same result: ascending parts, first maximum wins); NULL = one workgroup per tile streams all K.
+ * LSEG_ERR_UNSUPPORTED for other C, K > 32767 or maps beyond the kernel's 32-bit offsets. */
+int lseg_op_corr_argmax(const void* d_g16pad, const void* d_text16, const float* d_scale, int16_t* d_label, float* d_score, int B, int K,
+                        int H, int W, int C, void* d_ws, size_t ws_bytes, void* stream);
+/* The tile geometry that kernel was compiled with (host memory, no device needed), for the CPU index model of its tile -> footprint
+ * mapping: out8 = {mid rows/columns per tile band, mid rows/columns of its footprint, base rows/columns of its footprint, labels per
+ * panel, LDS pitch of a text row in bytes, labels per interpolation chunk, output rows per wave, dynamic LDS bytes}. */
+int lseg_op_corr_argmax_geometry(int* out8);
 
 /* Device side of the multi-scale / flip sliding-window evaluator that calls the forward (additional_utils/encoding_models.py:54-155
  * MultiEvalModule.forward, module_inference, pad_image, crop_image, flip_image; additional_utils/models.py:55-140).  Per scale:

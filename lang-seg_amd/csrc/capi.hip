@@ -92,6 +92,12 @@ int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out
     return h->e->forward(dev_x, B, dev_logits_out, dev_argmax_out, (hipStream_t)stream);
 }
 
+int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, void* stream) {
+    GUARD(h);
+    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
+    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out);
+}
+
 int lseg_forward_stats(lseg_handle h, const int64_t* dev_target, int ignore_index, int64_t* dev_counts, double* dev_nll, void* stream) {
     GUARD(h);
     return h->e->forward_stats(dev_target, ignore_index, dev_counts, dev_nll, (hipStream_t)stream);
@@ -379,6 +385,17 @@ int lseg_op_head_features(const void* x_bf16, const void* w_bf16, const float* b
     g.A = (const uint16_t*)x_bf16; g.W = (const uint16_t*)w_bf16; g.M = M; g.N = 512; g.K = F; g.lda = F; g.ldw = F;
     g.bias = bias; g.C = a_f16; g.out_dtype = DT_F16; g.ldc = 512; g.map_mode = MAP_ROWNORM; g.rn_scale = logit_scale;
     return launch_gemm(g, DT_BF16, (hipStream_t)stream);
+}
+
+int lseg_op_corr_argmax(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int B, int K, int H, int W,
+                        int C, void* d_ws, size_t ws_bytes, void* stream) {
+    return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, d_label, d_score, B, K, H, W, C, (hipStream_t)stream, d_ws, ws_bytes);
+}
+
+int lseg_op_corr_argmax_geometry(int* out8) {
+    if (!out8) return set_error(LSEG_ERR_INVALID, "corr_argmax_geometry: NULL pointer");
+    corr_argmax_geometry(out8);
+    return LSEG_OK;
 }
 
 int lseg_op_seg_stats(const float* d_scores, const int64_t* d_target, int B, int K, int H, int W, int ignore_index,

@@ -52,6 +52,21 @@ __device__ __forceinline__ float bilerp(float a, float b, float c, float d, floa
     const float h0 = __builtin_fmaf(lx, b, wx * a), h1 = __builtin_fmaf(lx, d, wx * c);
     return __builtin_fmaf(ly, h1, wy * h0);
 }
+// The arithmetic of the commuted head's x4 path (label plane R -> scaled fp16 (2h, 2w) logit -> output_conv's x2 bilinear), shared by
+// every kernel that evaluates it (upsample4x_planes_scaled_kernel writes the values, corr_argmax_kernel reduces them): same operations
+// in the same association = same bits.
+//   ups_low_value: one (2h, 2w) logit = fp16(scale * bilerp(R taps)) -- the rounding of the reference's `half @ half`
+//   hlerp / vlerp: bilerp() split into its horizontal and vertical halves, so that a horizontal result can be kept across output rows
+// The product is pinned to an fp32 register before the fp16 rounding: left to itself the compiler folds multiply + conversion into
+// v_fma_mixlo_f16 in some contexts (ONE rounding of the exact product) and keeps v_mul_f32 + v_cvt in others (two roundings) -- one fp16
+// ulp apart on ~1e-4 of the values.
+__device__ __forceinline__ float ups_low_value(float sc, float a, float b, float c, float d, float lx, float ly) {
+    float m = sc * bilerp(a, b, c, d, lx, ly);
+    asm("" : "+v"(m));
+    return round_f16(m);
+}
+__device__ __forceinline__ float hlerp(float a, float b, float l) { return __builtin_fmaf(l, b, (1.f - l) * a); }   // bilerp()'s h0 / h1
+__device__ __forceinline__ float vlerp(float h0, float h1, float ly) { return __builtin_fmaf(ly, h1, (1.f - ly) * h0); }
 
 template <typename T> __device__ __forceinline__ float to_f32(uint16_t v);
 template <> __device__ __forceinline__ float to_f32<BF16>(uint16_t v) { return bf16_to_f32(v); }

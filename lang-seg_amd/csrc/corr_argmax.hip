@@ -1,0 +1,415 @@
+// corr_argmax.hip -- masks for label sets of any size: the pixel x text correlation of LSeg (modules/models/lseg_net.py:187-196), the two
+// x2 bilinears behind it (lseg_net.py:203) and torch.max(pred, 1) (lsegmentation_module.py:114-117) as ONE gfx950 kernel that never
+// writes a label plane.  Per output pixel it keeps a running (best value, best label) pair while the labels stream past in panels.
+//
+// Inputs are what the engine holds on the commuted low-resolution schedule (engine.hip "commuted correlation"): g = padded NHWC fp16
+// [B, h+2, w+2, 512], T = normalised fp16 text features [K, 512], scale = the per-pixel factor of norm_scale_plane_kernel [B, 2h, 2w].
+// Outputs: label int16 [B, 4h, 4w] and (optional) score fp32 [B, 4h, 4w] = exactly the value upsample4x_planes_scaled_kernel would have
+// written to logits[b, label, y, x]: the same MFMA instruction / operand roles / k order as corr_planes_kernel and the generic GEMM's
+// MAP_LABELPLANES for R, and the shared interpolation functions of common.h (ups_low_value, hlerp, vlerp) behind it.
+//
+// Structure (one workgroup = 4 waves = one tile; the TILE is the outer loop, the label PANEL the inner one):
+//   * tile = a band of CA_LB x CA_LB pixels of the (2h, 2w) "mid" map; it owns the output pixels whose upper-left mid tap lies in the
+//     band (what upsample4x_planes_scaled_kernel does per row band).  Their footprint is <= 29 x 29 mid pixels and <= 16 x 16 base
+//     pixels (tests/test_corr_argmax_host.py pins the mapping; the launcher re-checks it for the shape at hand).
+//   * the tile's g -- 16 fragments of 16 pixels x 512 channels -- is loaded ONCE into MFMA operand registers (wave v: base rows 4v..4v+3)
+//     and stays there while the panels stream: g traffic = 256 KB per tile whatever K is.
+//   * per panel of CA_P = 48 labels: T rows -> LDS (pitch 1040 B, re-streamed from L2 per tile), 192 v_mfma_f32_16x16x32_f16 per wave
+//     with the pixels as rows, accumulators -> LDS staging Rs [48][16 x 16] fp32.
+//   * per chunk of 16 labels: all threads form the (2h, 2w) logits of the footprint, Lr [16][29 x 29]; then every lane owns one output
+//     COLUMN and <= 15 consecutive output rows (wave = row group): for the chunk's labels in ascending order it walks its rows with
+//     rolling horizontal interpolants (the row taps are wave-uniform and live in scalar registers) and keeps (best, arg) with a
+//     strict `>` -- the first maximum wins, as in torch.max.
+//   * (best, arg) never leave the registers until the last panel: 6 bytes are written per output pixel, once.
+//   * a 120 x 120 map has 81 tiles per image for 256 CUs: given a workspace the launcher splits the labels of a tile over up to 8
+//     workgroups (whole panels each, the split that minimises rounds x panels), each writes its (score, label) plane, and a merge
+//     kernel takes them in ascending label order with the same strict `>` (6 B x pixels x splits through HBM, ~17 MB at B = 4).
+// LDS: T 49 920 + Rs 49 920 + Lr 54 016 + row taps 1 024 = 154 880 B of the CU's 160 KB.
+// Traffic per image at 120 x 120, K = 1000 (81 tiles, 21 panels): g 21 MB (halo included) from HBM, T 81 x 1 MB from L2, 1.4 MB written --
+// against the 922 MB logits write (and read) this replaces.  The panel-outer alternative would read g 15 MB x 21 panels and carry the
+// state through HBM (6 B x 230 400 pixels x 2 x 21 = 58 MB).  Bound: VALU (the interpolation), not memory and not MFMA -- see DESIGN §3.4.
+#include "ops.h"
+#include "gemm.h"
+#include "../../include/lseg_hip.h"
+
+#include <atomic>
+
+namespace lseg {
+namespace {
+
+constexpr int CA_C = 512;                   // channels
+constexpr int CA_KS = CA_C / 32;            // k-steps of 32 channels
+constexpr int CA_PITCH = CA_C * 2 + 16;     // LDS row pitch of T in bytes
+constexpr int CA_LB = 28;                   // mid rows / columns of a tile's band
+constexpr int CA_MT = CA_LB + 1;            // mid rows / columns of its footprint
+constexpr int CA_BT = 16;                   // base rows / columns of its footprint (= one MFMA fragment of pixels per row)
+constexpr int CA_P = 48;                    // labels per panel
+constexpr int CA_NLB = CA_P / 16;
+constexpr int CA_LC = 16;                   // labels per interpolation chunk
+constexpr int CA_LU = 8;                    // labels that walk the output rows together
+constexpr int CA_RP = CA_BT * CA_BT + 4;    // floats per label in Rs (+4: the 16 labels of a store land in different banks)
+constexpr int CA_LP = (CA_MT * CA_MT + 3) / 4 * 4;   // floats per label in Lr
+constexpr int CA_ROWS = 15;                 // output rows per wave
+constexpr int CA_OMAX_Y = 4 * CA_ROWS;      // owned output rows per tile (<= 58 by construction)
+constexpr int CA_OMAX_X = 64;               // owned output columns per tile (one per lane)
+constexpr int CA_SLOTS = (CA_MT * CA_MT + 255) / 256;
+constexpr size_t CA_LDS = (size_t)CA_P * CA_PITCH + (size_t)CA_P * CA_RP * 4 + (size_t)CA_LC * CA_LP * 4 + 64 * 16;
+
+// first output index whose upper tap floor(r * o) is >= a   (r = (n_mid - 1) / (n_out - 1), the kernel's own float arithmetic)
+__host__ __device__ inline int ca_first_out(float r, int a) {
+    int o = (int)ceilf((float)a / r);
+    while (o > 0 && (int)(r * (float)(o - 1)) >= a) --o;
+    while ((int)(r * (float)o) < a) ++o;
+    return o;
+}
+__host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_out) {
+    int o = first;
+    while (o < n_out && (int)(r * (float)o) < a_end) ++o;
+    return o;
+}
+
+__global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ T,
+                                                            const float* __restrict__ scale, int16_t* __restrict__ label,
+                                                            float* __restrict__ score, int B, int K, int H, int W, int tiles_y, int tiles_x,
+                                                            int nsplit, int split_labels, size_t split_stride) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    char* tlds = lds;
+    float* Rs = reinterpret_cast<float*>(lds + CA_P * CA_PITCH);
+    float* Lr = Rs + CA_P * CA_RP;
+    int4* rtab = reinterpret_cast<int4*>(Lr + CA_LC * CA_LP);
+    const int HP = H + 2, WP = W + 2, Hl = 2 * H, Wl = 2 * W, Ho = 4 * H, Wo = 4 * W;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, kg = lane >> 4;
+
+    // label split `sp` of tile `ut` covers labels [k_lo, k_hi) (whole panels) and writes plane `sp` of the (label, score) workspace
+    const unsigned ut = blockIdx.x / (unsigned)nsplit, sp = blockIdx.x - ut * (unsigned)nsplit;
+    const int k_lo = (int)sp * split_labels, k_hi = k_lo + split_labels < K ? k_lo + split_labels : K;
+    const unsigned q = ut / (unsigned)tiles_x, tx = ut - q * (unsigned)tiles_x;
+    const unsigned b = q / (unsigned)tiles_y, ty = q - b * (unsigned)tiles_y;
+    const int Ya = (int)ty * CA_LB, Xa = (int)tx * CA_LB;
+    const int Yb = Ya + CA_LB < Hl - 1 ? Ya + CA_LB : Hl - 1, Xb = Xa + CA_LB < Wl - 1 ? Xa + CA_LB : Wl - 1;   // last mid row / column read
+    const int nmy = Yb - Ya + 1, nmx = Xb - Xa + 1;
+    const float ry1 = (float)(H - 1) / (float)(Hl - 1), rx1 = (float)(W - 1) / (float)(Wl - 1);
+    const float ry2 = (float)(Hl - 1) / (float)(Ho - 1), rx2 = (float)(Wl - 1) / (float)(Wo - 1);
+    const int by_lo = (int)(ry1 * (float)Ya), bx_lo = (int)(rx1 * (float)Xa);            // base origin of the footprint
+
+    // ---- owned output rows / columns; the row taps of the tile -> LDS -> scalar registers -------------------------------------------
+    const int yo_first = ca_first_out(ry2, Ya), yo_end = ca_end_out(ry2, yo_first, Ya + CA_LB, Ho);
+    const int xo_first = ca_first_out(rx2, Xa), xo_end = ca_end_out(rx2, xo_first, Xa + CA_LB, Wo);
+    if (tid < 64) {
+        int yo = yo_first + tid;
+        yo = yo < yo_end ? yo : yo_end - 1;
+        int y0, y1;
+        float ly;
+        src_tap(ry2, yo, Hl, y0, y1, ly);
+        rtab[tid] = make_int4((y0 - Ya) * CA_MT, (y1 - Ya) * CA_MT, __float_as_int(ly), 0);
+    }
+    const int per = (yo_end - yo_first + 3) / 4;                         // <= CA_ROWS (launcher)
+    const int ys = yo_first + wave * per;
+    const int nrow = ys >= yo_end ? 0 : (ys + per < yo_end ? per : yo_end - ys);
+    int xo = xo_first + lane;
+    const bool cvalid = xo < xo_end;
+    xo = cvalid ? xo : xo_end - 1;
+    int cx0, cx1;
+    float clx;
+    src_tap(rx2, xo, Wl, cx0, cx1, clx);
+    cx0 -= Xa; cx1 -= Xa;
+
+    // ---- this thread's mid pixels of the footprint (stage 1) -------------------------------------------------------------------------
+    int s_roff[CA_SLOTS], s_dx[CA_SLOTS], s_dy[CA_SLOTS], s_loff[CA_SLOTS];
+    float s_lx[CA_SLOTS], s_ly[CA_SLOTS], s_sc[CA_SLOTS];
+#pragma unroll
+    for (int s = 0; s < CA_SLOTS; ++s) {
+        const int i = tid + 256 * s;
+        const bool ok = i < nmy * nmx;
+        const int my = ok ? i / nmx : 0, mx = ok ? i - my * nmx : 0;
+        int y0, y1, x0, x1;
+        src_tap(ry1, Ya + my, H, y0, y1, s_ly[s]);
+        src_tap(rx1, Xa + mx, W, x0, x1, s_lx[s]);
+        s_roff[s] = (y0 - by_lo) * CA_BT + (x0 - bx_lo);
+        s_dx[s] = x1 - x0;
+        s_dy[s] = (y1 - y0) * CA_BT;
+        s_loff[s] = ok ? my * CA_MT + mx : -1;
+        s_sc[s] = scale[((size_t)b * Hl + Ya + my) * Wl + Xa + mx];
+    }
+
+    // ---- g: the tile's fragments, once (rows / columns clamped into the map: a clamped pixel is a copy nothing reads) ------------------
+    i32x4_t gf[CA_KS][4];
+    {
+        int bx = bx_lo + c;
+        bx = bx < W - 1 ? bx : W - 1;
+        const char* gbase = reinterpret_cast<const char*>(g);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            int by = by_lo + 4 * wave + rr;
+            by = by < H - 1 ? by : H - 1;
+            const uint32_t off = (((uint32_t)b * (uint32_t)HP + (uint32_t)(1 + by)) * (uint32_t)WP + (uint32_t)(1 + bx)) * (CA_C * 2) + (uint32_t)kg * 16u;
+#pragma unroll
+            for (int ks = 0; ks < CA_KS; ++ks) gf[ks][rr] = *reinterpret_cast<const i32x4_t*>(gbase + off + ks * 64);
+        }
+    }
+    __syncthreads();                                                    // rtab
+    int r_y0[CA_ROWS], r_y1[CA_ROWS];
+    float r_ly[CA_ROWS];
+#pragma unroll
+    for (int j = 0; j < CA_ROWS; ++j) {
+        int idx = ys - yo_first + j;
+        idx = idx < 63 ? idx : 63;
+        const int4 e = rtab[idx];
+        r_y0[j] = __builtin_amdgcn_readfirstlane(e.x);
+        r_y1[j] = __builtin_amdgcn_readfirstlane(e.y);
+        r_ly[j] = __int_as_float(__builtin_amdgcn_readfirstlane(e.z));
+    }
+
+    float best[CA_ROWS];
+    int arg[CA_ROWS];
+#pragma unroll
+    for (int j = 0; j < CA_ROWS; ++j) { best[j] = -INFINITY; arg[j] = 0; }
+
+    for (int pb = k_lo; pb < k_hi; pb += CA_P) {
+        // ---- T panel -> LDS (rows past K repeat the last label: computed, never compared) ------------------------------------------------
+        for (int i = tid; i < CA_P * (CA_C / 8); i += 256) {
+            const int row = i / (CA_C / 8), ch = i - row * (CA_C / 8);
+            int lab = pb + row;
+            lab = lab < K ? lab : K - 1;
+            *reinterpret_cast<i32x4_t*>(tlds + row * CA_PITCH + ch * 16) = *reinterpret_cast<const i32x4_t*>(T + (size_t)lab * CA_C + ch * 8);
+        }
+        __syncthreads();
+        // ---- R tile of the panel: pixels as rows, one accumulator chain over the 16 k-steps in ascending order --------------------------
+        {
+            f32x4_t acc[CA_NLB][4];
+#pragma unroll
+            for (int lb = 0; lb < CA_NLB; ++lb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) acc[lb][rr] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            // the T fragments of k-step ks + 1 are requested before the MFMAs of k-step ks: with one wave per SIMD nothing else hides the LDS
+            auto tread = [&](int ks, int lb) { return *reinterpret_cast<const i32x4_t*>(tlds + (lb * 16 + c) * CA_PITCH + kg * 16 + ks * 64); };
+            i32x4_t tf[2][CA_NLB];
+#pragma unroll
+            for (int lb = 0; lb < CA_NLB; ++lb) tf[0][lb] = tread(0, lb);
+#pragma unroll
+            for (int ks = 0; ks < CA_KS; ++ks) {
+                if (ks + 1 < CA_KS) {
+#pragma unroll
+                    for (int lb = 0; lb < CA_NLB; ++lb) tf[(ks + 1) & 1][lb] = tread(ks + 1, lb);
+                }
+#pragma unroll
+                for (int lb = 0; lb < CA_NLB; ++lb)
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) acc[lb][rr] = mfma16<F16>(gf[ks][rr], tf[ks & 1][lb], acc[lb][rr]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // D rows 4 kg .. 4 kg + 3 = 4 consecutive pixels of base row 4 wave + rr, D column c = label 16 lb + c
+#pragma unroll
+            for (int lb = 0; lb < CA_NLB; ++lb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    *reinterpret_cast<f32x4_t*>(Rs + (lb * 16 + c) * CA_RP + (4 * wave + rr) * CA_BT + 4 * kg) = acc[lb][rr];
+        }
+        __syncthreads();
+        for (int cb = 0; cb < CA_P && pb + cb < K; cb += CA_LC) {
+            // ---- stage 1: the (2h, 2w) logits of the footprint for the chunk's 16 labels (rows past K repeat the last label) -------------
+            // One wave per SIMD: nothing but the next labels' reads hides an LDS round trip, so four labels are in flight per pass
+#pragma unroll 4
+            for (int l = 0; l < CA_LC; ++l) {
+                const float* Rl = Rs + (cb + l) * CA_RP;
+                float* Ll = Lr + l * CA_LP;
+#pragma unroll
+                for (int s = 0; s < CA_SLOTS; ++s) {
+                    if (s_loff[s] < 0) continue;
+                    const float* p = Rl + s_roff[s];
+                    Ll[s_loff[s]] = ups_low_value(s_sc[s], p[0], p[s_dx[s]], p[s_dy[s]], p[s_dy[s] + s_dx[s]], s_lx[s], s_ly[s]);
+                }
+            }
+            __syncthreads();
+            // ---- stage 2: output_conv's bilinear + the running arg-max, labels in ascending order ----------------------------------------
+            // CA_LU labels walk the rows together: the row pattern (which mid row is new) is the same for every label, so one uniform
+            // branch serves CA_LU independent interpolants and their 2 CA_LU LDS reads are in flight at once
+            for (int l0 = 0; l0 < CA_LC && pb + cb + l0 < K; l0 += CA_LU) {
+                const float* Ll = Lr + l0 * CA_LP;
+                const int lab0 = pb + cb + l0;
+                float h0[CA_LU], h1[CA_LU];
+#pragma unroll
+                for (int u = 0; u < CA_LU; ++u) { h0[u] = 0.f; h1[u] = 0.f; }
+                int c0 = -1, c1 = -1;                                    // the mid rows h0 / h1 hold (wave-uniform)
+#pragma unroll
+                for (int j = 0; j < CA_ROWS; ++j) {
+                    if (j >= nrow) continue;                              // (wave-uniform)
+                    const int y0 = r_y0[j], y1 = r_y1[j];
+                    if (y0 != c0) {
+                        if (y0 == c1) {
+#pragma unroll
+                            for (int u = 0; u < CA_LU; ++u) h0[u] = h1[u];
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < CA_LU; ++u) h0[u] = hlerp(Ll[u * CA_LP + y0 + cx0], Ll[u * CA_LP + y0 + cx1], clx);
+                        }
+                        c0 = y0;
+                    }
+                    if (y1 != c1) {
+                        if (y1 == c0) {
+#pragma unroll
+                            for (int u = 0; u < CA_LU; ++u) h1[u] = h0[u];
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < CA_LU; ++u) h1[u] = hlerp(Ll[u * CA_LP + y1 + cx0], Ll[u * CA_LP + y1 + cx1], clx);
+                        }
+                        c1 = y1;
+                    }
+#pragma unroll
+                    for (int u = 0; u < CA_LU; ++u) {
+                        const float v = vlerp(h0[u], h1[u], r_ly[j]);
+                        if (lab0 + u < K && v > best[j]) { best[j] = v; arg[j] = lab0 + u; }      // first maximum wins
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    if (cvalid) {
+#pragma unroll
+        for (int j = 0; j < CA_ROWS; ++j) {
+            if (j >= nrow) continue;
+            const size_t o = (size_t)sp * split_stride + ((size_t)b * Ho + ys + j) * Wo + xo;
+            label[o] = (int16_t)arg[j];
+            if (score) score[o] = best[j];
+        }
+    }
+}
+
+// (label, score) planes of the label splits -> the final pair: ascending splits = ascending labels, strict `>` = the first maximum wins
+__global__ __launch_bounds__(256) void corr_argmax_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc, int nsplit, size_t n,
+                                                                int16_t* __restrict__ label, float* __restrict__ score) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float m = wsc[i];
+        int16_t a = wl[i];
+        for (int s = 1; s < nsplit; ++s) {
+            const float v = wsc[(size_t)s * n + i];
+            if (v > m) { m = v; a = wl[(size_t)s * n + i]; }
+        }
+        label[i] = a;
+        if (score) score[i] = m;
+    }
+}
+
+// the arg-max of the x2-upsampled logits read through the bilinear on the fly (seg_stats_kernel's `up` form, masks only) with an int16
+// label and an optional score: what the streamed kernel's callers get when the planes exist in memory
+__global__ __launch_bounds__(256) void seg_argmax16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
+                                                           int16_t* __restrict__ label, float* __restrict__ score) {
+    const int Wo = 2 * w, HW = 4 * h * w;
+    const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
+    const size_t kstride = (size_t)h * w;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i % HW);
+        const size_t b = i / HW;
+        const int yo = p / Wo, xo = p - yo * Wo;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_tap(ry, yo, h, y0, y1, ly);
+        src_tap(rx, xo, w, x0, x1, lx);
+        const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
+        const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
+        float m = -INFINITY;
+        int arg = 0;
+        for (int k = 0; k < K; ++k) {
+            const float* cc = col + (size_t)k * kstride;
+            const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
+            if (v > m) { m = v; arg = k; }
+        }
+        label[i] = (int16_t)arg;
+        if (score) score[i] = m;
+    }
+}
+
+// the tile -> footprint mapping for this shape, in the kernel's own arithmetic (tests/test_corr_argmax_host.py is its model)
+bool ca_tiles_fit(int n_base, int n_mid, int n_out, int max_out) {
+    const float r1 = (float)(n_base - 1) / (float)(n_mid - 1), r2 = (float)(n_mid - 1) / (float)(n_out - 1);
+    int covered = 0;
+    for (int a = 0; a < n_mid; a += CA_LB) {
+        const int bmid = a + CA_LB < n_mid - 1 ? a + CA_LB : n_mid - 1;
+        const int lo = (int)(r1 * (float)a);
+        int hi = (int)(r1 * (float)bmid);
+        hi += hi < n_base - 1;
+        if (hi - lo + 1 > CA_BT) return false;
+        const int first = ca_first_out(r2, a), end = ca_end_out(r2, first, a + CA_LB, n_out);
+        if (first != covered || end - first > max_out) return false;
+        covered = end;
+    }
+    return covered == n_out;
+}
+
+}  // namespace
+
+// the kernel's tile geometry, for the host-side index model: {CA_LB, CA_MT, CA_BT, CA_P, CA_PITCH, CA_LC, CA_ROWS, dynamic LDS bytes}
+void corr_argmax_geometry(int* out8) {
+    const int v[8] = {CA_LB, CA_MT, CA_BT, CA_P, CA_PITCH, CA_LC, CA_ROWS, (int)CA_LDS};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+}
+
+bool corr_argmax_supported(int K, int C) { return C == CA_C && K >= 1 && K <= 32767; }
+
+// g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W]; label: int16 [B, 4H, 4W]; score: fp32 [B, 4H, 4W] or NULL
+// ws (optional, ws_bytes): with 6 bytes x B x 16 H W per split the labels of a tile are split over up to 8 workgroups (whole panels each)
+// and merged afterwards -- a 120 x 120 map has only 81 tiles per image for 256 CUs; without it one workgroup per tile streams all K
+int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
+                       hipStream_t st, void* ws, size_t ws_bytes) {
+    if (!g || !T || !scale || !label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
+    if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
+    if (!corr_argmax_supported(K, C)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: K=%d C=%d (C must be 512, K >= 1)", K, C);
+    if (B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "corr_argmax: B=%d H=%d W=%d", B, H, W);
+    const int tiles_y = (2 * H + CA_LB - 1) / CA_LB, tiles_x = (2 * W + CA_LB - 1) / CA_LB;
+    const long ntiles = (long)B * tiles_y * tiles_x;
+    if (ntiles >= (1L << 31) || (size_t)B * (H + 2) * (W + 2) * CA_C * 2 >= ((size_t)1 << 32) || (size_t)B * 16 * H * W >= ((size_t)1 << 31))
+        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: B=%d %dx%d exceeds the kernel's 32-bit offsets", B, H, W);
+    if (!ca_tiles_fit(H, 2 * H, 4 * H, CA_OMAX_Y) || !ca_tiles_fit(W, 2 * W, 4 * W, CA_OMAX_X))
+        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: %dx%d: a tile's footprint exceeds %dx%d base pixels", H, W, CA_BT, CA_BT);
+    int dev = 0;
+    LSEG_HIP_TRY(hipGetDevice(&dev));
+    static std::atomic<unsigned long long> attr_done{0};             // per-device opt-in to > 64 KB of dynamic LDS (cf. corr.hip)
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_done.fetch_or(bit, std::memory_order_release);
+    }
+    // label splits: the fewest rounds x (panels per split + ~1 panel of set-up) over the CUs
+    const size_t npix = (size_t)B * 16 * H * W;
+    const int panels = (K + CA_P - 1) / CA_P, cus = device_cu_count(dev) > 0 ? device_cu_count(dev) : 1;
+    int nsplit = 1;
+    long best_cost = 0;
+    for (int s = 1; s <= 8 && s <= panels; ++s) {
+        const int per = (panels + s - 1) / s;
+        if ((per * (s - 1)) >= panels) continue;                       // the last split would be empty
+        if (s > 1 && (!ws || ws_bytes < (size_t)s * npix * 6 || ntiles * s >= (1L << 31))) break;
+        const long cost = ((ntiles * s + cus - 1) / cus) * (long)(per + 1);
+        if (s == 1 || cost < best_cost) { best_cost = cost; nsplit = s; }
+    }
+    const int split_labels = (panels + nsplit - 1) / nsplit * CA_P;
+    float* wsc = reinterpret_cast<float*>(ws);
+    int16_t* wl = nsplit > 1 ? reinterpret_cast<int16_t*>(wsc + (size_t)nsplit * npix) : nullptr;
+    hipLaunchKernelGGL(corr_argmax_kernel, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
+                       nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit, nsplit > 1 ? split_labels : K,
+                       nsplit > 1 ? npix : (size_t)0);
+    LSEG_HIP_TRY(hipGetLastError());
+    if (nsplit > 1) {
+        const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+        hipLaunchKernelGGL(corr_argmax_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, nsplit, npix, label, score);
+        LSEG_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// low: fp32 [B, K, h, w] (the (2h, 2w) logits of the engine); label int16 [B, 2h, 2w]; score fp32 [B, 2h, 2w] or NULL
+int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st) {
+    if (!low || !label) return set_error(LSEG_ERR_INVALID, "seg_argmax16: NULL pointer");
+    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_argmax16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
+    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_argmax16: B=%d h=%d w=%d", B, h, w);
+    const size_t npix = (size_t)B * 4 * h * w;
+    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(seg_argmax16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, label, score);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace lseg

@@ -647,7 +647,7 @@ __device__ __forceinline__ void ups_low4(const float* __restrict__ Rr, const flo
     const float4 sv = *reinterpret_cast<const float4*>(sc + (size_t)Y * (2 * W) + x4 * 4);
     const float se[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = round_f16(se[e] * bilerp(q0[t.x0[e]], q0[t.x1[e]], q1[t.x0[e]], q1[t.x1[e]], t.lx[e], ly));
+    for (int e = 0; e < 4; ++e) o[e] = ups_low_value(se[e], q0[t.x0[e]], q0[t.x1[e]], q1[t.x0[e]], q1[t.x1[e]], t.lx[e], ly);
 }
 __global__ __launch_bounds__(256) void upsample2x_planes_scaled_kernel(const float* __restrict__ in, const float* __restrict__ scale,
                                                                        float* __restrict__ out, int P, int K, int H, int W) {
@@ -686,7 +686,6 @@ __global__ __launch_bounds__(256) void upsample2x_planes_scaled_kernel(const flo
 // 6.9 TB/s (tools/fill_bench.py): the kernel is still bound by its phase structure (three barriers, global -> LDS -> LDS -> HBM), not by
 // the write.
 constexpr int UPS4_LB = 16;
-__device__ __forceinline__ float hlerp(float a, float b, float l) { return __builtin_fmaf(l, b, (1.f - l) * a); }   // bilerp()'s h0 / h1
 template <int LB>
 __global__ __launch_bounds__(256) void upsample4x_planes_scaled_kernel(const float* __restrict__ in, const float* __restrict__ scale,
                                                                        float* __restrict__ out, int P, int K, int H, int W) {
@@ -757,9 +756,7 @@ __global__ __launch_bounds__(256) void upsample4x_planes_scaled_kernel(const flo
                 }
                 c1 = y1;
             }
-            const float wy = 1.f - ly;
-            const f32x4_t ov = {__builtin_fmaf(ly, h1[0], wy * h0[0]), __builtin_fmaf(ly, h1[1], wy * h0[1]),
-                                __builtin_fmaf(ly, h1[2], wy * h0[2]), __builtin_fmaf(ly, h1[3], wy * h0[3])};
+            const f32x4_t ov = {vlerp(h0[0], h1[0], ly), vlerp(h0[1], h1[1], ly), vlerp(h0[2], h1[2], ly), vlerp(h0[3], h1[3], ly)};
             __builtin_nontemporal_store(ov, reinterpret_cast<f32x4_t*>(out + ((size_t)pl * Ho + yo) * Wo) + x4);     // written once, never re-read by the engine
         }
     }

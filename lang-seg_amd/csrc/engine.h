@@ -57,7 +57,10 @@ public:
     int set_text_features(const void* dev_feat_f16, int K, hipStream_t st);
     bool text_external_ = false;   // the text features were handed in (lseg_set_text_features): forward never runs the text tower
     int encode_text(hipStream_t st);
-    int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st);
+    // label_out / score_out (int16 / fp32 [B,img_h,img_w], lseg_forward_labels): masks for any K <= 32767; with no other output wanted the
+    // labels are streamed (corr_argmax.hip): no (2h, 2w) or full-resolution label plane is written
+    int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
+                float* score_out = nullptr);
     int get_text_features(void* out_f16, hipStream_t st);
     int forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st);
     int get_intermediate(const char* name, float* out, size_t cap, size_t* n, hipStream_t st);
@@ -139,6 +142,7 @@ private:
     bool finalized_ = false, inited_ = false;
     int last_B_ = 0, last_kout_ = 0;
     const float* last_low_ = nullptr;
+    bool labels_only_ = false;                                        // the last forward streamed its labels: low_ holds no planes of it
 
     // derived geometry
     int gh_, gw_, np_, ntok_, npad_, img_dt_;

@@ -870,13 +870,17 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
     return ns;
 }
 
-int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st) {
+int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out) {
     if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
     if (K_ < 1) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
     if (!x_in) return set_error(LSEG_ERR_INVALID, "x is NULL");
+    if (score_out && !label_out) return set_error(LSEG_ERR_INVALID, "a score output needs the label output");
+    if (label_out && (group_k > 0 ? group_k : K_) > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "int16 labels need K <= 32767 (K=%d)", K_);
     LSEG_HIP_TRY(hipSetDevice(device));
+    labels_only_ = false;
     if (train_mode) {                    // net.train(): activations saved for lseg_backward, BatchNorm on batch statistics
+        if (label_out) return set_error(LSEG_ERR_UNSUPPORTED, "label output is an inference feature (train mode is on)");
         if (argmax_out) return set_error(LSEG_ERR_UNSUPPORTED, "argmax output is an inference feature (train mode is on)");
         return forward_train(x_in, B, logits, st);
     }
@@ -1068,6 +1072,18 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         LSEG_HIP_TRY(hipMemcpyAsync(ovf_host_, ovf_dev_, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         LSEG_HIP_TRY(hipEventRecord(ev_ovf_, st));
         ovf_pending_ = true;
+        // masks only, any K: the labels stream past a running (best, arg) pair per output pixel (corr_argmax.hip) -- no (2h, 2w) logits, no
+        // full-resolution planes.  The scale plane must be the logits path's bit for bit, so the gram comes from where it comes there: for
+        // K <= 157 from corr_planes_kernel (which also writes its quarter-resolution planes into rpl_, 8.9 MB per image at K = 150, that
+        // nothing reads here: the two grams differ in the last bits and the score would no longer equal logits.max), above from pixel_gram
+        if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
+            // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
+            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, label_out, score_out, B, K_, lh_[0], lw_[0], c.out_c, st, low_,
+                                   (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
+            labels_only_ = true; last_low_ = nullptr; last_kout_ = K_;
+            prof_end(PF_FWD, fwd0, 0.0, st);
+            return 0;
+        }
         if (corr_fused) {
         } else if (group_k > 0) {
             // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [k, out_c] x [out_c, hp*wp]
@@ -1151,6 +1167,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     last_low_ = low; last_kout_ = Kout;
     if (argmax_out && Kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", Kout);
     if (argmax_out) TRY(launch_seg_stats_ex(low, nullptr, B, Kout, 4 * hw1, -1, nullptr, nullptr, argmax_out, 1, h1, w1, st));
+    if (label_out) TRY(launch_seg_argmax16(low, B, Kout, h1, w1, label_out, score_out, st));      // the int16 form, on the planes in memory
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
     if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
     prof_end(PF_FWD, fwd0, 0.0, st);
@@ -1167,6 +1184,7 @@ int Engine::materialize_low(hipStream_t st) {
 // pixAcc / IoU counts and the cross-entropy sum of the LAST forward's output against a target mask, from the low-resolution logits
 // through the x2 bilinear on the fly (lsegmentation_module.py:49-50,59-60,72: the metric / loss step after the path)
 int Engine::forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st) {
+    if (labels_only_) return set_error(LSEG_ERR_STATE, "the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
     if (!last_low_ || last_B_ < 1) return set_error(LSEG_ERR_STATE, "no forward has run");
     if (!target || !counts || !nll) return set_error(LSEG_ERR_INVALID, "forward_stats: NULL pointer");
     LSEG_HIP_TRY(hipSetDevice(device));
@@ -1214,6 +1232,7 @@ int Engine::get_intermediate(const char* name, float* out, size_t cap, size_t* n
         if (cap < need_n) return set_error(LSEG_ERR_INVALID, "buffer too small: %zu < %zu", cap, need_n);
         TRY(launch_rows_to_nchw_f32(feat_, out, B, hw1, cfg.out_c, st));
     } else if (!strcmp(name, "lowres")) {
+        if (labels_only_) return set_error(LSEG_ERR_STATE, "'lowres': the last forward was a labels-only forward (lseg_forward_labels streamed the masks)");
         TRY(materialize_low(st));
         const int hw1 = 4 * lh_[0] * lw_[0];
         need_n = (size_t)B * (group_k > 0 ? group_k : K_) * hw1;

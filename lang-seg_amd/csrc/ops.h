@@ -103,6 +103,14 @@ int launch_upsample_ce_backward_planes(const float* low, const int64_t* target, 
                                        int B, int K, int H, int W, int ignore_index, hipStream_t st, const float* gscale = nullptr);
 int launch_seg_stats(const float* scores, const int64_t* target, int B, int K, int HW, int ignore_index,
                      unsigned long long* counts, double* nll, hipStream_t st);
+// corr_argmax.hip -- masks for any K <= 32767.  The streamed kernel: g padded NHWC fp16 [B, H+2, W+2, 512], T fp16 [K, 512], scale fp32
+// [B, 2H, 2W] (launch_norm_scale_plane) -> label int16 / score fp32 (optional) [B, 4H, 4W], no label planes in memory
+bool corr_argmax_supported(int K, int C);
+void corr_argmax_geometry(int* out8);
+int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
+                       hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);   // ws: label-split planes, 6 B x B x 16 H W each (optional)
+// the int16 form of launch_seg_stats_ex's mask output (up = 1, no target): low fp32 [B, K, h, w] -> label / score (optional) [B, 2h, 2w]
+int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st);
 
 // ---- split-precision ("strict") mode (strict.hip): 16-bit tensors as (hi, lo) fp16 planes `plane` elements apart --------------
 int launch_convert_split(const void* in, int in_dtype, void* out, size_t n, size_t plane, hipStream_t st);

@@ -59,6 +59,7 @@ SIGNATURES = {
     "lseg_set_text_grouping": (_i, [_vp, _i]),
     "lseg_overflow_seen": (_i, [_vp, _i]),
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_stats": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_get_intermediate": (_i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
     "lseg_set_debug": (_i, [_vp, _i]),
@@ -79,6 +80,8 @@ SIGNATURES = {
     "lseg_set_bucket_callback": (_i, [_vp, _vp, _vp]),
     "lseg_sgd_step": (_i, [_vp, _f, _f, _f, _f, _vp]),
     "lseg_op_corr_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_corr_argmax_geometry": (_i, [_vp]),
+    "lseg_op_corr_argmax": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_vit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_res32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -176,16 +176,36 @@ class HipEngine:
         _lib.check(self.lib.lseg_set_text_cache(self._h, int(enabled)))
 
     # ---- forward -----------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):
+    def _check_input(self, x: torch.Tensor):
         if x.device != self.device or x.dtype != torch.float32:
             raise ValueError(f"x must be float32 on {self.device}, got {x.dtype} on {x.device}")
         x = x.contiguous()
         B, Cc, H, W = x.shape
         if (Cc, H, W) != (3, self.img_h, self.img_w):
             raise ValueError(f"engine was planned for 3x{self.img_h}x{self.img_w}, got {Cc}x{H}x{W}")
-        Kout = self._group if self._group > 0 else self._K
         if self._group > 0 and self._K != B * self._group:
             raise ValueError(f"per-image label sets: {self._K} token rows != batch {B} x {self._group}")
+        return x
+
+    def forward_labels(self, x: torch.Tensor, want_score: bool = False):
+        """Masks for any K <= 32767 (lseg_forward_labels): int16 [B,H,W] = torch.max(logits, 1)[1] of the logits forward() would return,
+        without those logits -- and, with want_score, fp32 [B,H,W] = torch.max(logits, 1)[0]."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        lab = torch.empty((B, H, W), dtype=torch.int16, device=self.device)
+        score = torch.empty((B, H, W), dtype=torch.float32, device=self.device) if want_score else None
+        _lib.check(self.lib.lseg_forward_labels(
+            self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(lab.data_ptr()),
+            C.c_void_p(score.data_ptr()) if score is not None else None, C.c_void_p(_stream_ptr(self.device))))
+        self._raise_callback_error()
+        return (lab, score) if want_score else lab
+
+    def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):
+        x = self._check_input(x)
+        B, Cc, H, W = x.shape
+        Kout = self._group if self._group > 0 else self._K
+        if want_argmax and not want_logits and Kout > 256:
+            return self.forward_labels(x)                     # uint8 cannot hold the labels: the int16 masks (uint8 stays the K <= 256 form)
         logits = torch.empty((B, Kout, H, W), dtype=torch.float32, device=self.device) if want_logits else None
         amax = torch.empty((B, H, W), dtype=torch.uint8, device=self.device) if want_argmax else None      # the masks
         _lib.check(self.lib.lseg_forward(

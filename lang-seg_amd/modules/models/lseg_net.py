@@ -277,6 +277,29 @@ class LSeg(BaseModel):
         finally:
             self.train(was)
 
+    def predict_labels(self, x, labelset=""):
+        """torch.max(self.forward(x, labelset), 1)[1] (what lseg_app.py:350-355 and every caller of the reference do with the logits) as
+        torch.long [B,H,W], for any K <= 32767, without the [B,K,H,W] logits (lseg_forward_labels)."""
+        text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
+        if not x.is_cuda:
+            raise RuntimeError("LSegNet.predict_labels needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        B, _, H, W = x.shape
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                eng = self._engine(B, H, W, text.shape[0], x.device)
+                if eng.training:
+                    eng.set_train(False)
+                self._set_tokens(eng, text, labelset)
+                self._last_engine = eng
+                lab = eng.forward_labels(x.float())
+                if self._range_guard(eng, x.device):
+                    return self.predict_labels(x, labelset)         # fell back to bf16: run again on a bf16 engine
+                return lab.long()
+        finally:
+            self.train(was)
+
     # ---- training step plumbing (lsegmentation_module.py:66-81 + what Lightning's DDP does around it) -----------------------------
     def _train_engine(self, B, H, W, K, device):
         import torch.distributed as dist
