@@ -507,7 +507,25 @@ int lseg_op_head_block_backward(const float* d_in, const float* d_out_saved, con
  *                          re-packs the MFMA operand copies.
  *   lseg_sgd_momentum      device pointer of a parameter's momentum buffer (torch.optim.SGD's state['momentum_buffer'], what
  *                          Lightning checkpoints under 'optimizer_states'); lseg_sgd_mark_initialized(h, 1) after restoring them makes
- *                          the next step a regular one (the first step of SGD copies the gradient into the buffer instead). */
+ *                          the next step a regular one (the first step of SGD copies the gradient into the buffer instead).
+ *   lseg_adam_step         replaces torch.optim.Adam(params_list, lr=base_lr, betas=(0.9, 0.999), weight_decay=...) of the --midasproto
+ *                          protocol (modules/lsegmentation_module.py:152-163, modules/lsegmentation_module_zs.py:270-281), amsgrad and
+ *                          maximize off: g += wd*w; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;
+ *                          w -= lr / (1-b1^step) * m / (sqrt(v) / sqrt(1-b2^step) + eps) on the bound fp32 parameters in one launch that
+ *                          also writes the same-layout MFMA operand copies, then the partial re-pack of lseg_sgd_step.  `step` is the
+ *                          count of THIS step (torch's state['step'] after it, >= 1); the hyper-parameters are doubles because torch
+ *                          derives the bias corrections from Python floats.  A group at lr 0 still moves m and v; w is not written.
+ *   lseg_adam_state        device pointer of a parameter's exp_avg (which = 0) / exp_avg_sq (which = 1), torch.optim.Adam's state under
+ *                          those names; both start at zero.  Mirrors lseg_sgd_momentum.
+ *   lseg_set_frozen_encoder  replaces the `pretrained.model` group at lr = 0 of use_pretrained='clip_fixed'
+ *                          (modules/lsegmentation_module_zs.py:220-235), which still pays the whole ViT backward: with it enabled
+ *                          pretrained.model.* is not trainable -- lseg_grad_bucket returns -1 for it, it gets no gradient buffer and
+ *                          no optimizer state, lseg_sgd_step / lseg_adam_step skip it -- and lseg_backward* stops after the four
+ *                          ProjectReadouts' own gradients (no timm Block, attention or embedding backward).  Every bucket callback still
+ *                          fires once, in order; pretrained.act_postprocess* take lr_pretrained, scratch.* lr_scratch.  The train-mode
+ *                          forward computes the same logits, bit for bit, and keeps one block's activations instead of `depth`.
+ *                          Legal only before the first lseg_set_train(h, 1) (afterwards LSEG_ERR_STATE); LSEG_ERR_UNSUPPORTED on the
+ *                          ResNet-101 tower. */
 typedef void (*lseg_reduce_cb)(void* user, void* dev_ptr, int64_t n_floats, void* stream);
 typedef void (*lseg_bucket_cb)(void* user, int bucket, void* stream);
 int lseg_set_train(lseg_handle h, int enabled);
@@ -524,6 +542,10 @@ int lseg_sgd_mark_initialized(lseg_handle h, int initialized);
 int lseg_set_bn_sync(lseg_handle h, lseg_reduce_cb fn, void* user, int world_size);
 int lseg_set_bucket_callback(lseg_handle h, lseg_bucket_cb fn, void* user);
 int lseg_sgd_step(lseg_handle h, float lr_pretrained, float lr_scratch, float momentum, float weight_decay, void* stream);
+int lseg_adam_step(lseg_handle h, double lr_pretrained, double lr_scratch, double beta1, double beta2, double eps, double weight_decay,
+                   int64_t step, void* stream);
+int lseg_adam_state(lseg_handle h, const char* key, int which /* 0 = exp_avg, 1 = exp_avg_sq */, float** dev_out, size_t* n_elems);
+int lseg_set_frozen_encoder(lseg_handle h, int enabled);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,13 @@ int lseg_sgd_step(lseg_handle h, float lr_pretrained, float lr_scratch, float mo
     GUARD(h);
     return h->e->sgd_step(lr_pretrained, lr_scratch, momentum, weight_decay, (hipStream_t)stream);
 }
+int lseg_adam_step(lseg_handle h, double lr_pretrained, double lr_scratch, double beta1, double beta2, double eps, double weight_decay,
+                   int64_t step, void* stream) {
+    GUARD(h);
+    return h->e->adam_step(lr_pretrained, lr_scratch, beta1, beta2, eps, weight_decay, (long long)step, (hipStream_t)stream);
+}
+int lseg_adam_state(lseg_handle h, const char* key, int which, float** dev_out, size_t* n) { GUARD(h); return h->e->adam_state(key, which, dev_out, n); }
+int lseg_set_frozen_encoder(lseg_handle h, int enabled) { GUARD(h); return h->e->set_frozen_encoder(enabled != 0); }
 
 // ---- single operators -----------------------------------------------------------------------------------
 static int op_dt(int lseg_dt, int* out) {

@@ -2106,6 +2106,69 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdSeg* __restrict
     }
 }
 
+// torch.optim.Adam (amsgrad=False, maximize=False; the --midasproto optimizer of lsegmentation_module.py:152-163 and
+// lsegmentation_module_zs.py:270-281) as ONE launch over the same (parameter, 4096-element chunk) table as the SGD step:
+//   g += wd*w ; m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; w -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
+// and, in the same pass, the engine's same-layout copies of the parameter (16-bit MFMA operand and / or fp32 copy).  The bias corrections
+// arrive folded by the host (double): ss_* = lr / (1-b1^t) per learning-rate group, bc2s = sqrt(1-b2^t).  A group at lr == 0 still moves m and
+// v (torch does) and leaves w and its copies alone.  HBM-bound: 16 B read + 12 B written per parameter, + 2 B for the 16-bit copy.
+__device__ __forceinline__ float adam_one(float wi, float gi, float& m, float& v, float ss, float b1, float omb1, float b2, float omb2, float bc2s,
+                                          float eps, float wd) {
+    const float g = gi + wd * wi;
+    m = b1 * m + omb1 * g;
+    v = b2 * v + omb2 * g * g;
+    return wi - ss * (m / (sqrtf(v) / bc2s + eps));
+}
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamSeg* __restrict__ segs, int nseg, float ss_pre, float ss_scr, float b1, float omb1,
+                                                         float b2, float omb2, float bc2s, float eps, float wd, int dtype) {
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const AdamSeg sg = segs[lo];
+    const float ss = sg.scratch ? ss_scr : ss_pre;
+    const bool move = ss != 0.f;                    // uniform over the block
+    const size_t base = (size_t)(blockIdx.x - sg.blk0) * 4096;
+    if (sg.vec) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const size_t e = base + (size_t)it * 1024 + threadIdx.x * 4;
+            if (e + 4 <= sg.n) {
+                const float4 wi = *reinterpret_cast<const float4*>(sg.w + e), gi = *reinterpret_cast<const float4*>(sg.g + e);
+                float4 mi = *reinterpret_cast<const float4*>(sg.m + e), vi = *reinterpret_cast<const float4*>(sg.v + e);
+                float4 wn;
+                wn.x = adam_one(wi.x, gi.x, mi.x, vi.x, ss, b1, omb1, b2, omb2, bc2s, eps, wd);
+                wn.y = adam_one(wi.y, gi.y, mi.y, vi.y, ss, b1, omb1, b2, omb2, bc2s, eps, wd);
+                wn.z = adam_one(wi.z, gi.z, mi.z, vi.z, ss, b1, omb1, b2, omb2, bc2s, eps, wd);
+                wn.w = adam_one(wi.w, gi.w, mi.w, vi.w, ss, b1, omb1, b2, omb2, bc2s, eps, wd);
+                *reinterpret_cast<float4*>(sg.m + e) = mi;
+                *reinterpret_cast<float4*>(sg.v + e) = vi;
+                if (move) {
+                    *reinterpret_cast<float4*>(sg.w + e) = wn;
+                    if (sg.w32) *reinterpret_cast<float4*>(sg.w32 + e) = wn;
+                    if (sg.w16) *reinterpret_cast<uint2*>(sg.w16 + e) = make_uint2(pack2_dt(wn.x, wn.y, dtype), pack2_dt(wn.z, wn.w, dtype));
+                }
+            }
+        }
+        return;
+    }
+    for (int it = 0; it < 16; ++it) {
+        const size_t e = base + (size_t)it * 256 + threadIdx.x;
+        if (e < sg.n) {
+            float mi = sg.m[e], vi = sg.v[e];
+            const float wn = adam_one(sg.w[e], sg.g[e], mi, vi, ss, b1, omb1, b2, omb2, bc2s, eps, wd);
+            sg.m[e] = mi;
+            sg.v[e] = vi;
+            if (move) {
+                sg.w[e] = wn;
+                if (sg.w32) sg.w32[e] = wn;
+                if (sg.w16) store_from_f32(sg.w16, e, dtype, wn);
+            }
+        }
+    }
+}
+
 // many small buffers zeroed in one launch (the atomically accumulated sums of a step: bias gradients, BatchNorm batch sums)
 __global__ __launch_bounds__(256) void zero_multi_kernel(const ZeroJob* __restrict__ jobs, int njobs) {
     const ZeroJob j = jobs[blockIdx.x];
@@ -2616,6 +2679,13 @@ int launch_sgd_multi(const SgdSeg* dev_segs, int nseg, unsigned blocks, float lr
                      hipStream_t st) {
     if (nseg < 1 || blocks < 1) return 0;
     hipLaunchKernelGGL(sgd_multi_kernel, dim3(blocks), dim3(256), 0, st, dev_segs, nseg, lr_pre, lr_scr, mu, wd, first, dtype);
+    CHECK_LAUNCH();
+    return 0;
+}
+int launch_adam_multi(const AdamSeg* dev_segs, int nseg, unsigned blocks, float ss_pre, float ss_scr, float b1, float omb1, float b2, float omb2,
+                      float bc2s, float eps, float wd, int dtype, hipStream_t st) {
+    if (nseg <= 0 || blocks == 0) return 0;
+    hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, st, dev_segs, nseg, ss_pre, ss_scr, b1, omb1, b2, omb2, bc2s, eps, wd, dtype);
     CHECK_LAUNCH();
     return 0;
 }

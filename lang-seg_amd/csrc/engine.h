@@ -83,6 +83,9 @@ public:
     int sgd_momentum(const char* key, float** out, size_t* n);
     int sgd_mark_initialized(bool on) { sgd_first_ = !on; return 0; }
     int sgd_step(float lr_pretrained, float lr_scratch, float momentum, float weight_decay, hipStream_t st);
+    int adam_step(double lr_pretrained, double lr_scratch, double beta1, double beta2, double eps, double weight_decay, long long step, hipStream_t st);
+    int adam_state(const char* key, int which, float** out, size_t* n);
+    int set_frozen_encoder(bool on);
     int n_buckets() const { return cfg.depth + 1; }
     int bucket_of(const std::string& key) const;
     lseg_reduce_fn bn_sync_fn = nullptr; void* bn_sync_user = nullptr; int bn_world = 1;
@@ -259,6 +262,19 @@ private:
     float* mom_flat_ = nullptr; size_t mom_flat_n_ = 0;
     TransposeJob* wt_table_ = nullptr; int wt_n_ = 0; unsigned wt_blocks_ = 0;
     int build_sgd_table();
+    // optimizer_segments: the walk both optimizer tables share -- one entry per trainable parameter with a gradient buffer, in key order
+    int optimizer_segments(std::vector<SgdSeg>& segs);
+    std::map<std::string, std::pair<size_t, size_t>> opt_off_;   // key -> {float offset in a flat state allocation, elements}: filled by the walk
+    int repack_after_step(hipStream_t st);
+    static bool is_encoder_key(const std::string& key) { return key.compare(0, 17, "pretrained.model.") == 0; }
+    // frozen encoder (lseg_set_frozen_encoder): pretrained.model.* is not trainable -- no gradient, no optimizer state, and the backward
+    // stops at the four readouts; the train-mode forward then keeps ONE block's activations instead of `depth`
+    bool frozen_ = false;
+    // fused Adam (torch.optim.Adam): exp_avg / exp_avg_sq of every trainable parameter in one flat allocation, [all m | all v]
+    AdamSeg* adam_table_ = nullptr; int adam_nseg_ = 0; unsigned adam_blocks_ = 0; bool adam_dirty_ = true;
+    float* adam_flat_ = nullptr; size_t adam_flat_n_ = 0;      // adam_flat_n_: padded floats of ONE moment
+    int build_adam_table();
+    void optimizer_dirty() { sgd_dirty_ = true; adam_dirty_ = true; }
     // small buffers that are accumulated into with atomics, zeroed by ONE launch per pass once their list is known (recorded during the
     // first pass, which still uses one memset each): [0] the forward's BatchNorm batch sums, [1] the backward's bias gradients
     struct ZeroSet { std::vector<ZeroJob> host; ZeroJob* dev = nullptr; int n = 0; bool ready = false; };

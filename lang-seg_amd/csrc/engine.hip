@@ -238,7 +238,7 @@ int Engine::bind(const char* key, const void* p, int dtype, const int64_t* shape
     b.shape.assign(shape, shape + ndim);
     bound_[key] = b;
     finalized_ = false;
-    sgd_dirty_ = true;
+    optimizer_dirty();
     return 0;
 }
 
@@ -420,7 +420,7 @@ int Engine::finalize(hipStream_t st) {
     char buf[256];
     const std::string vm = "pretrained.model.";
     if (resnet_) TRY(pack_resnet(st));
-    else {
+    else if (!(partial_pack_ && frozen_)) {      // (optimizer step on a frozen encoder: pretrained.model.* did not move)
         // ---- ViT --------------------------------------------------------------------------------------------
         TRY(pack_linear(vm + "patch_embed.proj.weight", vm + "patch_embed.proj.bias", D, 3 * P * P, img_dt_, patch_, st, true));
         TRY(pack_f32(vm + "cls_token", D, cls_, st));

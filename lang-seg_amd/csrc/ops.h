@@ -177,6 +177,16 @@ struct SgdSeg {
     int scratch;                             // learning-rate group: 0 = pretrained.*, 1 = scratch.*  (lsegmentation_module.py:119-127)
     int vec;                                 // every pointer 16-byte aligned (w16: 8) -> float4 path
 };
+struct AdamSeg {                              // SgdSeg with the two moment buffers of torch.optim.Adam (exp_avg, exp_avg_sq)
+    float* w; const float* g; float* m; float* v;
+    uint16_t* w16; float* w32;
+    unsigned long long n;
+    unsigned blk0;
+    int scratch;
+    int vec;
+};
+int launch_adam_multi(const AdamSeg* dev_segs, int nseg, unsigned blocks, float ss_pre, float ss_scr, float b1, float omb1, float b2, float omb2,
+                      float bc2s, float eps, float wd, int dtype, hipStream_t st);
 struct ZeroJob { float* p; unsigned n; };      // one block per job
 int launch_zero_multi(const ZeroJob* dev_jobs, int njobs, hipStream_t st);
 struct TransposeJob { const uint16_t* src; uint16_t* dst; int R, C; unsigned blk0; int tiles_r; };   // dst [C, R] = src [R, C]^T, R and C multiples of 8

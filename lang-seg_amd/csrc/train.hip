@@ -1,7 +1,10 @@
 // train.hip -- the training step of the LSeg path on one MI355X: train-mode forward (activations saved, BatchNorm on batch
 // statistics), backward of everything LSegmentationModule.training_step differentiates (modules/lsegmentation_module.py:66-81:
 // `out = self(img)`; `loss = criterion(out, target)`; autograd), gradients written straight into caller-provided fp32 buffers
-// laid out like the reference's parameters, per-bucket "gradients enqueued" notifications for the RCCL all-reduce, fused SGD.
+// laid out like the reference's parameters, per-bucket "gradients enqueued" notifications for the RCCL all-reduce, and the optimizer step
+// as one launch: fused SGD, or fused Adam for the reference's --midasproto protocol (lsegmentation_module.py:152-163).
+// With a frozen encoder (lseg_set_frozen_encoder; the reference's use_pretrained='clip_fixed' puts pretrained.model at lr 0,
+// lsegmentation_module_zs.py:220-235) the backward stops at the four ProjectReadouts: no timm Block, no embedding backward.
 //
 // What the reference's autograd would traverse and what runs here:
 //   output_conv x2 bilinear, CrossEntropyLoss(ignore_index)      seg_stats (through the bilinear) + upsample_ce_bwd_rows on the low-res logits
@@ -56,7 +59,16 @@ int Engine::set_train(bool on) {
     return 0;
 }
 
+int Engine::set_frozen_encoder(bool on) {
+    if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only: there is no encoder backward to skip");
+    if (train_alloc_) return set_error(LSEG_ERR_STATE, "lseg_set_frozen_encoder is legal only before lseg_set_train(h, 1)");
+    frozen_ = on;
+    optimizer_dirty();
+    return 0;
+}
+
 int Engine::bucket_of(const std::string& key) const {
+    if (frozen_ && is_encoder_key(key)) return -1;         // not trainable: the readouts and the reassemble keep their buckets
     // bucket 0: DPT head + reassemble (their gradients are complete first); bucket 1 + j: ViT block depth-1-j together with
     // the ProjectReadout hooked on it; the last bucket (block 0) also carries patch_embed / cls_token / pos_embed.
     const std::string bp = "pretrained.model.blocks.";
@@ -76,16 +88,17 @@ int Engine::bind_grad(const char* key, float* p) {
     if (!key || !p) return set_error(LSEG_ERR_INVALID, "bind_grad: NULL argument");
     auto it = bound_.find(key);
     if (it == bound_.end()) return set_error(LSEG_ERR_MISSING_PARAM, "bind_grad: parameter '%s' was never bound", key);
+    if (frozen_ && is_encoder_key(key)) return set_error(LSEG_ERR_INVALID, "bind_grad: '%s' is not trainable (frozen encoder)", key);
     GradSlot& s = grads_[key];
     s.ptr = p; s.n = it->second.numel(); s.bound = true;
-    sgd_dirty_ = true;
+    optimizer_dirty();
     zero_bwd_.ready = false; zero_bwd_.host.clear();
     return 0;
 }
 
 float* Engine::grad(const std::string& key, size_t n) {
     GradSlot& s = grads_[key];
-    if (!s.ptr) { s.ptr = (float*)dalloc(n * sizeof(float)); s.n = n; sgd_dirty_ = true; }
+    if (!s.ptr) { s.ptr = (float*)dalloc(n * sizeof(float)); s.n = n; optimizer_dirty(); }
     if (s.n != n) { set_error(LSEG_ERR_INVALID, "gradient of '%s' has %zu elements, expected %zu", key.c_str(), s.n, n); return nullptr; }
     return s.ptr;
 }
@@ -132,14 +145,24 @@ int Engine::train_alloc() {
     const lseg_config& c = cfg;
     const size_t B = c.max_batch, D = c.dim, F = c.features, M = B * ntok_, Mr = B * np_, H = c.heads;
     sv_.resize(c.depth);
-    for (int i = 0; i < c.depth; ++i) {
+    // frozen encoder: no block_backward reads the saved activations, so every block writes the same set (the block input ping-pongs:
+    // a block reads xin and writes the next one's); the kernels and their operands are the unfrozen forward's, the logits bit-identical
+    const int nsave = frozen_ ? 1 : c.depth;
+    for (int i = 0; i < nsave; ++i) {
         BlockSave& s = sv_[i];
         TALLOC(s.xin, float, M * D); TALLOC(s.xmid, float, M * D); TALLOC(s.lse, float, B * H * npad_);
         TALLOC(s.ln1, uint16_t, M * D); TALLOC(s.att, uint16_t, M * D); TALLOC(s.ln2, uint16_t, M * D);
         TALLOC(s.q, uint16_t, B * H * npad_ * 64); TALLOC(s.k, uint16_t, B * H * npad_ * 64); TALLOC(s.vt, uint16_t, B * H * 64 * npad_);
         TALLOC(s.pre, uint16_t, M * 4 * D); TALLOC(s.mlp, uint16_t, M * 4 * D);
     }
-    TALLOC(xlast_, float, M * D);
+    if (frozen_) {
+        float* xb;
+        TALLOC(xb, float, M * D);
+        for (int i = 1; i < c.depth; ++i) { sv_[i] = sv_[0]; if (i & 1) sv_[i].xin = xb; }
+        xlast_ = (c.depth & 1) ? xb : sv_[0].xin;
+    } else {
+        TALLOC(xlast_, float, M * D);
+    }
     size_t rows_max = B * 4 * lh_[0] * lw_[0] * F;               // largest row-major 16-bit temporary (d path_1 / d up_1)
     size_t wsa = 0, wsb = 0, wdw = 0;
     auto lin_need = [&](size_t m, size_t n, size_t k) { wsa = std::max(wsa, n * up64(m)); wsb = std::max(wsb, k * up64(m)); };
@@ -194,10 +217,12 @@ int Engine::train_alloc() {
         ws_det_n_ = (size_t)1 << 20;                 // gradients, BatchNorm batch sums forward / backward) instead of fp32 atomics
         TALLOC(ws_det_, float, ws_det_n_);
     }
-    TALLOC(gx_, float, M * D); TALLOC(dpos_, float, (size_t)ntok_ * D);
-    TALLOC(attn_ws_, char, attention_backward_ws_bytes((int)B, (int)H, npad_));
-    TALLOC(g16_, uint16_t, M * D); TALLOC(dmlp_, uint16_t, M * 4 * D); TALLOC(dln_, uint16_t, M * D); TALLOC(datt_, uint16_t, M * D);
-    TALLOC(dqkv_, uint16_t, M * 3 * D); TALLOC(dtok_, uint16_t, Mr * D);
+    if (!frozen_) {                                  // the block / embedding backward's own buffers
+        TALLOC(gx_, float, M * D); TALLOC(dpos_, float, (size_t)ntok_ * D);
+        TALLOC(attn_ws_, char, attention_backward_ws_bytes((int)B, (int)H, npad_));
+        TALLOC(g16_, uint16_t, M * D); TALLOC(dmlp_, uint16_t, M * 4 * D); TALLOC(dln_, uint16_t, M * D); TALLOC(datt_, uint16_t, M * D);
+        TALLOC(dqkv_, uint16_t, M * 3 * D); TALLOC(dtok_, uint16_t, Mr * D);
+    }
     const size_t hw1 = (size_t)4 * lh_[0] * lw_[0], Kp = up64(c.max_labels);
     TALLOC(lse_px_, float, B * 4 * hw1);
     TALLOC(drows_, uint16_t, B * hw1 * Kp); TALLOC(da_, uint16_t, B * hw1 * c.out_c); TALLOC(df_, uint16_t, B * hw1 * c.out_c);
@@ -227,9 +252,10 @@ int Engine::finalize_train(hipStream_t st) {
         if (!L.wd) TALLOC(L.wd, uint16_t, (size_t)co * 9 * ci);
         return launch_conv_dgrad_pack(L.w, L.wd, co, ci, st);
     };
-    for (auto& b : blocks_) { wts.push_back(&b.qkv); wts.push_back(&b.proj); wts.push_back(&b.fc1); wts.push_back(&b.fc2); }
+    if (!frozen_) for (auto& b : blocks_) { wts.push_back(&b.qkv); wts.push_back(&b.proj); wts.push_back(&b.fc1); wts.push_back(&b.fc2); }
     for (int l = 0; l < 4; ++l) {
-        wts.push_back(&readout_[l]); wts.push_back(&r1x1_[l]);
+        if (!frozen_) wts.push_back(&readout_[l]);       // (frozen encoder: the readout's dgrad never runs)
+        wts.push_back(&r1x1_[l]);
         if (c.resample_kind[l] == LSEG_RS_CONVT) wts.push_back(&rsmp_[l]);
         else if (c.resample_kind[l] == LSEG_RS_CONV_S2) TRY(make_wd(rsmp_[l], cp_[l], cp_[l]));
         TRY(make_wd(layer_rn_[l], F, cp_[l]));
@@ -702,7 +728,10 @@ int Engine::readout_backward(int l, int B, int acc, hipStream_t st) {
     char buf[96];
     snprintf(buf, sizeof(buf), "pretrained.act_postprocess%d.0.project.0.", l + 1);
     const std::string a = buf;
-    TRY(lin_bwd(v.dro, Mr, D, 2 * D, v.cat, readout_[l].wt, rowsA_, grad(a + "weight", (size_t)D * 2 * D), grad(a + "bias", D), acc, st));
+    // frozen encoder: the parameter gradients only -- d(block output) has no consumer
+    TRY(lin_bwd(v.dro, Mr, D, 2 * D, v.cat, readout_[l].wt, frozen_ ? nullptr : rowsA_, grad(a + "weight", (size_t)D * 2 * D), grad(a + "bias", D),
+                acc, st));
+    if (frozen_) return 0;
     TRY(launch_readout_cat_bwd(rowsA_, gx_, B, ntok_, D, img_dt_, st));
     g16_valid_ = false;
     return 0;
@@ -839,6 +868,16 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     for (int r = 1; r <= 4; ++r) TRY(refine_backward(r, B, acc, st));
     for (int l = 0; l < 4; ++l) TRY(reassemble_backward(l, B, acc, st));
     bucket_done(0, st);
+    if (frozen_) {
+        // ---- frozen encoder: the four readouts' own gradients, every bucket announced once in the usual order, nothing else ----------
+        for (int i = c.depth - 1; i >= 0; --i) {
+            for (int l = 0; l < 4; ++l)
+                if (c.hooks[l] == i) TRY(readout_backward(l, B, acc, st));
+            bucket_done(1 + (c.depth - 1 - i), st);
+        }
+        if (!acc) TRY(zero_end(zero_bwd_));
+        return 0;
+    }
     // ---- ViT blocks, readouts joining at their hooks --------------------------------------------------------------------------
     LSEG_HIP_TRY(hipMemsetAsync(gx_, 0, (size_t)M * D * sizeof(float), st));
     g16_valid_ = false;
@@ -868,16 +907,18 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     return 0;
 }
 
-// ---- fused SGD (torch.optim.SGD semantics; two learning-rate groups, lsegmentation_module.py:119-127,165-171) ------------------
-// One table entry per trainable parameter: fp32 master (the caller's tensor), gradient, momentum (one flat allocation) and the
-// engine's same-layout copies of it (`direct_`, noted by finalize()).
-int Engine::build_sgd_table() {
-    std::vector<SgdSeg> segs;
-    size_t mom = 0;
+// ---- the optimizer step (two learning-rate groups by key prefix, lsegmentation_module.py:119-127) ------------------------------------
+// One table entry per trainable parameter: fp32 master (the caller's tensor), gradient, optimizer state (one flat allocation) and the
+// engine's same-layout copies of it (`direct_`, noted by finalize()).  With a frozen encoder pretrained.model.* has no entry.
+int Engine::optimizer_segments(std::vector<SgdSeg>& segs) {
+    segs.clear();
+    opt_off_.clear();
+    size_t off = 0;
     for (auto& kv : grads_) {
         const std::string& key = kv.first;
         auto it = bound_.find(key);
         if (it == bound_.end() || it->second.dtype != LSEG_F32 || !kv.second.ptr) continue;
+        if (frozen_ && is_encoder_key(key)) continue;
         int scr;
         if (key.compare(0, 11, "pretrained.") == 0) scr = 0;
         else if (key.compare(0, 8, "scratch.") == 0) scr = 1;
@@ -888,10 +929,20 @@ int Engine::build_sgd_table() {
         s.n = kv.second.n; s.blk0 = 0; s.scratch = scr; s.vec = 0;
         auto d = direct_.find(key);
         if (d != direct_.end() && !d->second.conflict) { s.w16 = d->second.w16; s.w32 = d->second.w32; }
-        mom += (s.n + 3) / 4 * 4;
         segs.push_back(s);
+        opt_off_[key] = std::make_pair(off, (size_t)s.n);          // offset of the parameter in a flat state allocation (both optimizers)
+        off += (s.n + 3) / 4 * 4;
         sgd_keys_[key] = 1;
     }
+    return 0;
+}
+
+// ---- fused SGD (torch.optim.SGD semantics, lsegmentation_module.py:165-171) -------------------------------------------------------------
+int Engine::build_sgd_table() {
+    std::vector<SgdSeg> segs;
+    TRY(optimizer_segments(segs));
+    size_t mom = 0;
+    for (auto& s : segs) mom += (s.n + 3) / 4 * 4;
     if (mom > mom_flat_n_) {
         if (!sgd_first_) return set_error(LSEG_ERR_STATE, "the set of trainable parameters grew after the first optimizer step");
         mom_flat_ = (float*)dalloc(mom * sizeof(float));
@@ -922,15 +973,18 @@ int Engine::build_sgd_table() {
 // the momentum buffer of a trainable parameter (torch.optim.SGD's state['momentum_buffer']): checkpoint / resume, engine rebuilds
 int Engine::sgd_momentum(const char* key, float** out, size_t* n) {
     if (sgd_dirty_) TRY(build_sgd_table());
-    size_t off = 0;
-    for (auto& kv : grads_) {          // same walk as build_sgd_table
-        auto it = bound_.find(kv.first);
-        if (it == bound_.end() || it->second.dtype != LSEG_F32 || !kv.second.ptr) continue;
-        if (kv.first.compare(0, 11, "pretrained.") != 0 && kv.first.compare(0, 8, "scratch.") != 0) continue;
-        if (kv.first == key) { if (out) *out = mom_flat_ + off; if (n) *n = kv.second.n; return 0; }
-        off += (kv.second.n + 3) / 4 * 4;
-    }
+    auto it = opt_off_.find(key ? key : "");
+    if (it != opt_off_.end()) { if (out) *out = mom_flat_ + it->second.first; if (n) *n = it->second.second; return 0; }
     return set_error(LSEG_ERR_MISSING_PARAM, "no momentum buffer for '%s'", key ? key : "");
+}
+
+// refresh the packs with a real re-layout (padded / tap-major / transposed / flipped copies) from the updated masters; the straight
+// copies were written by the optimizer kernel, the frozen text tower and the eval-only packs are left alone
+int Engine::repack_after_step(hipStream_t st) {
+    partial_pack_ = true;
+    const int r = finalize(st);
+    partial_pack_ = false;
+    return r;
 }
 
 int Engine::sgd_step(float lr_pre, float lr_scr, float mu, float wd, hipStream_t st) {
@@ -939,12 +993,68 @@ int Engine::sgd_step(float lr_pre, float lr_scr, float mu, float wd, hipStream_t
     if (sgd_dirty_) TRY(build_sgd_table());
     TRY(launch_sgd_multi(sgd_table_, sgd_nseg_, sgd_blocks_, lr_pre, lr_scr, mu, wd, sgd_first_ ? 1 : 0, img_dt_, st));
     sgd_first_ = false;
-    // refresh the packs with a real re-layout (padded / tap-major / transposed / flipped copies) from the updated masters; the straight
-    // copies were written by the optimizer kernel, the frozen text tower and the eval-only packs are left alone
-    partial_pack_ = true;
-    const int r = finalize(st);
-    partial_pack_ = false;
-    return r;
+    return repack_after_step(st);
+}
+
+// ---- fused Adam (torch.optim.Adam semantics, amsgrad / maximize off; lsegmentation_module.py:152-163, lsegmentation_module_zs.py:270-281) --
+// exp_avg and exp_avg_sq start at zero (torch creates them with zeros_like), so there is no "first step" form: the step count alone
+// carries the bias correction, and it is the caller's (torch keeps it in state['step']).
+int Engine::build_adam_table() {
+    std::vector<SgdSeg> base;
+    TRY(optimizer_segments(base));
+    size_t tot = 0;
+    for (auto& s : base) tot += (s.n + 3) / 4 * 4;
+    if (tot > adam_flat_n_) {
+        if (adam_flat_) return set_error(LSEG_ERR_STATE, "the set of trainable parameters grew after the Adam state was created");
+        adam_flat_ = (float*)dalloc(2 * tot * sizeof(float));           // zeroed
+        if (!adam_flat_) return set_error(LSEG_ERR_HIP, "out of device memory (Adam state)");
+        adam_flat_n_ = tot;
+    }
+    std::vector<AdamSeg> segs(base.size());
+    size_t off = 0;
+    unsigned blk = 0;
+    for (size_t i = 0; i < base.size(); ++i) {
+        AdamSeg& s = segs[i];
+        s.w = base[i].w; s.g = base[i].g; s.w16 = base[i].w16; s.w32 = base[i].w32; s.n = base[i].n; s.scratch = base[i].scratch;
+        s.m = adam_flat_ + off;
+        s.v = adam_flat_ + adam_flat_n_ + off;
+        off += (s.n + 3) / 4 * 4;
+        s.blk0 = blk;
+        blk += (unsigned)((s.n + 4095) / 4096);
+        const uintptr_t a = (uintptr_t)s.w | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v | (uintptr_t)s.w32;
+        s.vec = !(a & 15) && !((uintptr_t)s.w16 & 7) && !(s.n & 3);
+    }
+    if (adam_table_ && (int)segs.size() > adam_nseg_) adam_table_ = nullptr;
+    if (!adam_table_ && !segs.empty()) {
+        adam_table_ = (AdamSeg*)dalloc(segs.size() * sizeof(AdamSeg));
+        if (!adam_table_) return set_error(LSEG_ERR_HIP, "out of device memory (optimizer table)");
+    }
+    if (!segs.empty()) LSEG_HIP_TRY(hipMemcpy(adam_table_, segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice));
+    adam_nseg_ = (int)segs.size(); adam_blocks_ = blk;
+    adam_dirty_ = false;
+    return 0;
+}
+
+// exp_avg (which = 0) / exp_avg_sq (which = 1) of a trainable parameter: torch.optim.Adam's state, for checkpoints and path changes
+int Engine::adam_state(const char* key, int which, float** out, size_t* n) {
+    if (which != 0 && which != 1) return set_error(LSEG_ERR_INVALID, "lseg_adam_state: which = %d (0 = exp_avg, 1 = exp_avg_sq)", which);
+    if (adam_dirty_) TRY(build_adam_table());
+    auto it = opt_off_.find(key ? key : "");
+    if (it != opt_off_.end()) { if (out) *out = adam_flat_ + (which ? adam_flat_n_ : 0) + it->second.first; if (n) *n = it->second.second; return 0; }
+    return set_error(LSEG_ERR_MISSING_PARAM, "no Adam state for '%s'", key ? key : "");
+}
+
+int Engine::adam_step(double lr_pre, double lr_scr, double b1, double b2, double eps, double wd, long long step, hipStream_t st) {
+    LSEG_HIP_TRY(hipSetDevice(device));
+    if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised");
+    if (step < 1) return set_error(LSEG_ERR_INVALID, "lseg_adam_step: step %lld (the count of this step, >= 1)", step);
+    if (!(b1 >= 0 && b1 < 1 && b2 >= 0 && b2 < 1 && eps >= 0)) return set_error(LSEG_ERR_INVALID, "lseg_adam_step: betas in [0, 1), eps >= 0");
+    if (adam_dirty_) TRY(build_adam_table());
+    // the bias corrections in double, as torch's Python scalars: step_size = lr / (1 - b1^t), sqrt(1 - b2^t)
+    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2s = std::sqrt(1.0 - std::pow(b2, (double)step));
+    TRY(launch_adam_multi(adam_table_, adam_nseg_, adam_blocks_, (float)(lr_pre / bc1), (float)(lr_scr / bc1), (float)b1, (float)(1.0 - b1), (float)b2,
+                          (float)(1.0 - b2), (float)bc2s, (float)eps, (float)wd, img_dt_, st));
+    return repack_after_step(st);
 }
 
 }  // namespace lseg

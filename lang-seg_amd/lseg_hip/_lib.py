@@ -79,6 +79,9 @@ SIGNATURES = {
     "lseg_set_bn_sync": (_i, [_vp, _vp, _vp, _i]),
     "lseg_set_bucket_callback": (_i, [_vp, _vp, _vp]),
     "lseg_sgd_step": (_i, [_vp, _f, _f, _f, _f, _vp]),
+    "lseg_adam_step": (_i, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
+    "lseg_adam_state": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+    "lseg_set_frozen_encoder": (_i, [_vp, _i]),
     "lseg_op_corr_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_corr_argmax_geometry": (_i, [_vp]),
     "lseg_op_corr_argmax": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),

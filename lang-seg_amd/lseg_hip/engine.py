@@ -106,6 +106,7 @@ class HipEngine:
         self.training = False
         self.image_dtype = image_dtype
         self.grads: Dict[str, torch.Tensor] = {}
+        self.frozen_encoder = False
         self._cb_error: Optional[BaseException] = None     # first exception raised inside a ctypes callback (ctypes would swallow it)
 
     def close(self):
@@ -232,9 +233,18 @@ class HipEngine:
                 keys.append((b, k))
         return [k for _, k in sorted(keys, key=lambda t: t[0])]
 
-    def enable_training(self, sd: Dict[str, torch.Tensor]):
+    def set_frozen_encoder(self, enabled: bool = True):
+        """pretrained.model.* stops being trainable (lseg_set_frozen_encoder): legal only before the first set_train(True)."""
+        _lib.check(self.lib.lseg_set_frozen_encoder(self._h, int(enabled)))
+        self.frozen_encoder = bool(enabled)
+
+    def enable_training(self, sd: Dict[str, torch.Tensor], freeze_encoder: bool = False):
         """net.train(): allocate the saved-activation workspace, and one FLAT fp32 gradient buffer per bucket (what the RCCL
-        all-reduce runs on, in place); every parameter's gradient is a view into its bucket, bound to the engine."""
+        all-reduce runs on, in place); every parameter's gradient is a view into its bucket, bound to the engine.
+        freeze_encoder: the clip_fixed setup (lsegmentation_module_zs.py:220-235) without its wasted work -- pretrained.model.* gets no
+        gradient (it is absent from `self.grads`), the backward stops at the four readouts, the optimizer steps skip it."""
+        if freeze_encoder:
+            self.set_frozen_encoder(True)
         _lib.check(self.lib.lseg_set_train(self._h, 1))
         nb = self.lib.lseg_num_grad_buckets(self._h)
         groups: List[List[str]] = [[] for _ in range(nb)]
@@ -337,6 +347,38 @@ class HipEngine:
         same tensors (other engines of an LSegNet) must be told (LSeg.invalidate_engines)."""
         _lib.check(self.lib.lseg_sgd_step(self._h, lr_pretrained, lr_scratch, momentum, weight_decay,
                                           C.c_void_p(_stream_ptr(self.device))))
+
+    # ---- fused Adam (torch.optim.Adam: state['exp_avg'], state['exp_avg_sq']; the step count stays with the caller) ----
+    def _adam_ptr(self, key: str, which: int):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        _lib.check(self.lib.lseg_adam_state(self._h, key.encode(), int(which), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def get_adam_state(self, key: str):
+        """(exp_avg, exp_avg_sq) of a trainable parameter, copies in the parameter's shape."""
+        out = []
+        for which in (0, 1):
+            ptr, n = self._adam_ptr(key, which)
+            t = torch.empty(n, dtype=torch.float32, device=self.device)
+            _HipMemcpy.copy(t.data_ptr(), ptr, 4 * n, _stream_ptr(self.device))
+            out.append(t.view(self.bound[key].shape))
+        return out[0], out[1]
+
+    def set_adam_state(self, key: str, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor):
+        for which, value in ((0, exp_avg), (1, exp_avg_sq)):
+            ptr, n = self._adam_ptr(key, which)
+            v = value.detach().to(self.device, torch.float32).contiguous()
+            if v.numel() != n:
+                raise ValueError(f"Adam state of '{key}' has {v.numel()} elements, expected {n}")
+            _HipMemcpy.copy(ptr, v.data_ptr(), 4 * n, _stream_ptr(self.device))
+            torch.cuda.current_stream(self.device).synchronize()   # v may be a temporary
+
+    def adam_step(self, lr_pretrained: float, lr_scratch: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8,
+                  weight_decay: float = 0.0):
+        """Fused torch.optim.Adam step (amsgrad / maximize off) on the bound fp32 masters + re-pack of the engine's operand copies;
+        `step` is the count of this step, starting at 1.  Writes the masters through raw pointers, like sgd_step."""
+        _lib.check(self.lib.lseg_adam_step(self._h, float(lr_pretrained), float(lr_scratch), float(betas[0]), float(betas[1]), float(eps),
+                                           float(weight_decay), int(step), C.c_void_p(_stream_ptr(self.device))))
 
     def _guarded(self, fn):
         def call(*a):

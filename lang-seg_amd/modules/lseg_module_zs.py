@@ -30,7 +30,8 @@ class LSegModuleZS(LSegmentationModuleZS):
             self.net = LSegNetZS(label_list=label_list, backbone=kwargs.get("backbone", "clip_vitl16_384"),
                                  features=kwargs.get("num_features", 256), aux=kwargs.get("aux", False),
                                  use_pretrained=use_pretrained, arch_option=kwargs.get("arch_option", 0),
-                                 block_depth=kwargs.get("block_depth", 0), activation=kwargs.get("activation", "lrelu"))
+                                 block_depth=kwargs.get("block_depth", 0), activation=kwargs.get("activation", "lrelu"),
+                                 freeze_encoder=self.skip_frozen_backward)
 
     def get_labels(self, dataset):                      # lseg_module_zs.py:60-71
         path = "label_files/fewshot_{}.txt".format(dataset)

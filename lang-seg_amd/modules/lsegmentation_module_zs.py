@@ -5,11 +5,16 @@ What is mirrored: the learning-rate rule (`base_lr / 16 * batch_size`, :43), `fi
 (:86-155: finetune 5-shot, finetune 1-shot, support + query) and `configure_optimizers` (:218-293: SGD momentum 0.9 + weight decay under
 the poly LambdaLR, the same parameter groups including the empty `auxlayer` one and the clip_fixed groups).
 
-The optimizer is EngineSGD (modules/lsegmentation_module.py): after an engine backward its step is the engine's fused lseg_sgd_step when
-the live groups are exactly {pretrained.*, scratch.*} -- the non-frozen layout, the empty `auxlayer` group counting as absent.  The
-clip_fixed layout (pretrained.model at lr 0, act_postprocess1..4 at base_lr, scratch at 10x) is not that shape and takes torch's own
-SGD step on the engine's gradients: lr 0 leaves pretrained.model.* bit-identical.  As in the reference, the ViT's gradients are still
-computed in that mode.
+The optimizer is EngineSGD, or EngineAdam with midasproto (modules/lsegmentation_module.py): after an engine backward its step is the
+engine's fused lseg_sgd_step / lseg_adam_step when the live groups are exactly {pretrained.*, scratch.*} -- the non-frozen layout, the
+empty `auxlayer` group counting as absent.  The clip_fixed layout (pretrained.model at lr 0, act_postprocess1..4 at base_lr, scratch at
+10x) is not that shape and by default takes torch's own step on the engine's gradients: lr 0 leaves pretrained.model.* bit-identical,
+and as in the reference the ViT's gradients are still computed.
+
+skip_frozen_backward=True (opt-in, only with use_pretrained == 'clip_fixed'): the network's training engines freeze the encoder
+(LSegNetZS(freeze_encoder=True) -> lseg_set_frozen_encoder) -- the backward stops at the four readouts, the same six groups come back
+from configure_optimizers, and the optimizer's fused step accepts them.  DIFFERENCE from the default path: the .grad of every
+pretrained.model.* parameter stays None (the default path fills it with gradients that the lr-0 group then ignores).
 
 Not mirrored (host-side data plumbing, SURVEY.md §8 out of scope): the few-shot FSSDataset loaders, Logger, AverageMeter, Evaluator and
 the few-shot IoU bookkeeping of training_step / validation_step.
@@ -17,7 +22,7 @@ the few-shot IoU bookkeeping of training_step / validation_step.
 import torch
 import torch.nn as nn
 
-from .lsegmentation_module import _Base, EngineSGD
+from .lsegmentation_module import _Base, EngineAdam, EngineSGD
 
 
 class LSegmentationModuleZS(_Base):
@@ -31,6 +36,8 @@ class LSegmentationModuleZS(_Base):
         self.other_kwargs = kwargs
         self.enabled = False                                  # AMP off (:47): the reference's GradScaler(enabled=False).scale is the identity
         self.fixed_encoder = kwargs.get("use_pretrained") in ["clip_fixed"]     # :50
+        # opt-in: do not compute the gradients the lr-0 group of clip_fixed discards (pretrained.model.*.grad stays None in this mode)
+        self.skip_frozen_backward = bool(kwargs.get("skip_frozen_backward", False)) and self.fixed_encoder
         self.cross_entropy_loss = nn.CrossEntropyLoss()       # :53 (ignore_index = -100, mean)
         self.nshot = kwargs.get("nshot", 1)
         self.finetune_mode = kwargs.get("finetune_mode", False)
@@ -100,8 +107,8 @@ class LSegmentationModuleZS(_Base):
             params_list.append({"params": net.scratch.parameters(), "lr": self.base_lr * 10})
         if hasattr(net, "auxlayer"):
             params_list.append({"params": net.auxlayer.parameters(), "lr": self.base_lr * 10})
-        if self.other_kwargs.get("midasproto", False):
-            opt = torch.optim.Adam(params_list, lr=self.base_lr, betas=(0.9, 0.999), weight_decay=self.other_kwargs.get("weight_decay", 1e-4))
+        if self.other_kwargs.get("midasproto", False):        # :270-281
+            opt = EngineAdam(params_list, net=net, lr=self.base_lr, betas=(0.9, 0.999), weight_decay=self.other_kwargs.get("weight_decay", 1e-4))
         else:
             opt = EngineSGD(params_list, net=net, lr=self.base_lr, momentum=0.9, weight_decay=self.other_kwargs.get("weight_decay", 1e-4))
         sch = torch.optim.lr_scheduler.LambdaLR(opt, lambda x: pow(1.0 - x / self.epochs, 0.9))

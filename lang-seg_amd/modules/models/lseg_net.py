@@ -67,13 +67,14 @@ def _make_fusion_block(features, use_bn):
 
 class _TrainState:
     """What one training engine carries across steps: the gradient exchange (when torch.distributed is up), the lazy zero_grad flag,
-    the number of fused optimizer steps (momentum lives in the engine), pending momentum to restore."""
+    the number of fused optimizer steps (momentum / the Adam moments live in the engine), pending momentum to restore."""
 
     def __init__(self):
         self.exchange = None
         self.lazy_zero = True            # no gradient values to add to yet: the next backward overwrites
         self.fresh = False               # the engine's buckets hold this step's (exchanged) gradients -> EngineSGD may use the fused step
         self.sgd_steps = 0
+        self.adam_steps = 0              # fused Adam steps whose exp_avg / exp_avg_sq live in the engine (torch's state['step'])
         self.sync_bn = False
 
 
@@ -180,6 +181,9 @@ class LSeg(BaseModel):
         self.sync_batchnorm = kwargs.get("sync_batchnorm", True)       # utils.py:34 (only matters when torch.distributed is initialised)
         self._native_epoch = 0                   # bumped whenever the engine wrote the masters / running statistics through raw pointers
         self._last_train_counts = None
+        # every training engine of this network is built with a frozen encoder (HipEngine.enable_training(freeze_encoder=True)):
+        # pretrained.model.* gets no gradient -- its .grad stays None -- and the backward stops at the four readouts
+        self.freeze_encoder = bool(kwargs.get("freeze_encoder", False))
 
     # ---- engine plumbing -----------------------------------------------------------------------
 
@@ -218,6 +222,9 @@ class LSeg(BaseModel):
                     if train and getattr(eng, "_ts", None) is not None and eng._ts.sgd_steps > 0:
                         # a bigger batch on a training engine: rebuild it, but the optimizer state moves over
                         carried = ({k: eng.get_momentum(k) for k in eng.grads}, eng._ts.sgd_steps)
+                        torch.cuda.current_stream(device).synchronize()
+                    elif train and getattr(eng, "_ts", None) is not None and eng._ts.adam_steps > 0:
+                        carried = ("adam", {k: eng.get_adam_state(k) for k in eng.grads}, eng._ts.adam_steps)
                         torch.cuda.current_stream(device).synchronize()
                     eng.close()
                 eng = HipEngine(self.cfg, H, W, max_batch=max(B, eng.max_batch if eng else 1),
@@ -307,7 +314,7 @@ class LSeg(BaseModel):
         eng = self._engine(B, H, W, K, device, train=True)
         if eng._ts is None:
             sd = self.state_dict()
-            eng.enable_training({k: v for k, v in sd.items()})
+            eng.enable_training({k: v for k, v in sd.items()}, freeze_encoder=bool(getattr(self, "freeze_encoder", False)))
             ts = _TrainState()
             world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
             if world > 1 and not self.autograd_grads:
@@ -324,7 +331,13 @@ class LSeg(BaseModel):
             eng._named = [(k, p) for k, p in self.named_parameters() if k in eng.grads]
             eng._nbt = [b for k, b in self.named_buffers() if k.endswith("num_batches_tracked") and k.startswith("scratch.")
                         and ".refinenet4.resConfUnit1." not in k]
-            if eng._carried is not None:
+            if eng._carried is not None and eng._carried[0] == "adam":
+                _, state, steps = eng._carried
+                for k, (m, v) in state.items():
+                    eng.set_adam_state(k, m, v)
+                ts.adam_steps = steps
+                eng._carried = None
+            elif eng._carried is not None:
                 mom, steps = eng._carried
                 for k, v in mom.items():
                     eng.set_momentum(k, v)

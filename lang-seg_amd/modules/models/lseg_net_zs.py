@@ -60,6 +60,7 @@ class LSeg(_LSegShared):
         self.sync_batchnorm = False
         self._native_epoch = 0
         self._last_train_counts = None
+        self.freeze_encoder = bool(kwargs.get("freeze_encoder", False))      # as LSegNet: training engines skip the encoder backward
 
     def forward(self, x, class_info):
         ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
