@@ -190,6 +190,18 @@ int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_l
  * of the criterion (:72).  dev_target int64 [B,img_h,img_w]; dev_counts / dev_nll as in lseg_op_seg_stats. */
 int lseg_forward_stats(lseg_handle h, const int64_t* dev_target, int ignore_index, int64_t* dev_counts, double* dev_nll, void* stream);
 
+/* The few-shot episode evaluation of the zero-shot networks on the LAST lseg_forward's output (csrc/episode.hip) -- replaces
+ * Evaluator.classify_prediction(out.argmax(1), target, ignore) (fewshot_data/common/evaluation.py:12-39), AverageMeter.update
+ * (fewshot_data/common/logger.py:29-34) and the value of the 2-class criterion (lsegmentation_module_zs.py:338-343) as
+ * test_lseg_zs.py:289-312 and LSegmentationModuleZS.training_step / validation_step (:100-143, :157-192) call them.  Reads the
+ * (img_h/2, img_w/2) logits wherever the forward left them (an inference forward or a train-mode one: the sources of lseg_forward_stats
+ * and lseg_train_loss) through output_conv's x2 bilinear on the fly; the workspace is the engine's own scratch.  Arguments and outputs
+ * as lseg_op_episode_stats.  LSEG_ERR_STATE after lseg_forward_labels or before any forward; LSEG_ERR_INVALID unless the last forward
+ * had exactly 2 labels per image (labels_per_image = 2, or one shared label set with K = 2). */
+int lseg_episode_stats(lseg_handle h, const int64_t* dev_target, const uint8_t* dev_ignore, int ignore_index, const int64_t* dev_class_id,
+                       int nclass, int64_t* dev_inter_buf, int64_t* dev_union_buf, int64_t* dev_areas, double* dev_nll, int64_t* dev_flags,
+                       void* stream);
+
 /* Intermediate taps for parity tests (names: "act1".."act4", "layer1".."layer4",
  * "rn1".."rn4", "path1".."path4", "image_features", "lowres").  Copies the tensor in the oracle's layout
  * ([B,N,D] / NCHW fp32) into dev_out; *n_elems gets the element count. */
@@ -328,6 +340,30 @@ int lseg_op_seg_stats(const float* d_scores, const int64_t* d_target, int B, int
  * are not touched); d_argmax uint8 [B,2h,2w] or NULL. */
 int lseg_op_seg_stats_lowres(const float* d_low, const int64_t* d_target, int B, int K, int h, int w, int ignore_index,
                              int64_t* d_counts, double* d_nll, uint8_t* d_argmax, void* stream);
+
+/* Few-shot episode statistics of 2-label scores, bare (csrc/episode.hip; the kernel behind lseg_episode_stats).
+ * replaces: Evaluator.classify_prediction (fewshot_data/common/evaluation.py:12-39: per image torch.histc x 3 and a host
+ *   synchronisation), AverageMeter.update's index_add_ (fewshot_data/common/logger.py:29-31) and nn.CrossEntropyLoss() on [B,2,H*W]
+ *   (lsegmentation_module_zs.py:338-343).
+ * d_scores fp32 [B,2,H,W] (up = 0), or the low-resolution logits [B,2,H/2,W/2] read through the x2 bilinear (align_corners=True) on the
+ *   fly (up = 1; H, W even and >= 4): bit-identical to lseg_op_upsample2x_planes of the same planes.
+ * d_target int64 [B,H,W]; d_ignore uint8 [B,H,W] or NULL.  Per pixel pred = (v1 > v0) (a tie is class 0, torch's first maximum).  Where
+ *   the ignore mask is set neither pred nor target counts; a target outside {0, 1} is in no area_gt and no intersection, pred still
+ *   counts there.  The cross-entropy is logsumexp(v0, v1) - v[target] over the pixels with target in {0, 1} and != ignore_index; the
+ *   ignore MASK does not enter it (the reference hands `target` to the criterion).
+ * d_areas int64 [B,6] per image {inter0, inter1, pred0, pred1, gt0, gt1} (union = pred + gt - inter), exact;
+ * d_nll double [B,2] per image {sum, pixels}: per-workgroup partials in d_ws folded in a fixed order -- two calls on the same input
+ *   give the same bits;
+ * d_flags int64 [2] = {pixels with ignore set and target != 0 (the reference asserts 0), pixels with a target outside {0, 1} that is
+ *   not ignore_index}.  d_areas, d_nll and d_flags are overwritten.
+ * Meter scatter (optional: d_class_id, d_inter_buf, d_union_buf all given or all NULL): d_class_id int64 [B], the int64 [2,nclass]
+ *   buffers get every image's inter / union ADDED to column d_class_id[b] (duplicates add up).  The caller validates the ids on the host
+ *   (it has them there: they picked the label pairs); the kernel skips an id outside [0, nclass) rather than write out of bounds.
+ * d_ws / ws_bytes: at least lseg_op_episode_stats_ws_bytes(B, H, W) bytes of device scratch, 8-byte aligned. */
+size_t lseg_op_episode_stats_ws_bytes(int B, int H, int W);
+int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const uint8_t* d_ignore, int B, int H, int W, int up,
+                          int ignore_index, const int64_t* d_class_id, int nclass, int64_t* d_inter_buf, int64_t* d_union_buf,
+                          int64_t* d_areas, double* d_nll, int64_t* d_flags, void* d_ws, size_t ws_bytes, void* stream);
 
 /* The pixel x text correlation on the engine's commuted schedule (DESIGN.md par. 3.4), one dedicated kernel (csrc/corr.hip).
  * replaces: `logits_per_image = self.logit_scale * image_features.half() @ text_features.t()` (modules/models/lseg_net.py:194) together

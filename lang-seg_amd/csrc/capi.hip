@@ -103,6 +103,14 @@ int lseg_forward_stats(lseg_handle h, const int64_t* dev_target, int ignore_inde
     return h->e->forward_stats(dev_target, ignore_index, dev_counts, dev_nll, (hipStream_t)stream);
 }
 
+int lseg_episode_stats(lseg_handle h, const int64_t* dev_target, const uint8_t* dev_ignore, int ignore_index, const int64_t* dev_class_id,
+                       int nclass, int64_t* dev_inter_buf, int64_t* dev_union_buf, int64_t* dev_areas, double* dev_nll, int64_t* dev_flags,
+                       void* stream) {
+    GUARD(h);
+    return h->e->episode_stats(dev_target, dev_ignore, ignore_index, dev_class_id, nclass, dev_inter_buf, dev_union_buf, dev_areas, dev_nll,
+                               dev_flags, (hipStream_t)stream);
+}
+
 int lseg_set_debug(lseg_handle h, int enabled) { GUARD(h); h->e->debug = enabled != 0; return LSEG_OK; }
 int lseg_get_intermediate(lseg_handle h, const char* name, float* dev_out, size_t cap, size_t* n, void* stream) {
     GUARD(h);
@@ -397,6 +405,16 @@ int lseg_op_head_features(const void* x_bf16, const void* w_bf16, const float* b
 int lseg_op_corr_argmax(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int B, int K, int H, int W,
                         int C, void* d_ws, size_t ws_bytes, void* stream) {
     return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, d_label, d_score, B, K, H, W, C, (hipStream_t)stream, d_ws, ws_bytes);
+}
+
+size_t lseg_op_episode_stats_ws_bytes(int B, int H, int W) { return episode_stats_ws_bytes(B, H, W); }
+int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const uint8_t* d_ignore, int B, int H, int W, int up,
+                          int ignore_index, const int64_t* d_class_id, int nclass, int64_t* d_inter_buf, int64_t* d_union_buf,
+                          int64_t* d_areas, double* d_nll, int64_t* d_flags, void* d_ws, size_t ws_bytes, void* stream) {
+    int r = require_device();
+    if (r) return r;
+    return launch_episode_stats(d_scores, d_target, d_ignore, B, H, W, up, ignore_index, d_class_id, nclass, d_inter_buf, d_union_buf, d_areas,
+                                d_nll, d_flags, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
 int lseg_op_corr_argmax_geometry(int* out8) {

@@ -63,6 +63,9 @@ public:
                 float* score_out = nullptr);
     int get_text_features(void* out_f16, hipStream_t st);
     int forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st);
+    // few-shot episode statistics of the last forward's 2 label planes (episode.hip), inference or train-mode forward alike
+    int episode_stats(const int64_t* target, const uint8_t* ignore, int ignore_index, const int64_t* class_id, int nclass, int64_t* inter_buf,
+                      int64_t* union_buf, int64_t* areas, double* nll, int64_t* flags, hipStream_t st);
     int get_intermediate(const char* name, float* out, size_t cap, size_t* n, hipStream_t st);
     int get_profile(const char* family, double* ms, int64_t* launches, double* flops);
     // 16-bit range check of the image tower (fp16 operands saturate at 65504): scans every 16-bit activation buffer of the plan

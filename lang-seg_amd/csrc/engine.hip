@@ -1194,6 +1194,29 @@ int Engine::forward_stats(const int64_t* target, int ignore_index, int64_t* coun
                                nll, nullptr, 1, h1, w1, st);
 }
 
+// Evaluator.classify_prediction + AverageMeter.update + the 2-class criterion on the LAST forward's output (episode.hip), from the
+// (2h, 2w) logits through the x2 bilinear on the fly: last_low_ after an inference forward, train_out_ after a train-mode one (the
+// sources of forward_stats / train_loss).  The workspace is the split-K slab buffer, idle between forwards.
+int Engine::episode_stats(const int64_t* target, const uint8_t* ignore, int ignore_index, const int64_t* class_id, int nclass, int64_t* inter_buf,
+                          int64_t* union_buf, int64_t* areas, double* nll, int64_t* flags, hipStream_t st) {
+    const float* low = nullptr;
+    int B = 0, kout = 0;
+    if (train_mode) {
+        if (!train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: no forward has run (train mode is on: it needs a train-mode lseg_forward)");
+        low = train_out_; B = train_B_; kout = train_G_ > 0 ? train_G_ : K_;
+    } else {
+        if (labels_only_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
+        if (!last_low_ || last_B_ < 1) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: no forward has run");
+        low = last_low_; B = last_B_; kout = last_kout_;
+    }
+    if (kout != 2) return set_error(LSEG_ERR_INVALID, "lseg_episode_stats: the last forward had %d labels per image, the episode evaluation needs exactly 2 (['others', class])", kout);
+    if (!target || !areas || !nll || !flags) return set_error(LSEG_ERR_INVALID, "lseg_episode_stats: NULL pointer");
+    LSEG_HIP_TRY(hipSetDevice(device));
+    if (!train_mode) TRY(materialize_low(st));
+    return launch_episode_stats(low, target, ignore, B, 4 * lh_[0], 4 * lw_[0], 1, ignore_index, class_id, nclass, inter_buf, union_buf, areas, nll,
+                                flags, ws_split_, ws_split_n_ * sizeof(float), st);
+}
+
 int Engine::get_text_features(void* out, hipStream_t st) {
     if (!text_valid) return set_error(LSEG_ERR_STATE, "text features not computed yet");
     LSEG_HIP_TRY(hipMemcpyAsync(out, tnorm_, (size_t)K_ * cfg.out_c * 2, hipMemcpyDeviceToDevice, st));

@@ -111,6 +111,13 @@ int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t
                        hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);   // ws: label-split planes, 6 B x B x 16 H W each (optional)
 // the int16 form of launch_seg_stats_ex's mask output (up = 1, no target): low fp32 [B, K, h, w] -> label / score (optional) [B, 2h, 2w]
 int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st);
+// episode.hip -- few-shot episode evaluation (Evaluator.classify_prediction + AverageMeter.update + the 2-class criterion): scores fp32
+// [B,2,H,W] (up = 0) or low-resolution logits [B,2,H/2,W/2] read through the x2 bilinear (up = 1), target int64 / ignore uint8 (or NULL)
+// [B,H,W] -> areas int64 [B,6], nll double [B,2], flags int64 [2], optional scatter into the meter's int64 [2,nclass] buffers
+size_t episode_stats_ws_bytes(int B, int H, int W);
+int launch_episode_stats(const float* scores, const int64_t* target, const uint8_t* ignore, int B, int H, int W, int up, int ignore_index,
+                         const int64_t* class_id, int nclass, int64_t* inter_buf, int64_t* union_buf, int64_t* areas, double* nll,
+                         int64_t* flags, void* ws, size_t ws_bytes, hipStream_t st);
 
 // ---- split-precision ("strict") mode (strict.hip): 16-bit tensors as (hi, lo) fp16 planes `plane` elements apart --------------
 int launch_convert_split(const void* in, int in_dtype, void* out, size_t n, size_t plane, hipStream_t st);

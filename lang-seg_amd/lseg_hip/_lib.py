@@ -61,6 +61,7 @@ SIGNATURES = {
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_stats": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "lseg_episode_stats": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_get_intermediate": (_i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
     "lseg_set_debug": (_i, [_vp, _i]),
     "lseg_set_profiling": (_i, [_vp, _i]),
@@ -105,6 +106,8 @@ SIGNATURES = {
     "lseg_op_head_features": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "lseg_op_seg_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lseg_op_seg_stats_lowres": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "lseg_op_episode_stats_ws_bytes": (_sz, [_i, _i, _i]),
+    "lseg_op_episode_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lseg_op_linear_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lseg_op_attention_backward_ws_bytes": (_sz, [_i, _i, _i]),
     "lseg_op_attention_backward_qkv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

@@ -415,6 +415,55 @@ class HipEngine:
         return {"correct": int(c[0]), "labeled": int(c[1]), "area_inter": inter, "area_pred": pred, "area_lab": lab,
                 "area_union": pred + lab - inter, "nll_sum": float(n[0]), "nll_count": int(n[1])}
 
+    def episode_stats(self, target: torch.Tensor, ignore: Optional[torch.Tensor] = None, ignore_index: int = -100, class_id=None,
+                      meter=None) -> dict:
+        """Few-shot episode evaluation of the last forward's two label planes (lseg_episode_stats; inference or train-mode forward):
+        Evaluator.classify_prediction(out.argmax(1), target, ignore) and the value of nn.CrossEntropyLoss() on `out`, per image, in one
+        pass over the low-resolution logits -- pair it with forward(x, want_logits=False).  Returns DEVICE tensors in the reference's
+        layout, no host synchronisation: area_inter / area_union int64 [2, B], nll_sum / nll_count float64 [B] (the criterion's value
+        is nll_sum.sum() / nll_count.sum()), flags int64 [2] = {pixels with ignore set and target != 0, pixels whose target is outside
+        {0, 1} and not ignore_index}, areas int64 [B, 6] = {inter0, inter1, pred0, pred1, gt0, gt1}.
+        target [B,H,W] (any integer / float dtype holding 0 / 1, as the loaders give it); ignore [B,H,W] or None (non-zero = ignored).
+        class_id + meter (lseg_hip.episode.EpisodeMeter): the same launch adds every image's inter / union into column class_id[b]
+        of the meter (AverageMeter.update).  class_id is validated HERE, on the host: hand over the list the caller already has
+        (net.forward reads class_info to pick the token pairs); a device tensor is read back, which synchronises."""
+        t = target.detach().to(self.device, torch.int64).contiguous()
+        if t.dim() != 3 or tuple(t.shape[1:]) != (self.img_h, self.img_w):
+            raise ValueError(f"target must be [B, {self.img_h}, {self.img_w}], got {tuple(t.shape)}")
+        B = t.shape[0]
+        ig = None
+        if ignore is not None:
+            ig = ignore.detach().to(self.device)
+            ig = (ig if ig.dtype == torch.uint8 else (ig != 0).to(torch.uint8)).contiguous()
+            if ig.shape != t.shape:
+                raise ValueError(f"ignore mask {tuple(ig.shape)} does not match the target {tuple(t.shape)}")
+        cid = ib = ub = None
+        nclass = 0
+        if meter is not None:
+            if class_id is None:
+                raise ValueError("episode_stats: a meter needs class_id")
+            ids = [int(c) for c in (class_id.tolist() if torch.is_tensor(class_id) else class_id)]
+            nclass = int(meter.nclass)
+            bad = [c for c in ids if not 0 <= c < nclass]
+            if len(ids) != B or bad:
+                raise _lib.LSegError(-1, f"episode_stats: class_id {ids} for a batch of {B}: every id must lie in [0, nclass={nclass})")
+            if meter.intersection_buf.device != self.device:
+                raise ValueError(f"the meter lives on {meter.intersection_buf.device}, the engine on {self.device}")
+            cid = torch.tensor(ids, dtype=torch.int64).to(self.device, non_blocking=True)
+            ib, ub = meter.intersection_buf, meter.union_buf
+        areas = torch.empty((B, 6), dtype=torch.int64, device=self.device)
+        nll = torch.empty((B, 2), dtype=torch.float64, device=self.device)
+        flags = torch.empty(2, dtype=torch.int64, device=self.device)
+        P = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        _lib.check(self.lib.lseg_episode_stats(self._h, P(t), P(ig), int(ignore_index), P(cid), nclass, P(ib), P(ub), P(areas), P(nll),
+                                               P(flags), C.c_void_p(_stream_ptr(self.device))))
+        inter = areas[:, 0:2]
+        out = {"area_inter": inter.t(), "area_union": (areas[:, 2:4] + areas[:, 4:6] - inter).t(), "nll_sum": nll[:, 0],
+               "nll_count": nll[:, 1], "flags": flags, "areas": areas}
+        if meter is not None:
+            meter.note_scatter(flags, (nll[:, 0].sum() / nll[:, 1].sum()).float())
+        return out
+
     # ---- taps / measurement ----------------------------------------------------------------------------
     def set_debug(self, enabled: bool):
         _lib.check(self.lib.lseg_set_debug(self._h, int(enabled)))

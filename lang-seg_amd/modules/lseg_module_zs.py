@@ -4,8 +4,9 @@
 (`LSegRNNetZS` for backbone="clip_resnet101")
 from `label_files/fewshot_<dataset>.txt` (get_labels, :60-71) and forwards `(x, class_info)` to it
 (lsegmentation_module_zs.py:82-83).  Criterion, training_step and configure_optimizers come from LSegmentationModuleZS
-(modules/lsegmentation_module_zs.py), as in the reference.  The few-shot episode loaders / Evaluator of lsegmentation_module_zs.py
-and fewshot_data/ are host-side data plumbing outside the hot path and are not mirrored (SURVEY.md §8 out of scope).
+(modules/lsegmentation_module_zs.py), as in the reference, and so do validation_step / validation_epoch_end (the few-shot episode
+evaluation on the device: lseg_hip.episode).  The few-shot episode LOADERS of fewshot_data/ are host-side data plumbing outside the hot
+path and are not mirrored (SURVEY.md §8 out of scope).
 """
 import os
 

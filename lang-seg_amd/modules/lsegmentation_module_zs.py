@@ -16,8 +16,17 @@ skip_frozen_backward=True (opt-in, only with use_pretrained == 'clip_fixed'): th
 from configure_optimizers, and the optimizer's fused step accepts them.  DIFFERENCE from the default path: the .grad of every
 pretrained.model.* parameter stays None (the default path fills it with gradients that the lr-0 group then ignores).
 
-Not mirrored (host-side data plumbing, SURVEY.md §8 out of scope): the few-shot FSSDataset loaders, Logger, AverageMeter, Evaluator and
-the few-shot IoU bookkeeping of training_step / validation_step.
+The few-shot episode evaluation (:100-143, :157-216): `validation_step` / `validation_epoch_end` and, when the module carries a
+`train_average_meter`, the IoU bookkeeping of `training_step` run on the device -- LSeg.evaluate_episode / HipEngine.episode_stats
+(csrc/episode.hip) in place of Evaluator.classify_prediction, lseg_hip.episode.EpisodeMeter in place of AverageMeter.  The meters are
+attached by the caller (`module.val_average_meter = EpisodeMeter(benchmark, dataset.class_ids, device)`), who owns the dataset.
+Three differences from the reference: the meter keeps exact int64 areas (the reference's float32 buffers stop being exact above 2^24
+pixels per class); the reference's `assert` on ignored-and-labelled pixels is a ValueError raised by compute_iou() in
+validation_epoch_end (no per-batch synchronisation); validation_epoch_end carries neither the reference's `exit()` after epoch 3
+(:204-216) nor its tensorboard writer.
+
+Not mirrored (host-side data plumbing, SURVEY.md §8 out of scope): the few-shot FSSDataset loaders, Logger (write_process /
+write_result) and visualisation.
 """
 import torch
 import torch.nn as nn
@@ -85,7 +94,8 @@ class LSegmentationModuleZS(_Base):
     def training_step(self, batch, batch_nb):                 # :86-155 (loss part)
         img, target, class_info = self.batch_inputs(batch)
         ignore = self._fused_ignore_index()
-        if ignore is not None and hasattr(self.net, "forward_loss") and not self.other_kwargs.get("materialize_logits", False):
+        fused = ignore is not None and hasattr(self.net, "forward_loss") and not self.other_kwargs.get("materialize_logits", False)
+        if fused:
             # `out = self(img, class_info); loss = self.criterion(out, target)` as ONE autograd node on the engine (no [B, 2, H, W] logits)
             t = target.reshape(img.shape[0], img.shape[2], img.shape[3]).long()
             loss = self.net.forward_loss(img, class_info, t, ignore_index=ignore)
@@ -93,7 +103,78 @@ class LSegmentationModuleZS(_Base):
             out = self(img, class_info)
             loss = self.criterion(out, target)
         self.log("train_loss", loss)
+        meter = getattr(self, "train_average_meter", None)
+        if meter is not None:                                 # :100-137: Evaluator.classify_prediction + AverageMeter.update, on the device
+            self._train_meter_update(meter, batch, img, target, class_info, loss, fused)
         return loss
+
+    def _train_meter_update(self, meter, batch, img, target, class_info, loss, fused):
+        """The IoU bookkeeping of training_step on the train-mode forward's own logits (lseg_episode_stats after forward_loss: the
+        engine still holds them).  Needs the fused step; with materialize_logits or a custom criterion it raises."""
+        B, H, W = img.shape[0], img.shape[2], img.shape[3]
+        ignore = self.train_ignore_mask(batch)
+        ids = [int(c) for c in class_info.tolist()]
+        eng = getattr(self.net, "_last_train_engine", None) if fused else None
+        if eng is None:
+            raise RuntimeError("train_average_meter needs the fused training step (net.forward_loss): detach the meter or drop materialize_logits")
+        eng.episode_stats(target.reshape(B, H, W), None if ignore is None else ignore.reshape(B, H, W), ignore_index=self._fused_ignore_index(),
+                          class_id=ids, meter=meter)
+        meter.loss_buf[-1] = loss.detach().clone()            # the reference stores the step's own loss (:137)
+
+    def train_ignore_mask(self, batch):
+        """The ignore mask of a training batch in batch_inputs' layout, or None: only for benchmark 'pascal' and when the batch
+        carries one (:101-102, :116-117, :132-133)."""
+        if self.dataset != "pascal":                          # self.args.benchmark = dataset (:60)
+            return None
+        if self.finetune_mode:
+            ig = batch.get("support_ignore_idxs")
+            if ig is None:
+                return None
+            return ig.reshape(-1, ig.shape[-2], ig.shape[-1]) if self.nshot == 5 else ig.squeeze(1)
+        if batch.get("query_ignore_idx") is None:
+            return None
+        return torch.cat([batch["support_ignore_idxs"].squeeze(1), batch["query_ignore_idx"]], dim=0)
+
+    def validation_batch_inputs(self, batch):
+        """(img, target, class_info, ignore) of a validation batch, the reference's two layouts (:158-184): the 5-shot finetune
+        `view(-1, ...)` with class_id repeated shot-major, and the query layout.  ignore is None unless benchmark == 'pascal' and the
+        batch carries `query_ignore_idx` (:168, :180)."""
+        ig = batch.get("query_ignore_idx") if self.dataset == "pascal" else None      # self.args.benchmark = dataset (:60)
+        if self.finetune_mode and self.nshot == 5:            # :158-164
+            bshape = batch["query_img"].shape
+            img = batch["query_img"].view(-1, bshape[2], bshape[3], bshape[4])
+            target = batch["query_mask"].view(-1, bshape[3], bshape[4])
+            class_info = batch["class_id"]
+            for _ in range(1, 5):
+                class_info = torch.cat([class_info, batch["class_id"]])
+            if ig is not None:
+                ig = ig.view(-1, bshape[3], bshape[4])
+        else:                                                 # :174-176
+            img = batch["query_img"].squeeze(1)
+            target = batch["query_mask"].squeeze(1)
+            class_info = batch["class_id"]
+            if ig is not None:
+                ig = ig.squeeze(1)
+        return img, target, class_info, ig
+
+    def validation_step(self, batch, batch_nb):               # :157-192
+        """out = self(img, class_info); val_loss = criterion(out, target); Evaluator.classify_prediction; val_average_meter.update --
+        one inference forward and one statistics launch on the device (LSeg.evaluate_episode).  Without the reference's
+        write_process logging (Logger is not mirrored)."""
+        meter = getattr(self, "val_average_meter", None)
+        if meter is None:
+            raise RuntimeError("validation_step needs `module.val_average_meter = lseg_hip.episode.EpisodeMeter(benchmark, dataset.class_ids, device)`")
+        img, target, class_info, ignore = self.validation_batch_inputs(batch)
+        _, _, val_loss = self.net.evaluate_episode(img, class_info, target, ignore=ignore, meter=meter)
+        return val_loss
+
+    def validation_epoch_end(self, outs):                     # :195-202 (no exit() after epoch 3, no tensorboard writer: :204-216)
+        meter = self.val_average_meter
+        val_loss = torch.stack(meter.loss_buf).mean() if meter.loss_buf else torch.zeros(())
+        val_miou, val_fb_iou = meter.compute_iou()            # raises ValueError on ignored-and-labelled pixels / targets outside {0, 1}
+        self.log("fewshot_val_loss", val_loss)
+        self.log("fewshot_val_miou", val_miou)
+        self.log("fewshot_val_fb_iou", val_fb_iou)
 
     def configure_optimizers(self):                           # :218-293
         net = self.net

@@ -82,6 +82,32 @@ class LSeg(_LSegShared):
             return self.forward(x, class_info)                                # fp16 overflowed: again on bf16 operands (loud)
         return out
 
+    def evaluate_episode(self, x, class_info, target, ignore=None, meter=None, want_logits=False):
+        """One few-shot evaluation step on the device -- `out = self(x, class_info)`, Evaluator.classify_prediction(out.argmax(1),
+        target, ignore), criterion(out, target) and, with a meter (lseg_hip.episode.EpisodeMeter), AverageMeter.update -- as
+        test_lseg_zs.py:289-312 / LSegmentationModuleZS.validation_step (:157-192) do it: an inference forward that keeps only the
+        low-resolution logits, then lseg_episode_stats.  Returns (area_inter int64 [2, B], area_union int64 [2, B], loss) -- loss a
+        0-dim fp32 device tensor = sum(nll_sum) / sum(nll_count), nn.CrossEntropyLoss()'s mean -- and, with want_logits, the
+        [B, 2, H, W] logits as a fourth item.  No host synchronisation beyond the range guard's (as in forward)."""
+        ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
+        if not x.is_cuda:
+            raise RuntimeError("LSegNetZS.evaluate_episode needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        B, _, H, W = x.shape
+        if len(ids) != B:
+            raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
+        text = torch.cat([self.texts[c] for c in ids], dim=0)
+        eng = self._engine(B, H, W, text.shape[0], x.device)
+        if eng.training:
+            eng.set_train(False)
+        self._set_group_tokens(eng, text, ids)
+        out = eng.forward(x.float(), want_logits=bool(want_logits))            # None without logits: only the low planes stay
+        if self._range_guard(eng, x.device):
+            return self.evaluate_episode(x, class_info, target, ignore, meter, want_logits)    # fp16 overflowed: again on bf16 operands
+        r = eng.episode_stats(target.reshape(B, H, W), None if ignore is None else ignore.reshape(B, H, W),
+                              ignore_index=-100, class_id=ids, meter=meter)
+        loss = (r["nll_sum"].sum() / r["nll_count"].sum()).float()
+        res = (r["area_inter"], r["area_union"], loss)
+        return res + (out,) if want_logits else res
 
     def _set_group_tokens(self, eng, text, ids):
         tkey = ("zs", tuple(ids))
@@ -114,6 +140,7 @@ class LSeg(_LSegShared):
         if not (self.training and torch.is_grad_enabled()):
             raise RuntimeError("forward_loss is the training-step path: call it under net.train() with grad enabled")
         eng, keys, params = self._train_inputs(x, class_info)
+        self._last_train_engine = eng                    # holds this step's train-mode logits: LSegmentationModuleZS's train_average_meter
         return _EngineLossFn.apply(x.float(), target, self, eng, keys, int(ignore_index), *params)
 
 
