@@ -1,5 +1,6 @@
 // engine.h -- the whole-forward plan of LSeg on one MI355X (owned buffers, packed weights).
 #pragma once
+#include <cmath>
 #include <map>
 #include <string>
 #include <vector>
@@ -19,6 +20,38 @@ struct BoundParam {
 // w: packed [n, k] MFMA operand; b: fp32 bias.  Train mode adds wt = w transposed [k, n] (dgrad GEMM operand) for Linears and
 // wd = the flipped / channel-swapped 3x3 weights (dgrad as a forward conv) for convs.
 struct Lin { uint16_t* w = nullptr; float* b = nullptr; int n = 0, k = 0; uint16_t* wt = nullptr; uint16_t* wd = nullptr; };
+
+// ---- GemmArgs builders: the one description of each GEMM shape the schedules (engine.hip, train.hip) launch.  A builder sets what its
+// shape needs and nothing else; whatever is particular to one call site follows the call as an explicit line.
+inline GemmArgs gemm_operands(const void* A, const Lin& w, int M) {       // A [M, w.k] against w [w.n, w.k], + w.b
+    GemmArgs g;
+    gemm_args_init(g);
+    g.A = (const uint16_t*)A; g.W = w.w; g.M = M; g.N = w.n; g.K = w.k; g.lda = w.k; g.ldw = w.k; g.bias = w.b;
+    return g;
+}
+// C [M, w.n] = A . w^T + w.b: nn.Linear, a 1x1 conv on pixel rows
+inline GemmArgs lin_args(const void* A, const Lin& w, int M, void* C, int out_dtype) {
+    GemmArgs g = gemm_operands(A, w, M);
+    g.C = C; g.out_dtype = out_dtype; g.ldc = w.n; g.map_mode = MAP_LINEAR;
+    return g;
+}
+inline void add_residual(GemmArgs& g, const void* res, int res_dtype) { g.res_mode = RES_DEST; g.res = res; g.res_dtype = res_dtype; }
+inline void to_padded(GemmArgs& g, int ho, int wo) { g.map_mode = MAP_PADDED; g.ho = ho; g.wo = wo; }     // rows = pixels of a padded NHWC map
+// the fused q/k/v Linear: q, k -> [b, head, t, 64], v -> [b, head, 64, t]
+inline GemmArgs qkv_args(const void* A, const Lin& w, int M, void* q, void* k, void* vt, int ntok, int npad, int heads, int out_dtype) {
+    GemmArgs g = gemm_operands(A, w, M);
+    g.out_dtype = out_dtype; g.map_mode = MAP_QKV;
+    g.C = q; g.Ck = k; g.Cv = vt; g.qkv_dim = w.k; g.qkv_ntok = ntok; g.qkv_npad = npad; g.qkv_heads = heads;
+    return g;
+}
+// ConvTranspose2d(k = s = stride) on the (ho, wo) grid as a GEMM with a pixel-shuffle scatter into the padded (ho*s, wo*s) map
+inline GemmArgs pixshuf_args(const void* A, const Lin& w, int M, void* C, int ch, int s, int ho, int wo, int out_dtype) {
+    GemmArgs g = gemm_operands(A, w, M);
+    g.bias_mod = ch; g.C = C; g.out_dtype = out_dtype; g.ldc = ch;
+    g.map_mode = MAP_PIXSHUF; g.ho = ho; g.wo = wo; g.ps_s = s; g.ps_C = ch;
+    return g;
+}
+inline float logit_scale() { return expf(logf(1.0f / 0.07f)); }            // lseg_net.py:141
 
 struct VitBlock { float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; Lin qkv, proj, fc1, fc2; };
 struct TextBlock { float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; Lin qkv, out, fc, proj; };
@@ -41,6 +74,7 @@ struct BlockSave {
     float *xin = nullptr, *xmid = nullptr, *lse = nullptr;
     uint16_t *ln1 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *att = nullptr, *ln2 = nullptr, *pre = nullptr, *mlp = nullptr;
 };
+// buffers of one reassemble level (Engine::reassemble): train mode keeps one set per level, inference shares one (ropre NULL, no dro)
 struct LevelSave { uint16_t *cat = nullptr, *ropre = nullptr, *ro = nullptr, *r1 = nullptr, *tmp = nullptr, *dro = nullptr; };
 
 typedef void (*lseg_reduce_fn)(void* user, void* dev_ptr, int64_t n_floats, void* stream);   // in-place sum over ranks
@@ -116,6 +150,14 @@ private:
     int pack_resnet(hipStream_t st);
     int resnet_forward(const float* x, int B, hipStream_t st);
     int refine(int r, int B, hipStream_t st, bool stop_before_upsample = false);
+    // stages the inference and the train-mode forward share; the destination buffers are the caller's
+    int patch_embed(const float* x_in, float* x, int B, hipStream_t st);                       // im2col, patch GEMM + pos-embed, cls rows
+    int reassemble(int l, const float* x, const LevelSave& v, int B, hipStream_t st);          // readout .. layerN_rn -> rn_[l]
+    int out_conv(int l, int B, hipStream_t st);                                                // up_[l] -> path_[l]
+    int correlate_planes(const uint16_t* t, const uint16_t* pixels, int K, int npix, int p_div, float* planes, int round_mid, hipStream_t st);
+    int text_fork(hipStream_t st);
+    int text_join(hipStream_t st);
+    int check_grouping(int B);
     int flush_events();
     int materialize_low(hipStream_t st);
     bool low_pending_ = false; int low_planes_ = 0, low_k_ = 0;      // low_ = scaled x2 upsample of rpl_ not yet written (one-pass x4 upsample ran)
@@ -290,7 +332,7 @@ private:
     // ---- side stream: the (small, latency-bound) text tower overlaps the image tower ----------------
     hipStream_t text_stream_ = nullptr;
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_text_done_ = nullptr;
-    bool text_pending_ = false;
+    bool text_pending_ = false, text_forked_ = false;
 
     // ---- profiling: HIP-event pairs around kernel families on the caller's stream (lseg_set_profiling mask bit = family index) --------
 public:

@@ -619,40 +619,60 @@ int Engine::encode_text(hipStream_t st) {
     for (int i = 0; i < c.text_layers; ++i) {
         TextBlock& b = tblocks_[i];
         TRY(launch_layernorm(tx_, DT_F16, b.g1, b.b1, tln_, DT_F16, M, W, 1e-5f, st));
-        gemm_args_init(g);
-        g.A = tln_; g.W = b.qkv.w; g.M = M; g.N = 3 * W; g.K = W; g.lda = W; g.ldw = W;
-        g.bias = b.qkv.b; g.out_dtype = DT_F16; g.map_mode = MAP_QKV;
-        g.C = tq_; g.Ck = tk_; g.Cv = tvt_; g.qkv_dim = W; g.qkv_ntok = L; g.qkv_npad = tnpad_; g.qkv_heads = H;
+        g = qkv_args(tln_, b.qkv, M, tq_, tk_, tvt_, L, tnpad_, H, DT_F16);
         TRY(launch_gemm(g, DT_F16, st));
         TRY(launch_attention(tq_, tk_, tvt_, tatt_, K_, H, L, tnpad_, DT_F16, 1, 0.125f, st));
-        gemm_args_init(g);
-        g.A = tatt_; g.W = b.out.w; g.M = M; g.N = W; g.K = W; g.lda = W; g.ldw = W;
-        g.bias = b.out.b; g.round_mid = 1; g.res_mode = RES_DEST; g.res = tx_; g.res_dtype = DT_F16;
-        g.C = tx_; g.out_dtype = DT_F16; g.ldc = W; g.map_mode = MAP_LINEAR;
+        g = lin_args(tatt_, b.out, M, tx_, DT_F16);
+        g.round_mid = 1;                                  // CLIP's fp16 Linear rounds before the fp16 add (the text Linears only)
+        add_residual(g, tx_, DT_F16);
         TRY(launch_gemm(g, DT_F16, st));
         TRY(launch_layernorm(tx_, DT_F16, b.g2, b.b2, tln_, DT_F16, M, W, 1e-5f, st));
-        gemm_args_init(g);
-        g.A = tln_; g.W = b.fc.w; g.M = M; g.N = 4 * W; g.K = W; g.lda = W; g.ldw = W;
-        g.bias = b.fc.b; g.round_mid = 1; g.act = ACT_QUICKGELU;
-        g.C = tmlp_; g.out_dtype = DT_F16; g.ldc = 4 * W; g.map_mode = MAP_LINEAR;
+        g = lin_args(tln_, b.fc, M, tmlp_, DT_F16);
+        g.round_mid = 1; g.act = ACT_QUICKGELU;
         TRY(launch_gemm(g, DT_F16, st));
-        gemm_args_init(g);
-        g.A = tmlp_; g.W = b.proj.w; g.M = M; g.N = W; g.K = 4 * W; g.lda = 4 * W; g.ldw = 4 * W;
-        g.bias = b.proj.b; g.round_mid = 1; g.res_mode = RES_DEST; g.res = tx_; g.res_dtype = DT_F16;
-        g.C = tx_; g.out_dtype = DT_F16; g.ldc = W; g.map_mode = MAP_LINEAR;
+        g = lin_args(tmlp_, b.proj, M, tx_, DT_F16);
+        g.round_mid = 1;
+        add_residual(g, tx_, DT_F16);
         TRY(launch_gemm(g, DT_F16, st));
     }
     TRY(launch_layernorm(tx_, DT_F16, tlnf_g_, tlnf_b_, tln_, DT_F16, M, W, 1e-5f, st));
     TRY(launch_text_pool(tln_, d_eot_, tpool_, K_, L, W, st));
-    gemm_args_init(g);
-    g.A = tpool_; g.W = tproj_.w; g.M = K_; g.N = c.out_c; g.K = W; g.lda = W; g.ldw = W;
-    g.C = tfeat_; g.out_dtype = DT_F16; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+    g = lin_args(tpool_, tproj_, K_, tfeat_, DT_F16);      // text_projection: no bias (tproj_.b is NULL)
     TRY(launch_gemm(g, DT_F16, st));
     TRY(launch_text_l2norm(tfeat_, tnorm_, K_, c.out_c, st));
     LSEG_HIP_TRY(hipEventRecord(ev_text_done_, st));
     text_pending_ = true;
     text_valid = true;
     return 0;
+}
+
+// The text tower (lseg_net.py:181-183) is re-run every forward unless caching is on.  Its ~90 small kernels are latency-bound, so they
+// run on a side stream next to the image tower; the fork / join events keep everything ordered with respect to the caller's stream.
+int Engine::text_fork(hipStream_t st) {
+    text_forked_ = !text_external_ && (!text_cache || !text_valid);
+    if (!text_forked_) return 0;
+    LSEG_HIP_TRY(hipEventRecord(ev_fork_, st));
+    LSEG_HIP_TRY(hipStreamWaitEvent(text_stream_, ev_fork_, 0));
+    TRY(encode_text(text_stream_));
+    LSEG_HIP_TRY(hipEventRecord(ev_join_, text_stream_));
+    return 0;
+}
+int Engine::text_join(hipStream_t st) {                  // before the first reader of tnorm_: the correlation
+    if (text_forked_) LSEG_HIP_TRY(hipStreamWaitEvent(st, ev_join_, 0));
+    return 0;
+}
+
+// per-image label sets (LSegNetZS, lseg_net_zs.py:198-208): image b against token rows [b*k, (b+1)*k)
+int Engine::check_grouping(int B) {
+    if (group_k <= 0) return 0;
+    if (K_ != B * group_k) return set_error(LSEG_ERR_INVALID, "grouped labels: %d token rows != B=%d x %d labels per image", K_, B, group_k);
+    if (cfg.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "per-image label sets have no head blocks (lseg_net_zs.py:177-214)");
+    return 0;
+}
+
+static bool splitk_enabled() {                           // LSEG_SPLITK=0 (tools) switches both split-K plans off
+    static const int on = getenv("LSEG_SPLITK") ? atoi(getenv("LSEG_SPLITK")) : 1;
+    return on != 0;
 }
 
 int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* res2, void* out, int B, int H, int W,
@@ -673,8 +693,7 @@ int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* r
     if (relu_written) *relu_written = false;
     // Small batches: the deep levels of the pyramid are a handful of tiles with a 36..144-step contraction (layer3_rn at B = 1: 60 tiles of
     // 64 x 64, K = 9216, 95 us on a quarter of the chip).  Split-K work items into fp32 slabs + one streaming epilogue kernel.
-    static const int split_on = getenv("LSEG_SPLITK") ? atoi(getenv("LSEG_SPLITK")) : 1;
-    if (split_on && !(cfg.flags & 4) && !train_mode && !strict_ && !relu_in && (w.n % 64) == 0) {
+    if (splitk_enabled() && !(cfg.flags & 4) && !train_mode && !strict_ && !relu_in && (w.n % 64) == 0) {
         const int nk = w.k / 64;
         const long tiles = (long)((g.M + 63) / 64) * (w.n / 64);
         long ns = 512 / tiles;
@@ -727,13 +746,61 @@ int Engine::refine(int r, int B, hipStream_t st, bool stop_before_upsample) {
     if (stop_before_upsample) return 0;         // the commuted head takes it from here
     if (strict_) TRY(launch_upsample2x_nhwc_split(t2_[l], pl(t2_[l]), up_[l], pl(up_[l]), B, H, W, F, st));
     else TRY(launch_upsample2x_nhwc(t2_[l], up_[l], B, H, W, F, img_dt_, st));          // :352-354
-    GemmArgs g;
-    gemm_args_init(g);                                                                 // out_conv :356
-    g.A = up_[l]; g.W = R.out_conv.w; g.M = B * 4 * H * W; g.N = F; g.K = F; g.lda = F; g.ldw = F;
-    g.bias = R.out_conv.b; g.C = path_[l]; g.out_dtype = img_dt_; g.ldc = F;
-    if (l > 0) { g.map_mode = MAP_PADDED; g.ho = 2 * H; g.wo = 2 * W; }
-    else g.map_mode = MAP_LINEAR;
+    return out_conv(l, B, st);                                                         // :356
+}
+
+// FeatureFusionBlock_custom.out_conv on the x2-upsampled rows: path_r, padded at the next level's size (r = 1: plain rows, the head's input)
+int Engine::out_conv(int l, int B, hipStream_t st) {
+    GemmArgs g = lin_args(up_[l], refine_[l].out_conv, B * 4 * lh_[l] * lw_[l], path_[l], img_dt_);
+    if (l > 0) to_padded(g, 2 * lh_[l], 2 * lw_[l]);
     return igemm(g, st);
+}
+
+// forward_flex (lseg_vit.py:166-201): patch embed + pos embed into token rows 1.. of x [B*ntok, D], cls + pos into row 0
+int Engine::patch_embed(const float* x_in, float* x, int B, hipStream_t st) {
+    const lseg_config& c = cfg;
+    if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
+    else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
+    GemmArgs g = lin_args(patchA_, patch_, B * np_, x, DT_F32);
+    g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = c.dim;
+    g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
+    TRY(igemm(g, st));
+    return launch_cls_rows(cls_, pos_, x, B, ntok_, c.dim, st);
+}
+
+// Hook l of the ViT: ProjectReadout (lseg_vit.py:86-90) on the block output x, act_postprocess[3:] (1x1 conv, then ConvTranspose /
+// identity / 3x3 stride-2 conv) into L_[l], scratch.layerN_rn (lseg_net.py:171-174) into rn_[l].  v.ropre != NULL (train mode) also
+// keeps the readout's GELU input.
+int Engine::reassemble(int l, const float* x, const LevelSave& v, int B, hipStream_t st) {
+    const lseg_config& c = cfg;
+    const int D = c.dim, C = cp_[l], kind = c.resample_kind[l];      // C: padded channel count (== reassemble_ch unless ViT-B/32 level 1)
+    if (strict_) TRY(launch_readout_cat_split(x, v.cat, pl(v.cat), B, ntok_, D, st));
+    else TRY(launch_readout_cat(x, v.cat, B, ntok_, D, img_dt_, st));
+    GemmArgs g = lin_args(v.cat, readout_[l], B * np_, v.ro, img_dt_);
+    if (v.ropre) TRY(linear_gelu_saved(g, v.ropre, v.ro, st));
+    else { g.act = ACT_GELU; TRY(igemm(g, st)); }
+    // act_postprocess[3]: 1x1 conv (token-major rows == NHWC pixels, the Transpose/Unflatten are free)
+    g = lin_args(v.ro, r1x1_[l], B * np_, kind == LSEG_RS_CONVT ? v.r1 : kind == LSEG_RS_IDENTITY ? L_[l] : v.tmp, img_dt_);
+    if (kind != LSEG_RS_CONVT) to_padded(g, gh_, gw_);
+    TRY(igemm(g, st));
+    if (kind == LSEG_RS_CONVT) {
+        g = pixshuf_args(v.r1, rsmp_[l], B * np_, L_[l], C, c.resample_k[l], gh_, gw_, img_dt_);
+        TRY(igemm(g, st));
+    } else if (kind == LSEG_RS_CONV_S2) {
+        TRY(conv3x3(v.tmp, rsmp_[l], nullptr, nullptr, L_[l], B, gh_, gw_, 2, 0, 0, st));
+    }
+    return conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]);
+}
+
+// The correlation with the labels as GEMM rows and the pixels as its columns: planes [npix / p_div, K, p_div] (fp32) = t [K, out_c] .
+// pixels [npix, out_c]^T.  Each lane ends up with 4 consecutive pixels of one label plane (16-byte stores) and K = 150 pads to 160 rows,
+// not to 256 columns.  round_mid: the fp16 rounding of the reference's half matmul (lseg_net.py:194).
+int Engine::correlate_planes(const uint16_t* t, const uint16_t* pixels, int K, int npix, int p_div, float* planes, int round_mid, hipStream_t st) {
+    GemmArgs g;
+    gemm_args_init(g);
+    g.A = t; g.W = pixels; g.M = K; g.N = npix; g.K = cfg.out_c; g.lda = cfg.out_c; g.ldw = cfg.out_c;
+    g.round_mid = round_mid; g.C = planes; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = p_div;
+    return launch_gemm(g, DT_F16, st);
 }
 
 // timing events come from a free list filled outside the timed region (lseg_set_profiling / flush): no hipEventCreate per forward
@@ -843,8 +910,7 @@ int Engine::get_profile(const char* family, double* ms, int64_t* launches, doubl
 // each writes an fp32 partial slab (EPI_PART32), and the LayerNorm that follows anyway adds bias + slabs into x_ in a fixed order
 // (launch_layernorm_reduce) -- no extra launch, no atomics, deterministic.  Returns ns (0: the GEMM was left as it is).
 int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
-    static const int enabled = getenv("LSEG_SPLITK") ? atoi(getenv("LSEG_SPLITK")) : 1;      // tools: 0 switches it off
-    if (strict_ || !enabled || (cfg.flags & 4) || (N % 256) != 0) return 0;
+    if (strict_ || !splitk_enabled() || (cfg.flags & 4) || (N % 256) != 0) return 0;
     // Tile and split factor together, from measured per-K-step costs of the two tile shapes (us per 64-deep K-step of one work item on
     // one CU: 256x256 2.07, 128x128 0.87, 0.81 with two work items resident; ~4 K-steps of fixed cost per item; tools/step_probe.py
     // sweeps): a CU works through ceil(items / CUs) items; the slabs cost the LayerNorm ns * M * N * 4 bytes at ~4 TB/s.
@@ -886,22 +952,13 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     }
     if (eval_stale_) TRY(finalize(st));  // optimizer steps refresh only the train-mode packs: fold BatchNorm / the commuted head again
     const lseg_config& c = cfg;
-    const int D = c.dim, H = c.heads, F = c.features, M = B * ntok_;
+    const int D = c.dim, H = c.heads, M = B * ntok_;
     last_B_ = B;
     low_pending_ = false;
     hipEvent_t fwd0 = prof_begin(PF_FWD, st);
     const double ntok2 = (double)ntok_ * ntok_;
 
-    // ---- text tower (lseg_net.py:181-183): re-run every call unless caching is on.  Its ~90 small
-    // kernels are latency-bound, so they run on a side stream next to the image tower; fork/join
-    // events keep everything ordered with respect to the caller's stream.
-    const bool run_text = !text_external_ && (!text_cache || !text_valid);
-    if (run_text) {
-        LSEG_HIP_TRY(hipEventRecord(ev_fork_, st));
-        LSEG_HIP_TRY(hipStreamWaitEvent(text_stream_, ev_fork_, 0));
-        TRY(encode_text(text_stream_));
-        LSEG_HIP_TRY(hipEventRecord(ev_join_, text_stream_));
-    }
+    TRY(text_fork(st));                  // ---- text tower (lseg_net.py:181-183) on the side stream
 
     GemmArgs g;
     if (resnet_) {
@@ -911,14 +968,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
     } else {
         // ---- forward_flex (lseg_vit.py:166-201): patch embed + cls + pos -------------------------------------
-        if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
-        else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
-        gemm_args_init(g);
-        g.A = patchA_; g.W = patch_.w; g.M = B * np_; g.N = D; g.K = patch_.k; g.lda = patch_.k; g.ldw = patch_.k;
-        g.bias = patch_.b; g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = D;
-        g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
-        TRY(igemm(g, st));
-        TRY(launch_cls_rows(cls_, pos_, x_, B, ntok_, D, st));
+        TRY(patch_embed(x_in, x_, B, st));
+        const LevelSave neck{catA_, nullptr, ro_, r1_, tmp_pad_};       // one set of reassemble buffers for the four hooks; no saved GELU input
 
         // ---- 24 x timm Block; hooks feed readout/reassemble/layer_rn immediately ------------------------------
         int pend_ns = 0;                    // > 0: x_ still lacks `pend_bias` + the pend_ns split-K slabs in ws_split_ (see split_residual)
@@ -930,10 +981,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
             else TRY(launch_layernorm(x_, DT_F32, b.g1, b.b1, ln_, img_dt_, M, D, 1e-6f, st));
             prof_end(PF_LN, pe, 0.0, st);
-            gemm_args_init(g);
-            g.A = ln_; g.W = b.qkv.w; g.M = M; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D;
-            g.bias = b.qkv.b; g.out_dtype = img_dt_; g.map_mode = MAP_QKV;
-            g.C = q_; g.Ck = k_; g.Cv = vt_; g.qkv_dim = D; g.qkv_ntok = ntok_; g.qkv_npad = npad_; g.qkv_heads = H;
+            g = qkv_args(ln_, b.qkv, M, q_, k_, vt_, ntok_, npad_, H, img_dt_);
             // the softmax scale (head_dim^-0.5 = 0.125 for 64) * log2(e) rides on q through the QKV epilogue's single rounding: the attention
             // kernel's matrix pipe then delivers exp2 arguments (attention.hip PRE)
             g.qkv_qscale = 0.125f * 1.4426950408889634f;
@@ -949,10 +997,9 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             if (strict_) TRY(launch_attention_strict(q_, k_, vt_, att_, pl(q_), pl(vt_), pl(att_), B, H, ntok_, npad_, 0.125f, st));
             else TRY(launch_attention_ex(q_, k_, vt_, att_, nullptr, B, H, ntok_, npad_, img_dt_, 0, 0.125f, prescaled ? 1 : 0, st));
             prof_end(PF_ATTN, pe, 4.0 * B * ntok2 * D, st);          // QK^T + PV, SURVEY 8(d): 4 N^2 D per image and block
-            gemm_args_init(g);
-            g.A = att_; g.W = b.proj.w; g.M = M; g.N = D; g.K = D; g.lda = D; g.ldw = D;
-            g.bias = b.proj.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
-            g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
+            g = lin_args(att_, b.proj, M, x_, DT_F32);
+            add_residual(g, x_, DT_F32);
+            g.rows_alloc = rows_alloc_;                           // x_ / att_ reach the next 256 rows (inference buffers only)
             pend_ns = split_residual(g, M, D, D);                 // small batches: partial slabs, summed into x_ by the LayerNorm that follows
             pend_bias = b.proj.b;
             pe = prof_begin(PF_PROJ, st);
@@ -963,17 +1010,15 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             else if (pend_ns) { TRY(launch_layernorm_reduce(x_, ws_split_, pend_ns, (size_t)M * D, pend_bias, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st)); pend_ns = 0; }
             else TRY(launch_layernorm(x_, DT_F32, b.g2, b.b2, ln_, img_dt_, M, D, 1e-6f, st));
             prof_end(PF_LN, pe, 0.0, st);
-            gemm_args_init(g);
-            g.A = ln_; g.W = b.fc1.w; g.M = M; g.N = 4 * D; g.K = D; g.lda = D; g.ldw = D;
-            g.bias = b.fc1.b; g.act = ACT_GELU; g.C = mlp_; g.out_dtype = img_dt_; g.ldc = 4 * D; g.map_mode = MAP_LINEAR;
-            g.tag = 1;
+            g = lin_args(ln_, b.fc1, M, mlp_, img_dt_);
+            g.act = ACT_GELU;
+            g.tag = 1;                                            // the profiled instance (inference only)
             pe = prof_begin(PF_FC1, st);
             TRY(igemm(g, st));
             prof_end(PF_FC1, pe, 2.0 * M * 4.0 * D * D, st);
-            gemm_args_init(g);
-            g.A = mlp_; g.W = b.fc2.w; g.M = M; g.N = D; g.K = 4 * D; g.lda = 4 * D; g.ldw = 4 * D;
-            g.bias = b.fc2.b; g.res_mode = RES_DEST; g.res = x_; g.res_dtype = DT_F32;
-            g.C = x_; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR; g.rows_alloc = rows_alloc_;
+            g = lin_args(mlp_, b.fc2, M, x_, DT_F32);
+            add_residual(g, x_, DT_F32);
+            g.rows_alloc = rows_alloc_;
             pend_ns = split_residual(g, M, D, 4 * D);
             pend_bias = b.fc2.b;
             pe = prof_begin(PF_FC2, st);
@@ -993,38 +1038,9 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
                     if (!acts_[l]) ALLOC(acts_[l], float, (size_t)c.max_batch * ntok_ * D);
                     LSEG_HIP_TRY(hipMemcpyAsync(acts_[l], x_, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
                 }
-                const int C = cp_[l];                 // padded channel count (== reassemble_ch unless ViT-B/32 level 1)
-                // ProjectReadout (lseg_vit.py:86-90)
-                if (strict_) TRY(launch_readout_cat_split(x_, catA_, pl(catA_), B, ntok_, D, st));
-                else TRY(launch_readout_cat(x_, catA_, B, ntok_, D, img_dt_, st));
-                gemm_args_init(g);
-                g.A = catA_; g.W = readout_[l].w; g.M = B * np_; g.N = D; g.K = 2 * D; g.lda = 2 * D; g.ldw = 2 * D;
-                g.bias = readout_[l].b; g.act = ACT_GELU; g.C = ro_; g.out_dtype = img_dt_; g.ldc = D; g.map_mode = MAP_LINEAR;
-                TRY(igemm(g, st));
-                // act_postprocess[3]: 1x1 conv (token-major rows == NHWC pixels, the Transpose/Unflatten are free)
-                gemm_args_init(g);
-                g.A = ro_; g.W = r1x1_[l].w; g.M = B * np_; g.N = C; g.K = D; g.lda = D; g.ldw = D;
-                g.bias = r1x1_[l].b; g.out_dtype = img_dt_; g.ldc = C;
-                if (c.resample_kind[l] == LSEG_RS_CONVT) { g.C = r1_; g.map_mode = MAP_LINEAR; }
-                else if (c.resample_kind[l] == LSEG_RS_IDENTITY) { g.C = L_[l]; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-                else { g.C = tmp_pad_; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-                TRY(igemm(g, st));
-                if (c.resample_kind[l] == LSEG_RS_CONVT) {
-                    // ConvTranspose2d(k = s = stride) as a GEMM with a pixel-shuffle scatter epilogue
-                    const int s = c.resample_k[l];
-                    gemm_args_init(g);
-                    g.A = r1_; g.W = rsmp_[l].w; g.M = B * np_; g.N = s * s * C; g.K = C; g.lda = C; g.ldw = C;
-                    g.bias = rsmp_[l].b; g.bias_mod = C; g.C = L_[l]; g.out_dtype = img_dt_; g.ldc = C;
-                    g.map_mode = MAP_PIXSHUF; g.ho = gh_; g.wo = gw_; g.ps_s = s; g.ps_C = C;
-                    TRY(igemm(g, st));
-                } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
-                    TRY(conv3x3(tmp_pad_, rsmp_[l], nullptr, nullptr, L_[l], B, gh_, gw_, 2, 0, 0, st));
-                }
-                // scratch.layerN_rn (lseg_net.py:171-174)
-                TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
+                TRY(reassemble(l, x_, neck, B, st));
             }
         }
-
     }
 
     // ---- refinenet4..1 (lseg_net.py:176-179) ---------------------------------------------------------------
@@ -1033,27 +1049,18 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
     for (int r = 4; r >= 1; --r) TRY(refine(r, B, st, commuted && r == 1));
 
-    if (run_text) LSEG_HIP_TRY(hipStreamWaitEvent(st, ev_join_, 0));     // join before the correlation
+    TRY(text_join(st));                  // before the correlation
+    TRY(check_grouping(B));
 
     // ---- head1 + normalise + correlation (lseg_net.py:185-196) ------------------------------------------------
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp = B * hw1;
-    const float logit_scale = expf(logf(1.0f / 0.07f));                // lseg_net.py:141
-    gemm_args_init(g);
-    g.A = path_[0]; g.W = head1_.w; g.M = Mp; g.N = c.out_c; g.K = F; g.lda = F; g.ldw = F;
-    g.bias = head1_.b;
     // ... and so does the correlation: t_k . up(g)_P = up(t_k . g)_P, with ||up(g)_P|| from the dot products of g's 2x2 cells
     // (elementwise.hip "commuted correlation"): the pixel x text GEMM runs on 4x fewer pixels and the 240x240x512 feature map never exists
     static const bool corr_full = getenv("LSEG_CORR_FULLRES") != nullptr;           // A/B switch (tools): the correlation at (2h, 2w)
     const bool corr_low = commuted && !corr_full && (lw_[0] % 2) == 0;
-    if (corr_low && group_k > 0) {
-        if (K_ != B * group_k)
-            return set_error(LSEG_ERR_INVALID, "grouped labels: %d token rows != B=%d x %d labels per image", K_, B, group_k);
-        if (c.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "per-image label sets have no head blocks (lseg_net_zs.py:177-214)");
-    }
     if (corr_low) {
         const int hp = lh_[0] + 2, wp = lw_[0] + 2;
-        g.A = t2_[0]; g.W = headc_.w; g.bias = headc_.b; g.M = B * hp * wp;
-        g.C = g16pad_; g.out_dtype = DT_F16; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+        g = lin_args(t2_[0], headc_, B * hp * wp, g16pad_, DT_F16);      // every row of the padded map (border rows are never read)
         TRY(igemm(g, st));
         // the dedicated kernel (corr.hip): T resident in LDS, g streamed once, label planes and cell dot products from the same registers;
         // per-image label sets (zero-shot), other widths and label sets that do not fit the LDS take the generic GEMM + pixel_gram pair
@@ -1066,7 +1073,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         else TRY(launch_pixel_gram(g16pad_, gram_, B, lh_[0], lw_[0], c.out_c, st));
         if (corr_fused) prof_end(PF_CORR, pc, (double)B * hp * wp * c.out_c * 2.0 + (double)B * K_ * lh_[0] * lw_[0] * 4.0 + (double)B * lh_[0] * lw_[0] * 20.0 +
                                               (double)K_ * c.out_c * 2.0, st);
-        TRY(launch_norm_scale_plane(gram_, nscale_, B, lh_[0], lw_[0], logit_scale, st, ovf_dev_));
+        TRY(launch_norm_scale_plane(gram_, nscale_, B, lh_[0], lw_[0], logit_scale(), st, ovf_dev_));
         // the sentinel travels to pinned host memory behind the forward; Engine::overflow_seen reads it once the event has passed (no sync)
         (void)overflow_seen(false);                      // harvest the previous forward's copy before its event is recorded again
         LSEG_HIP_TRY(hipMemcpyAsync(ovf_host_, ovf_dev_, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1087,18 +1094,12 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         if (corr_fused) {
         } else if (group_k > 0) {
             // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [k, out_c] x [out_c, hp*wp]
-            for (int b = 0; b < B; ++b) {
-                gemm_args_init(g);
-                g.A = tnorm_ + (size_t)b * group_k * c.out_c; g.W = g16pad_ + (size_t)b * hp * wp * c.out_c;
-                g.M = group_k; g.N = hp * wp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
-                g.C = rpl_ + (size_t)b * group_k * hp * wp; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hp * wp;
-                TRY(launch_gemm(g, DT_F16, st));
-            }
+            for (int b = 0; b < B; ++b)
+                TRY(correlate_planes(tnorm_ + (size_t)b * group_k * c.out_c, g16pad_ + (size_t)b * hp * wp * c.out_c, group_k, hp * wp, hp * wp,
+                                     rpl_ + (size_t)b * group_k * hp * wp, 0, st));
         } else {
-            gemm_args_init(g);
-            g.A = tnorm_; g.W = g16pad_; g.M = K_; g.N = B * hp * wp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
-            g.C = rpl_; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hp * wp;
-            TRY(launch_gemm(g, DT_F16, st));
+            // round_mid 0: R holds the unscaled dot products t_k . g as they are; the scale plane comes in with the upsample
+            TRY(correlate_planes(tnorm_, g16pad_, K_, B * hp * wp, hp * wp, rpl_, 0, st));
         }
         // R -> logits.  When only the full-resolution logits are wanted the two x2 upsamples run as one pass and the (2h, 2w) logits
         // stay in LDS; masks, head blocks, the "lowres" tap and lseg_forward_stats need them in memory (made on demand below).
@@ -1114,28 +1115,25 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         TRY(materialize_low(st));
     } else if (commuted) {
         // g = Wc t2 + bc on every row of the padded map (border rows are never read), fp32; then x2 bilinear + L2-norm + fp16 casts
-        g.A = t2_[0]; g.W = headc_.w; g.bias = headc_.b; g.M = B * (lh_[0] + 2) * (lw_[0] + 2);
-        g.C = gpad_; g.out_dtype = DT_F32; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+        g = lin_args(t2_[0], headc_, B * (lh_[0] + 2) * (lw_[0] + 2), gpad_, DT_F32);
         TRY(igemm(g, st));
-        TRY(launch_upsample_norm_f16(gpad_, a16_, B, lh_[0], lw_[0], c.out_c, logit_scale, st));
+        TRY(launch_upsample_norm_f16(gpad_, a16_, B, lh_[0], lw_[0], c.out_c, logit_scale(), st));
     } else if (c.out_c == 512 && !debug && !strict_) {
         // fused: head1 + fp32 L2-norm + the two fp16 roundings in one epilogue (rows are complete inside
         // a workgroup); the 118 MB/image fp32 feature map is never written
-        g.C = a16_; g.out_dtype = DT_F16; g.ldc = c.out_c; g.map_mode = MAP_ROWNORM; g.rn_scale = logit_scale;
+        g = lin_args(path_[0], head1_, Mp, a16_, DT_F16);
+        g.map_mode = MAP_ROWNORM; g.rn_scale = logit_scale();
         TRY(igemm(g, st));
     } else {
-        g.C = feat_; g.out_dtype = DT_F32; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+        g = lin_args(path_[0], head1_, Mp, feat_, DT_F32);
         TRY(igemm(g, st));
-        TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale, st));
+        TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale(), st));
     }
     const int Kout = group_k > 0 ? group_k : K_;            // label planes per image
     if (corr_low) {
         // low_ already holds the (2h, 2w) logits
     } else if (group_k > 0) {
         // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [hw1,out_c] x [out_c,k]
-        if (K_ != B * group_k)
-            return set_error(LSEG_ERR_INVALID, "grouped labels: %d token rows != B=%d x %d labels per image", K_, B, group_k);
-        if (c.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "per-image label sets have no head blocks (lseg_net_zs.py:177-214)");
         for (int b = 0; b < B; ++b) {
             gemm_args_init(g);
             g.A = a16_ + (size_t)b * hw1 * c.out_c; g.W = tnorm_ + (size_t)b * group_k * c.out_c;
@@ -1144,12 +1142,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             TRY(launch_gemm(g, DT_F16, st));
         }
     } else {
-    // the labels are the GEMM's rows and the pixels its columns: each lane ends up with 4 consecutive pixels of one label plane
-    // (16-byte stores into [B, K, h*w]) and K = 150 pads to 160 rows, not to 256 columns
-    gemm_args_init(g);
-    g.A = tnorm_; g.W = a16_; g.M = K_; g.N = Mp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
-    g.round_mid = 1; g.C = low_; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hw1;
-    TRY(launch_gemm(g, DT_F16, st));
+        TRY(correlate_planes(tnorm_, a16_, K_, Mp, hw1, low_, 1, st));
     }
     float* low = low_;
     if (c.arch_option == 1 || c.arch_option == 2) {                    // lseg_net.py:198-201

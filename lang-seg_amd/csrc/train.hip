@@ -337,89 +337,38 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     const lseg_config& c = cfg;
     const int D = c.dim, H = c.heads, F = c.features, M = B * ntok_;
     if (!train_alloc_) return set_error(LSEG_ERR_STATE, "train mode was not enabled (lseg_set_train)");
-    if (group_k > 0) {              // per-image label sets (LSegNetZS, lseg_net_zs.py:198-208): image b against token rows [b*k, (b+1)*k)
-        if (K_ != B * group_k)
-            return set_error(LSEG_ERR_INVALID, "grouped labels: %d token rows != B=%d x %d labels per image", K_, B, group_k);
-        if (c.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "per-image label sets have no head blocks (lseg_net_zs.py:177-214)");
-        if (!corr_group_supported(group_k, c.out_c))
-            return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
-                             CORR_GROUP_MAX, group_k);
-    }
+    TRY(check_grouping(B));
+    if (group_k > 0 && !corr_group_supported(group_k, c.out_c))
+        return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
+                         CORR_GROUP_MAX, group_k);
     train_fwd_valid_ = false;
     loss_target_ = nullptr;
     last_B_ = B;
     low_pending_ = false;
     eval_stale_ = true;             // the BatchNorm running statistics move: the eval-mode (BN-folded) packs are refreshed by the next eval forward
-    const bool run_text = !text_external_ && (!text_cache || !text_valid);
-    if (run_text) {
-        LSEG_HIP_TRY(hipEventRecord(ev_fork_, st));
-        LSEG_HIP_TRY(hipStreamWaitEvent(text_stream_, ev_fork_, 0));
-        TRY(encode_text(text_stream_));
-        LSEG_HIP_TRY(hipEventRecord(ev_join_, text_stream_));
-    }
+    TRY(text_fork(st));
     TRY(zero_begin(zero_fwd_, st));
-    TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
+    TRY(patch_embed(x_in, sv_[0].xin, B, st));
     GemmArgs g;
-    gemm_args_init(g);
-    g.A = patchA_; g.W = patch_.w; g.M = B * np_; g.N = D; g.K = patch_.k; g.lda = patch_.k; g.ldw = patch_.k;
-    g.bias = patch_.b; g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = D;
-    g.C = sv_[0].xin; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
-    TRY(launch_gemm(g, img_dt_, st));
-    TRY(launch_cls_rows(cls_, pos_, sv_[0].xin, B, ntok_, D, st));
     for (int i = 0; i < c.depth; ++i) {
         VitBlock& b = blocks_[i];
         BlockSave& s = sv_[i];
         float* xout = i + 1 < c.depth ? sv_[i + 1].xin : xlast_;
         TRY(launch_layernorm(s.xin, DT_F32, b.g1, b.b1, s.ln1, img_dt_, M, D, 1e-6f, st));
-        gemm_args_init(g);
-        g.A = s.ln1; g.W = b.qkv.w; g.M = M; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.qkv.b; g.out_dtype = img_dt_; g.map_mode = MAP_QKV;
-        g.C = s.q; g.Ck = s.k; g.Cv = s.vt; g.qkv_dim = D; g.qkv_ntok = ntok_; g.qkv_npad = npad_; g.qkv_heads = H;
+        g = qkv_args(s.ln1, b.qkv, M, s.q, s.k, s.vt, ntok_, npad_, H, img_dt_);
         TRY(launch_gemm(g, img_dt_, st));
         TRY(launch_attention_lse(s.q, s.k, s.vt, s.att, s.lse, B, H, ntok_, npad_, img_dt_, 0, 0.125f, st));
-        gemm_args_init(g);
-        g.A = s.att; g.W = b.proj.w; g.M = M; g.N = D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.proj.b; g.res_mode = RES_DEST; g.res = s.xin; g.res_dtype = DT_F32;
-        g.C = s.xmid; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR;
+        g = lin_args(s.att, b.proj, M, s.xmid, DT_F32);
+        add_residual(g, s.xin, DT_F32);
         TRY(launch_gemm(g, img_dt_, st));
         TRY(launch_layernorm(s.xmid, DT_F32, b.g2, b.b2, s.ln2, img_dt_, M, D, 1e-6f, st));
-        gemm_args_init(g);
-        g.A = s.ln2; g.W = b.fc1.w; g.M = M; g.N = 4 * D; g.K = D; g.lda = D; g.ldw = D;
-        g.bias = b.fc1.b; g.out_dtype = img_dt_; g.ldc = 4 * D; g.map_mode = MAP_LINEAR;
+        g = lin_args(s.ln2, b.fc1, M, s.mlp, img_dt_);
         TRY(linear_gelu_saved(g, s.pre, s.mlp, st));
-        gemm_args_init(g);
-        g.A = s.mlp; g.W = b.fc2.w; g.M = M; g.N = D; g.K = 4 * D; g.lda = 4 * D; g.ldw = 4 * D;
-        g.bias = b.fc2.b; g.res_mode = RES_DEST; g.res = s.xmid; g.res_dtype = DT_F32;
-        g.C = xout; g.out_dtype = DT_F32; g.ldc = D; g.map_mode = MAP_LINEAR;
+        g = lin_args(s.mlp, b.fc2, M, xout, DT_F32);
+        add_residual(g, s.xmid, DT_F32);
         TRY(launch_gemm(g, img_dt_, st));
-        for (int l = 0; l < 4; ++l) {
-            if (c.hooks[l] != i) continue;
-            LevelSave& v = lv_[l];
-            const int C = cp_[l];
-            TRY(launch_readout_cat(xout, v.cat, B, ntok_, D, img_dt_, st));
-            gemm_args_init(g);
-            g.A = v.cat; g.W = readout_[l].w; g.M = B * np_; g.N = D; g.K = 2 * D; g.lda = 2 * D; g.ldw = 2 * D;
-            g.bias = readout_[l].b; g.out_dtype = img_dt_; g.ldc = D; g.map_mode = MAP_LINEAR;
-            TRY(linear_gelu_saved(g, v.ropre, v.ro, st));
-            gemm_args_init(g);
-            g.A = v.ro; g.W = r1x1_[l].w; g.M = B * np_; g.N = C; g.K = D; g.lda = D; g.ldw = D;
-            g.bias = r1x1_[l].b; g.out_dtype = img_dt_; g.ldc = C;
-            if (c.resample_kind[l] == LSEG_RS_CONVT) { g.C = v.r1; g.map_mode = MAP_LINEAR; }
-            else if (c.resample_kind[l] == LSEG_RS_IDENTITY) { g.C = L_[l]; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-            else { g.C = v.tmp; g.map_mode = MAP_PADDED; g.ho = gh_; g.wo = gw_; }
-            TRY(launch_gemm(g, img_dt_, st));
-            if (c.resample_kind[l] == LSEG_RS_CONVT) {
-                const int s2 = c.resample_k[l];
-                gemm_args_init(g);
-                g.A = v.r1; g.W = rsmp_[l].w; g.M = B * np_; g.N = s2 * s2 * C; g.K = C; g.lda = C; g.ldw = C;
-                g.bias = rsmp_[l].b; g.bias_mod = C; g.C = L_[l]; g.out_dtype = img_dt_; g.ldc = C;
-                g.map_mode = MAP_PIXSHUF; g.ho = gh_; g.wo = gw_; g.ps_s = s2; g.ps_C = C;
-                TRY(launch_gemm(g, img_dt_, st));
-            } else if (c.resample_kind[l] == LSEG_RS_CONV_S2) {
-                TRY(conv3x3(v.tmp, rsmp_[l], nullptr, nullptr, L_[l], B, gh_, gw_, 2, 0, 0, st));
-            }
-            TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
-        }
+        for (int l = 0; l < 4; ++l)
+            if (c.hooks[l] == i) TRY(reassemble(l, xout, lv_[l], B, st));
     }
     // refinenet4..1 in train mode
     for (int r = 4; r >= 1; --r) {
@@ -429,31 +378,20 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
         if (R.has_u1) { TRY(rcu_train(rn_[l], in2r, R.u1, path_[l + 1], sum_[l], sumr_[l], B, Hh, Ww, st)); in2 = sum_[l]; in2r = sumr_[l]; }
         TRY(rcu_train(in2, in2r, R.u2, nullptr, t2_[l], nullptr, B, Hh, Ww, st));
         TRY(launch_upsample2x_nhwc(t2_[l], up_[l], B, Hh, Ww, F, img_dt_, st));
-        gemm_args_init(g);
-        g.A = up_[l]; g.W = R.out_conv.w; g.M = B * 4 * Hh * Ww; g.N = F; g.K = F; g.lda = F; g.ldw = F;
-        g.bias = R.out_conv.b; g.C = path_[l]; g.out_dtype = img_dt_; g.ldc = F;
-        if (l > 0) { g.map_mode = MAP_PADDED; g.ho = 2 * Hh; g.wo = 2 * Ww; }
-        else g.map_mode = MAP_LINEAR;
-        TRY(launch_gemm(g, img_dt_, st));
+        TRY(out_conv(l, B, st));
     }
-    if (run_text) LSEG_HIP_TRY(hipStreamWaitEvent(st, ev_join_, 0));
+    TRY(text_join(st));
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp = B * hw1;
-    const float logit_scale = expf(logf(1.0f / 0.07f));
-    gemm_args_init(g);
-    g.A = path_[0]; g.W = head1_.w; g.M = Mp; g.N = c.out_c; g.K = F; g.lda = F; g.ldw = F;
-    g.bias = head1_.b; g.C = feat_; g.out_dtype = DT_F32; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+    g = lin_args(path_[0], head1_, Mp, feat_, DT_F32);
     TRY(launch_gemm(g, img_dt_, st));
-    TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale, st));
+    TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale(), st));
     const int kout = group_k > 0 ? group_k : K_;             // label planes per image
     if (group_k > 0) {
         // per-image correlation (corr_group.hip): the same rounding points as the GEMM below; the grouped backward reads tnorm_ itself,
         // so there is no transposed dgrad operand to make
         TRY(launch_corr_group_fwd(a16_, tnorm_, low_, B, hw1, group_k, c.out_c, st));
     } else {
-        gemm_args_init(g);
-        g.A = tnorm_; g.W = a16_; g.M = K_; g.N = Mp; g.K = c.out_c; g.lda = c.out_c; g.ldw = c.out_c;
-        g.round_mid = 1; g.C = low_; g.out_dtype = DT_F32; g.map_mode = MAP_LABELPLANES; g.p_div = hw1;
-        TRY(launch_gemm(g, DT_F16, st));
+        TRY(correlate_planes(tnorm_, a16_, K_, Mp, hw1, low_, 1, st));
         // the text features as the dgrad operand of the correlation: bf16, transposed, K padded to the GEMM's K-step
         const int Kp = (int)up64(K_);
         if (cfg.flags & 2) {
@@ -566,9 +504,8 @@ int Engine::lin_bwd(const uint16_t* dy, int M, int N, int K, const uint16_t* x, 
                     int acc, hipStream_t st, int dw_rows, const uint16_t* dgelu_pre) {
     GemmArgs g;
     if (dx) {
-        gemm_args_init(g);
-        g.A = dy; g.W = wt; g.M = M; g.N = K; g.K = N; g.lda = N; g.ldw = N;
-        g.bias = zeros_; g.C = dx; g.out_dtype = img_dt_; g.ldc = K; g.map_mode = MAP_LINEAR;
+        const Lin wT{const_cast<uint16_t*>(wt), zeros_, K, N};        // the dgrad is a Linear on W^T with a bias of zeros
+        g = lin_args(dy, wT, M, dx, img_dt_);
         // dgelu_pre: x = gelu(z) came out of a GELU; dx leaves as d z = (dy . W) * gelu'(z), in the GEMM epilogue where it can
         g.dgelu_pre = dgelu_pre;
         const bool fused = dgelu_pre && gemm_fuses_gelu(g, img_dt_);
@@ -583,9 +520,8 @@ int Engine::lin_bwd(const uint16_t* dy, int M, int N, int K, const uint16_t* x, 
         if ((size_t)N * Mp > ws_a_n_ || (size_t)K * Mp > ws_b_n_) return set_error(LSEG_ERR_STATE, "wgrad workspace too small (%d x %d x %d)", M, N, K);
         TRY(launch_transpose16(dy, ws_a_, M, N, N, Mp, st));
         TRY(launch_transpose16(x, ws_b_, M, K, K, Mp, st));
-        gemm_args_init(g);
-        g.A = ws_a_; g.W = ws_b_; g.M = dw_rows > 0 ? dw_rows : N; g.N = K; g.K = Mp; g.lda = Mp; g.ldw = Mp;
-        g.C = dw; g.out_dtype = DT_F32; g.ldc = K; g.map_mode = MAP_LINEAR;
+        const Lin xT{ws_b_, nullptr, K, Mp};                          // dw = dy^T . (x^T)^T, no bias
+        g = lin_args(ws_a_, xT, dw_rows > 0 ? dw_rows : N, dw, DT_F32);
         const int ns = pick_split(g.M, g.N, Mp / 64, g);
         if (ns > 1) {      // small output, long contraction: split-K partials, summed (and accumulated) afterwards
             g.C = ws_part_; g.c_split_stride = (size_t)g.M * K;
@@ -621,10 +557,8 @@ int Engine::conv_bwd(const uint16_t* dy_pad, const uint16_t* x_pad, int relu_x, 
             const int shift = (t / 3 - 1) * (W + 2) + (t % 3 - 1);
             TRY(launch_transpose16(x_pad, ws_b_ + (size_t)t * Cin * Mpp, Mp, Cin, Cin, Mpp, st, shift, relu_x));
         }
-        GemmArgs g;
-        gemm_args_init(g);
-        g.A = ws_a_; g.W = ws_b_; g.M = Cout; g.N = 9 * Cin; g.K = Mpp; g.lda = Mpp; g.ldw = Mpp;
-        g.C = ws_dw_; g.out_dtype = DT_F32; g.ldc = 9 * Cin; g.map_mode = MAP_LINEAR;
+        const Lin xT{ws_b_, nullptr, 9 * Cin, Mpp};                   // the 9 shifted transposes of x, no bias
+        GemmArgs g = lin_args(ws_a_, xT, Cout, ws_dw_, DT_F32);
         const int ns = pick_split(Cout, 9 * Cin, Mpp / 64, g);
         if (ns > 1) { g.C = ws_part_; g.c_split_stride = (size_t)Cout * 9 * Cin; }
         TRY(launch_gemm(g, img_dt_, st));
@@ -830,7 +764,6 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp1 = B * hw1;
     // label planes per image and the row pitch of d(low): per-image sets (G <= 8) hand the grouped kernel one 16-byte row per pixel
     const int G = train_G_, kout = G > 0 ? G : K_, Kp = G > 0 ? 8 : (int)up64(K_);
-    const float logit_scale = expf(logf(1.0f / 0.07f));
     if (!acc) TRY(zero_begin(zero_bwd_, st));
     // The reference back-propagates through `logit_scale * image_features.half() @ text_features.t()` (lseg_net.py:194) in HALF precision:
     // d(logits) is cast to fp16 (the `.float()` of :196 under autograd), dA = d(logits) @ text_features is an fp16 tensor (fp32
@@ -853,14 +786,12 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     // ---- head: correlation, L2-norm, head1 -------------------------------------------------------------------------------------
     if (G > 0) {
         // per-image label sets: dA from the image's own G text rows, the scale and the L2-norm backward in one pass (corr_group.hip)
-        TRY(launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, G, c.out_c, logit_scale, st));
+        TRY(launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, G, c.out_c, logit_scale(), st));
     } else {
-        GemmArgs g;
-        gemm_args_init(g);
-        g.A = drows_; g.W = tnT_; g.M = Mp1; g.N = c.out_c; g.K = Kp; g.lda = Kp; g.ldw = Kp;
-        g.bias = zeros_; g.C = da_; g.out_dtype = hdt; g.ldc = c.out_c; g.map_mode = MAP_LINEAR;
+        const Lin tT{tnT_, zeros_, c.out_c, Kp};                      // dA = d(logits) . T on the transposed text features, bias of zeros
+        GemmArgs g = lin_args(drows_, tT, Mp1, da_, hdt);
         TRY(launch_gemm(g, hdt, st));
-        TRY(launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, c.out_c, logit_scale, st));
+        TRY(launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, c.out_c, logit_scale(), st));
     }
     TRY(lin_bwd(df_, Mp1, c.out_c, F, path_[0], head1_.wt, dpath0_, grad("scratch.head1.weight", (size_t)c.out_c * F),
                 grad("scratch.head1.bias", c.out_c), acc, st));

@@ -1,0 +1,154 @@
+"""Bit identity of two builds of liblseg_hip.so: sha256 of every output tensor of a fixed list of small cases that together reach each
+GEMM descriptor and stage the forwards, the text tower and the backward share (csrc/engine.h builders, Engine::patch_embed /
+reassemble / out_conv / correlate_planes).  A host-side restructuring of the schedule must leave every line unchanged.
+
+    python tools/ab_bit_identity.py --lib OLD/liblseg_hip.so --out old.txt
+    python tools/ab_bit_identity.py --out new.txt          # the in-tree build
+    diff old.txt new.txt                                   # must be empty; the last line of each is the case count + overall hash
+
+One fresh interpreter per case (the library is chosen through LSEG_HIP_LIB), each under its own time limit; the run stops at the first
+child that does not exit 0 and returns its status.  `--cases a,b` selects, `--list` names them.
+"""
+import argparse
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "lang-seg_amd")]
+
+LABELS = ["wall", "sky", "tree", "floor", "other", "road", "grass"]
+
+
+def emit(case, name, t):
+    import torch
+    t = t.detach().contiguous().cpu()
+    raw = t.view(torch.uint8).numpy().tobytes() if t.numel() else b""
+    print(f"{case} {name} {str(t.dtype).replace('torch.', '')}{list(t.shape)} {hashlib.sha256(raw).hexdigest()}", flush=True)
+
+
+def engine(backbone, S, B, K, dtype, group=0, **kw):
+    from lseg_hip.config import get_config
+    from lseg_hip.engine import HipEngine
+    from lseg_hip.synth import synthetic_state_dict, synthetic_tokens, synthetic_images
+    cfg = get_config(backbone, arch_option=kw.pop("arch_option", 0), block_depth=kw.pop("block_depth", 0))
+    sd = {k: v.cuda() for k, v in synthetic_state_dict(cfg, seed=7).items()}
+    eng = HipEngine(cfg, S, S, max_batch=B, max_labels=K, image_dtype=dtype, deterministic=True, **kw)
+    eng.load_state_dict(sd)
+    eng.set_tokens(synthetic_tokens([LABELS[i % len(LABELS)] for i in range(K)], cfg.text.vocab, cfg.text.ctx), labels_per_image=group)
+    return eng, sd, synthetic_images(B, S, S, seed=7).cuda()
+
+
+def run_eval(case, backbone, S, B, K, dtypes, group=0, debug=False, text_features=False, **kw):
+    import torch
+    for dt in dtypes:
+        eng, _, x = engine(backbone, S, B, K, dt, group, **kw)
+        if text_features:                                       # the tower's own features handed back in, scaled: the engine normalises
+            eng.set_text_features(eng.encode_text() * 3.0)
+        eng.set_debug(debug)
+        kout = group if group else K
+        emit(case, f"{dt}.logits", eng.forward(x))
+        emit(case, f"{dt}.lowres", eng.intermediate("lowres", (B, kout, S // 2, S // 2)))
+        emit(case, f"{dt}.masks", eng.forward(x, want_logits=False, want_argmax=True))
+        lab, score = eng.forward_labels(x, want_score=True)
+        emit(case, f"{dt}.labels", lab)
+        emit(case, f"{dt}.score", score)
+        if debug and eng.cfg.tower != "resnet101":
+            ntok = (S // eng.cfg.patch) ** 2 + 1
+            for l in range(4):
+                emit(case, f"{dt}.act{l + 1}", eng.intermediate(f"act{l + 1}", (B, ntok, eng.cfg.dim)))
+        torch.cuda.synchronize()
+        eng.close()
+
+
+def run_train(case, backbone, S, B, K, group=0, freeze=False, **kw):
+    import torch
+    eng, sd, x = engine(backbone, S, B, K, "bf16", group, **kw)
+    eng.enable_training(sd, freeze_encoder=freeze)
+    kout = group if group else K
+    target = torch.randint(0, kout, (B, S, S), generator=torch.Generator().manual_seed(11)).cuda()
+    emit(case, "logits", eng.forward(x))
+    eng.backward(target=target, ignore_index=-100)
+    torch.cuda.synchronize()
+    emit(case, "loss_pair", eng._loss)
+    for k in sorted(eng.grads):
+        emit(case, f"grad.{k}", eng.grads[k])
+    eng.close()
+
+
+ALL3, TWO = ("fp16", "bf16", "strict"), ("fp16", "bf16")
+CASES = {
+    # ConvT / identity / conv-s2 resamples, split-K slabs at B = 1, the commuted head, the one-pass x4 upsample, the streamed labels
+    "tiny16_b1": lambda c: run_eval(c, "tiny16", 64, 1, 5, ALL3),
+    "tiny16_b3": lambda c: run_eval(c, "tiny16", 64, 3, 5, ALL3),
+    # the reference-order head, the activation taps
+    "tiny16_debug_b1": lambda c: run_eval(c, "tiny16", 64, 1, 5, ALL3, debug=True),
+    "tiny16_debug_b3": lambda c: run_eval(c, "tiny16", 64, 3, 5, ALL3, debug=True),
+    "tiny32_b2": lambda c: run_eval(c, "tiny32", 96, 2, 7, TWO),
+    "tiny16_arch1": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO, arch_option=1, block_depth=2),
+    "tiny16_arch2": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO, arch_option=2, block_depth=2),
+    "tiny16_grouped": lambda c: run_eval(c, "tiny16", 64, 2, 6, TWO, group=3),
+    "tiny16_grouped_debug": lambda c: run_eval(c, "tiny16", 64, 2, 6, TWO, group=3, debug=True),
+    "tiny16_text_features": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO, text_features=True),
+    "tiny16_corr_generic": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO),                      # the parent sets LSEG_CORR_GENERIC=1
+    "tiny16_train": lambda c: run_train(c, "tiny16", 64, 2, 5),
+    "tiny16_train_frozen": lambda c: run_train(c, "tiny16", 64, 2, 5, freeze=True),
+    "tiny16_train_grouped": lambda c: run_train(c, "tiny16", 64, 2, 6, group=3),
+    "tiny16_train_arch1": lambda c: run_train(c, "tiny16", 64, 2, 5, arch_option=1, block_depth=2, head_block_training=True),
+    "rn101_zs": lambda c: run_eval(c, "clip_resnet101", 96, 2, 4, TWO, group=2),
+    # real width: the 256-wide tile choices, split_residual
+    "vitl16_b1": lambda c: run_eval(c, "clip_vitl16_384", 96, 1, 5, TWO),
+    "vitl16_train": lambda c: run_train(c, "clip_vitl16_384", 96, 1, 5),
+}
+CHILD_ENV = {"tiny16_corr_generic": {"LSEG_CORR_GENERIC": "1"}}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lib", help="the liblseg_hip.so to load (default: the in-tree build)")
+    ap.add_argument("--cases", help="comma-separated subset")
+    ap.add_argument("--timeout", type=float, default=180.0, help="seconds per child")
+    ap.add_argument("--out", help="also write the listing here")
+    ap.add_argument("--list", action="store_true")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.list:
+        print("\n".join(CASES))
+        return 0
+    if a.child:
+        import torch
+        assert torch.cuda.is_available(), "needs a GPU"
+        CASES[a.child](a.child)
+        return 0
+    names = a.cases.split(",") if a.cases else list(CASES)
+    lines = []
+    for name in names:
+        if name not in CASES:
+            print(f"unknown case '{name}'", file=sys.stderr)
+            return 2
+        env = dict(os.environ, LSEG_SYNTHETIC_TOKENS="1", **CHILD_ENV.get(name, {}))
+        if a.lib:
+            env["LSEG_HIP_LIB"] = os.path.abspath(a.lib)
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], env=env, stdout=subprocess.PIPE, text=True,
+                               timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            print(f"case {name}: no result after {a.timeout:.0f} s -- stopping", file=sys.stderr)
+            return 124
+        sys.stdout.write(r.stdout)
+        sys.stdout.flush()
+        if r.returncode != 0:
+            print(f"case {name}: exit status {r.returncode} -- stopping", file=sys.stderr)
+            return r.returncode if r.returncode > 0 else 128 - r.returncode
+        lines += r.stdout.splitlines()
+    lines.append(f"TOTAL {len(names)} cases {len(lines)} tensors {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}")
+    print(lines[-1])
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
