@@ -110,7 +110,17 @@ typedef struct {
                                * Parameters under the reference's keys pretrained.layer1.{0,1,4.*}, pretrained.layer{2,3,4}.*.  The ViT
                                * fields (patch, dim, depth, heads, hooks, pos_grid, reassemble_*, resample_*) are ignored.  Refused:
                                * img_h / img_w not a multiple of 32 (LSEG_ERR_INVALID), image_dtype LSEG_F16_SPLIT, arch_option != 0 and
-                               * lseg_set_train (LSEG_ERR_UNSUPPORTED).  Inference only. */
+                               * lseg_set_train (LSEG_ERR_UNSUPPORTED).  Inference only, unless bit 6 is set.
+                               * bit 6 (training, with bit 5 only; on a ViT config LSEG_ERR_INVALID): train the DECODER above the ResNet-101
+                               * tower.  lseg_set_train(h, 1) is accepted (bf16 operands): the train-mode forward runs every conv of the
+                               * tower on its unfolded weights and all 104 BatchNorms on batch statistics (biased variance), updating
+                               * running_mean / running_var in the bound tensors (momentum 0.1, unbiased variance) -- the reference's
+                               * module in train() with the pretrained group at lr 0.  lseg_backward* stops at the four stage outputs:
+                               * scratch.* (layerN_rn, the refinenets, head1) is the whole trainable set, in bucket 0
+                               * (lseg_num_grad_buckets = 1); pretrained.* has no bucket, no gradient and no optimizer state, and an
+                               * optimizer step does not touch its masters or operand copies.  lseg_set_frozen_encoder keeps refusing the
+                               * tower; synchronised BatchNorm (lseg_set_bn_sync with world_size > 1) is refused by the forward.  After
+                               * lseg_set_train(h, 0) the next forward folds the BatchNorms again, from the updated running statistics. */
 } lseg_config;
 
 typedef struct lseg_engine* lseg_handle;
@@ -296,7 +306,16 @@ int lseg_op_conv3x3(const void* d_in, const void* d_w_packed, const float* d_bia
  *   lseg_op_conv        1x1 (ksize 1, pad 0, w_packed [Cout, Cin]) or 3x3 (ksize 3, pad 1, w_packed [Cout, 9*Cin] tap-major) conv,
  *                       stride 1|2, on padded NHWC maps as lseg_op_conv3x3, bias fp32 [Cout] or NULL, residual (geometry of out) or
  *                       NULL; relu_out applies ReLU, BEFORE the residual add (relu_after_res = 0, the DPT units' order) or AFTER it
- *                       (relu_after_res = 1: relu(conv + bias + residual), the bottleneck's).  Cin % 64 == 0. */
+ *                       (relu_after_res = 1: relu(conv + bias + residual), the bottleneck's).  Cin % 64 == 0.
+ *   lseg_op_bn_apply_res  train-mode BatchNorm of the tower (flags bit 6) from batch sums, one streaming pass over a padded NHWC map
+ *                       [B,H+2,W+2,C] (C % 8 == 0; interior written, the zero border untouched): d_y = [relu](bn(d_x) + r), bn(x) =
+ *                       gamma (x - mean) / sqrt(var + eps) + beta with mean / BIASED var from d_stats fp32 [2C] = {sum x, sum x^2} over
+ *                       the B H W pixels (lseg_op_bn_stats).  r = 0 (d_res_pad NULL), the plain map d_res_pad (d_res_stats NULL: the
+ *                       identity of a bottleneck), or bn_r(d_res_pad) from d_res_stats / d_res_gamma / d_res_beta (the downsample branch
+ *                       of a stage's first block).  d_y_pad may be d_x_pad (in place) and d_res_pad may be d_y_pad. */
+int lseg_op_bn_apply_res(const void* d_x_pad, void* d_y_pad, const float* d_stats, const float* d_gamma, const float* d_beta, const void* d_res_pad,
+                         const float* d_res_stats, const float* d_res_gamma, const float* d_res_beta, int B, int H, int W, int C, float eps,
+                         int relu, int dtype, void* stream);
 int lseg_op_rn_stem(const float* d_x, const float* d_w, const float* d_bias, void* d_out, int B, int H, int W, int dtype, void* stream);
 int lseg_op_rn_maxpool(const void* d_in, void* d_out, int B, int H, int W, int C, int dtype, void* stream);
 int lseg_op_conv(const void* d_in, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_out, int B, int H, int W,
@@ -517,6 +536,8 @@ int lseg_op_head_block_backward(const float* d_in, const float* d_out_saved, con
  *
  *   lseg_set_train(h, 1)   net.train(): lseg_forward keeps the activations the backward needs, the refinenets' BatchNorm uses batch
  *                          statistics and updates running_mean / running_var IN the caller's bound tensors (momentum 0.1).  bf16 only.
+ *                          ResNet-101 tower (flags bit 5): LSEG_ERR_UNSUPPORTED unless flags bit 6 is set; with it the tower's BatchNorms
+ *                          run on batch statistics too and the step trains scratch.* only (see flags bit 6).
  *                          arch_option 1/2 (head blocks) needs lseg_config.flags bit 4, else LSEG_ERR_UNSUPPORTED.
  *   lseg_bind_grad         where the gradient of parameter `key` is written: fp32, same shape/layout as the bound parameter (the
  *                          caller's .grad tensor, typically a view into a flat bucket).  Unbound parameters get engine-owned buffers

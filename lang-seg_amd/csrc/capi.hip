@@ -644,6 +644,15 @@ int lseg_op_bn_train_forward(const void* d_x_pad, void* d_y_pad, float* d_stats,
     return launch_bn_train_forward(d_x_pad, d_y_pad, d_stats, d_gamma, d_beta, B, H, W, C, eps, DT_BF16, (hipStream_t)stream);
 }
 
+int lseg_op_bn_apply_res(const void* d_x_pad, void* d_y_pad, const float* d_stats, const float* d_gamma, const float* d_beta, const void* d_res_pad,
+                         const float* d_res_stats, const float* d_res_gamma, const float* d_res_beta, int B, int H, int W, int C, float eps,
+                         int relu, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (dtype != LSEG_BF16 && dtype != LSEG_F16) return set_error(LSEG_ERR_INVALID, "lseg_op_bn_apply_res: dtype must be LSEG_BF16 or LSEG_F16");
+    return launch_bn_apply_res(d_x_pad, d_y_pad, d_stats, d_gamma, d_beta, d_res_pad, d_res_stats, d_res_gamma, d_res_beta, B, H, W, C, eps,
+                               (double)B * H * W, relu, dtype == LSEG_F16 ? DT_F16 : DT_BF16, (hipStream_t)stream);
+}
+
 int lseg_op_bn_train_backward(const void* d_dy_pad, const void* d_x_pad, const float* d_stats, const float* d_gamma, void* d_dx_pad,
                               float* d_dgamma_dbeta, int B, int H, int W, int C, float eps, void* stream) {
     int r = require_device(); if (r) return r;

@@ -123,7 +123,7 @@ public:
     int adam_step(double lr_pretrained, double lr_scratch, double beta1, double beta2, double eps, double weight_decay, long long step, hipStream_t st);
     int adam_state(const char* key, int which, float** out, size_t* n);
     int set_frozen_encoder(bool on);
-    int n_buckets() const { return cfg.depth + 1; }
+    int n_buckets() const { return resnet_ ? 1 : cfg.depth + 1; }
     int bucket_of(const std::string& key) const;
     lseg_reduce_fn bn_sync_fn = nullptr; void* bn_sync_user = nullptr; int bn_world = 1;
     lseg_bucket_fn bucket_fn = nullptr; void* bucket_user = nullptr;
@@ -225,8 +225,23 @@ private:
 
     // ---- torchvision ResNet-101 image tower (lseg_config.flags bit 5; resnet.hip, Engine::resnet_forward) ------------------------
     // c1 / c3 / ds: BN-folded 1x1 convs, c2: BN-folded 3x3 conv (stride on it: Bottleneck v1.5)
-    struct RnBlock { Lin c1, c2, c3, ds; int width = 0, stride = 1; bool has_ds = false; };
+    // train mode (flags bit 6): r1 / r2 / r3 / rds = the UNFOLDED convs (bias = zeros_), bn[i] = {gamma, beta} in the caller's bound
+    // tensors, st[i] = [2C] batch sums of bn1 / bn2 / bn3 / downsample.1, key = "pretrained.layerL.J."
+    struct RnBlock {
+        Lin c1, c2, c3, ds; int width = 0, stride = 1; bool has_ds = false;
+        Lin r1, r2, r3, rds;
+        const float *ga[4] = {}, *be[4] = {}; float* st[4] = {};
+        std::string key;
+    };
     bool resnet_ = false;
+    bool rn_train_ = false;                                  // flags bit 6: lseg_set_train is accepted, the decoder above the tower trains
+    float *rs_stem_wraw_ = nullptr, *rs_stem_st_ = nullptr, *ones_ = nullptr;      // stem conv1 unfolded [147][64], its batch sums [128]
+    const float *rs_stem_ga_ = nullptr, *rs_stem_be_ = nullptr;
+    // conv outputs whose batch sums are taken need a zero border of their own geometry: per-stage conv2 / conv3 / downsample outputs
+    uint16_t *rs_t2l_[4] = {}, *rs_c3l_[4] = {}, *rs_dsl_[4] = {};
+    int resnet_forward_train(const float* x, int B, hipStream_t st);
+    int finalize_train_resnet(hipStream_t st);
+    int rn_bn(const uint16_t* x, uint16_t* y, RnBlock& k, int i, const uint16_t* res, int res_bn, int relu, int B, int H, int W, int C, hipStream_t st);
     float *rs_stem_w_ = nullptr, *rs_stem_b_ = nullptr;      // stem conv1 + bn1 folded: fp32 [147][64], [64]
     std::vector<RnBlock> rs_blocks_[4];
     uint16_t *rs_stem_ = nullptr, *rs_pool_ = nullptr;     // stem output (H/2, zero border: the max-pool reads it), max-pool output (H/4)

@@ -80,6 +80,9 @@ int Engine::init() {
     const lseg_config& c = cfg;
     if (c.abi_version != LSEG_ABI_VERSION) return set_error(LSEG_ERR_INVALID, "config abi_version %d != %d", c.abi_version, LSEG_ABI_VERSION);
     resnet_ = (c.flags & 32) != 0;
+    rn_train_ = (c.flags & 64) != 0;
+    if (rn_train_ && !resnet_)
+        return set_error(LSEG_ERR_INVALID, "lseg_config.flags bit 6 (train the decoder above the ResNet-101 tower) needs bit 5 (the ResNet-101 tower)");
     if (resnet_) {
         // torchvision ResNet-101 tower: the ViT fields are ignored; the stages feed scratch.layerN_rn with 256 / 512 / 1024 / 2048 channels
         if (c.image_dtype == LSEG_F16_SPLIT)
@@ -419,7 +422,7 @@ int Engine::finalize(hipStream_t st) {
     const int D = c.dim, F = c.features, P = c.patch;
     char buf[256];
     const std::string vm = "pretrained.model.";
-    if (resnet_) TRY(pack_resnet(st));
+    if (resnet_) { if (!partial_pack_) TRY(pack_resnet(st)); }        // (optimizer step: the tower is not trainable, nothing moved)
     else if (!(partial_pack_ && frozen_)) {      // (optimizer step on a frozen encoder: pretrained.model.* did not move)
         // ---- ViT --------------------------------------------------------------------------------------------
         TRY(pack_linear(vm + "patch_embed.proj.weight", vm + "patch_embed.proj.bias", D, 3 * P * P, img_dt_, patch_, st, true));

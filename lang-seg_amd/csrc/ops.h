@@ -211,7 +211,14 @@ int launch_eval_resize(const float* src, float* dst, int P, int Hi, int Wi, int 
 // ---- resnet.hip: the torchvision ResNet-101 image tower (lseg_config.flags bit 5) ----
 // stem: conv1 7x7/2 pad 3 (3 -> 64) + folded BN + ReLU, fp32 NCHW [B,3,H,W] -> padded NHWC 16-bit [B, Ho+2, Wo+2, 64]; w: fp32 [147][64]
 // (BN-folded, k = (ci*7 + ky)*7 + kx), bias fp32 [64]
-int launch_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, hipStream_t st);
+// relu 0: the raw conv output (train mode: bn1 on batch statistics follows)
+int launch_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, hipStream_t st, int relu = 1);
+// train-mode BatchNorm of the tower on a padded NHWC map [B, H+2, W+2, C] (interior written, border untouched): y = [relu](bn(x) + r) with
+// bn from the batch sums `stats` [2C] over `count` pixels (biased variance); r = 0 (res NULL), res (rstats NULL) or bn_r(res) with sums,
+// gamma and beta of its own.  y may alias x, res may alias y.
+int launch_bn_apply_res(const void* x, void* y, const float* stats, const float* gamma, const float* beta, const void* res, const float* rstats,
+                        const float* rgamma, const float* rbeta, int B, int H, int W, int C, float eps, double count, int relu, int dtype,
+                        hipStream_t st);
 // max-pool 3x3/2 pad 1 on a padded NHWC 16-bit map of NON-NEGATIVE values [B, H+2, W+2, C] -> padded [B, Ho+2, Wo+2, C]
 int launch_rn_maxpool(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t st);
 // BN-folding packers: 1x1 conv weight [Co, Ci] (+ BN) -> [Co, Ci] 16-bit + fp32 bias; stem 7x7 [64, 3, 7, 7] (+ BN) -> fp32 [147][64] + bias

@@ -5,6 +5,8 @@
 // What lives here: the stem (conv1 7x7/2 + bn1 + relu) as a direct fp32 kernel, the 3x3/2 max-pool, and the BN-folding packers.
 // The bottleneck convs themselves run on the GEMM family (gemm.hip implicit conv: ksize 1 | 3, stride 1 | 2, relu_after_res);
 // Engine::resnet_forward strings them together.  Every map is padded NHWC 16-bit (a 1-pixel zero border, as the DPT neck's maps).
+#include <algorithm>
+
 #include "ops.h"
 #include "../../include/lseg_hip.h"
 
@@ -20,6 +22,7 @@ constexpr int STEM_C = 64;
 // adjacent output columns: stride-2 reads that stay within a few cache lines per row).  ~1.1 GFLOP per 480 x 480 image: a small
 // share of the tower's 72 GFLOP.  An im2col + MFMA GEMM would need a [B*Ho*Wo, 192] 16-bit operand
 // (0.8 GB at B = 36) and round the image to 16 bits before the first conv; this keeps the stem in fp32 like the reference.
+template <bool RELU>
 __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                       uint16_t* __restrict__ out, int B, int H, int W, int Ho, int Wo, int dtype) {
     __shared__ float4 ws[STEM_K * STEM_C / 4];
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ 
     for (int c8 = 0; c8 < STEM_C / 8; ++c8) {
         float v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { const float t = acc[c8 * 8 + k] + bs[c8 * 8 + k]; v[k] = t > 0.f ? t : 0.f; }
+        for (int k = 0; k < 8; ++k) { const float t = acc[c8 * 8 + k] + bs[c8 * 8 + k]; v[k] = RELU ? (t > 0.f ? t : 0.f) : t; }
         dst[c8] = make_uint4(pack2_dt(v[0], v[1], dtype), pack2_dt(v[2], v[3], dtype), pack2_dt(v[4], v[5], dtype), pack2_dt(v[6], v[7], dtype));
     }
 }
@@ -124,6 +127,68 @@ __global__ void pack_rn_stem_kernel(const float* w, const float* bn_w, const flo
     }
 }
 
+// Train-mode BatchNorm of the tower on a padded NHWC map, interior pixels only (the zero border stays as it is: conv2's 3x3 window and
+// the next launch_bn_stats read it): y = bn(x) with mean / biased variance from the batch sums `stats` = {sum x, sum x^2} [2C] over
+// 1 / inv_n pixels; RES 1 adds a plain map (the identity of blocks 1..), RES 2 adds a second map normalised with batch sums of its own
+// (block 0's downsample branch); then the optional ReLU.  One lane = one pixel x 8 channels: 16-byte loads and one 16-byte store; the
+// per-channel scale / shift pairs are computed once per thread (the grid stride is a multiple of C / 8 for the tower's power-of-two
+// widths).  y may be x (in place) and res may be y (relu(bn3(t) + x) written over x): each element is read by the lane that then
+// writes it, hence no __restrict__ on the maps.
+template <int RES>
+__global__ __launch_bounds__(256) void rn_bn_apply_res_kernel(const uint16_t* x, uint16_t* y, const float* __restrict__ stats,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta, const uint16_t* res,
+                                                              const float* __restrict__ rstats, const float* __restrict__ rgamma,
+                                                              const float* __restrict__ rbeta, int B, int H, int W, int C, float eps, float inv_n,
+                                                              int relu, int dtype) {
+    const int c8n = C >> 3;
+    const size_t n = (size_t)B * H * W * c8n;
+    const bool fixed_c = ((size_t)gridDim.x * blockDim.x) % c8n == 0;
+    float sc[8], sh[8], rsc[8], rsh[8];
+    auto affine = [&](const float* st, const float* g, const float* b, int c0, float* scale, float* shift) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float4 s1 = *reinterpret_cast<const float4*>(st + c0 + 4 * h), s2 = *reinterpret_cast<const float4*>(st + C + c0 + 4 * h);
+            const float4 g4 = *reinterpret_cast<const float4*>(g + c0 + 4 * h), b4 = *reinterpret_cast<const float4*>(b + c0 + 4 * h);
+            const float a1[4] = {s1.x, s1.y, s1.z, s1.w}, a2[4] = {s2.x, s2.y, s2.z, s2.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float m = a1[k] * inv_n;
+                const float r = gg[k] * rsqrtf(fmaxf(a2[k] * inv_n - m * m, 0.f) + eps);
+                scale[4 * h + k] = r; shift[4 * h + k] = bb[k] - m * r;
+            }
+        }
+    };
+    auto load_c = [&](int c0) {
+        affine(stats, gamma, beta, c0, sc, sh);
+        if (RES == 2) affine(rstats, rgamma, rbeta, c0, rsc, rsh);
+    };
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (fixed_c && i < n) load_c((int)(i % c8n) * 8);
+    for (; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % c8n) * 8;
+        if (!fixed_c) load_c(c0);
+        size_t p = i / c8n;
+        const int xx = (int)(p % W); p /= W;
+        const int yy = (int)(p % H);
+        const int b = (int)(p / H);
+        const size_t off = (((size_t)b * (H + 2) + yy + 1) * (W + 2) + xx + 1) * C + c0;
+        const uint4 ux = *reinterpret_cast<const uint4*>(x + off);
+        uint4 ur = make_uint4(0u, 0u, 0u, 0u);
+        if (RES != 0) ur = *reinterpret_cast<const uint4*>(res + off);
+        const uint16_t *ex = reinterpret_cast<const uint16_t*>(&ux), *er = reinterpret_cast<const uint16_t*>(&ur);
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float t = fmaf(load_as_f32(ex, k, dtype), sc[k], sh[k]);
+            if (RES == 1) t += load_as_f32(er, k, dtype);
+            if (RES == 2) t += fmaf(load_as_f32(er, k, dtype), rsc[k], rsh[k]);
+            v[k] = relu ? fmaxf(t, 0.f) : t;
+        }
+        *reinterpret_cast<uint4*>(y + off) = make_uint4(pack2_dt(v[0], v[1], dtype), pack2_dt(v[2], v[3], dtype), pack2_dt(v[4], v[5], dtype),
+                                                        pack2_dt(v[6], v[7], dtype));
+    }
+}
+
 unsigned grid_of(size_t total) {
     size_t g = (total + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 65535 * 4 ? 65535 * 4 : g));
@@ -131,12 +196,30 @@ unsigned grid_of(size_t total) {
 
 }  // namespace
 
-int launch_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, hipStream_t st) {
+int launch_rn_stem(const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, hipStream_t st, int relu) {
     if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return set_error(LSEG_ERR_INVALID, "rn_stem: B=%d H=%d W=%d (H, W even)", B, H, W);
     if (dtype != DT_BF16 && dtype != DT_F16) return set_error(LSEG_ERR_INVALID, "rn_stem: dtype %d", dtype);
     const int Ho = H / 2, Wo = W / 2;
     const size_t total = (size_t)B * Ho * Wo;
-    hipLaunchKernelGGL(rn_stem_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, bias, (uint16_t*)out, B, H, W, Ho, Wo, dtype);
+    if (relu) hipLaunchKernelGGL(rn_stem_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, bias, (uint16_t*)out, B, H, W, Ho, Wo, dtype);
+    else hipLaunchKernelGGL(rn_stem_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, bias, (uint16_t*)out, B, H, W, Ho, Wo, dtype);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_bn_apply_res(const void* x, void* y, const float* stats, const float* gamma, const float* beta, const void* res, const float* rstats,
+                        const float* rgamma, const float* rbeta, int B, int H, int W, int C, float eps, double count, int relu, int dtype,
+                        hipStream_t st) {
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8) return set_error(LSEG_ERR_INVALID, "bn_apply_res: B=%d H=%d W=%d C=%d (C a multiple of 8)", B, H, W, C);
+    if (dtype != DT_BF16 && dtype != DT_F16) return set_error(LSEG_ERR_INVALID, "bn_apply_res: dtype %d", dtype);
+    if (!x || !y || !stats || !gamma || !beta || !(count > 0)) return set_error(LSEG_ERR_INVALID, "bn_apply_res: NULL pointer / count");
+    if (rstats && (!res || !rgamma || !rbeta)) return set_error(LSEG_ERR_INVALID, "bn_apply_res: a normalised residual needs its map, gamma and beta");
+    const dim3 grid(std::min(grid_of((size_t)B * H * W * (C / 8)), 4096u)), block(256);      // grid-stride: the per-channel affine is computed once per thread
+    const float inv_n = (float)(1.0 / count);
+    const uint16_t *xp = (const uint16_t*)x, *rp = (const uint16_t*)res;
+    if (rstats) hipLaunchKernelGGL(rn_bn_apply_res_kernel<2>, grid, block, 0, st, xp, (uint16_t*)y, stats, gamma, beta, rp, rstats, rgamma, rbeta, B, H, W, C, eps, inv_n, relu, dtype);
+    else if (res) hipLaunchKernelGGL(rn_bn_apply_res_kernel<1>, grid, block, 0, st, xp, (uint16_t*)y, stats, gamma, beta, rp, rstats, rgamma, rbeta, B, H, W, C, eps, inv_n, relu, dtype);
+    else hipLaunchKernelGGL(rn_bn_apply_res_kernel<0>, grid, block, 0, st, xp, (uint16_t*)y, stats, gamma, beta, rp, rstats, rgamma, rbeta, B, H, W, C, eps, inv_n, relu, dtype);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -45,7 +45,9 @@ static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 int Engine::set_train(bool on) {
     if (on) {
-        if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only (no train-mode BatchNorm / bottleneck backward)");
+        // flags bit 6 opts in to training the decoder above the tower (train-mode BatchNorm in the tower, no bottleneck backward)
+        if (resnet_ && !rn_train_)
+            return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only (no train-mode BatchNorm / bottleneck backward)");
         if (img_dt_ != DT_BF16) return set_error(LSEG_ERR_UNSUPPORTED, "training needs bf16 image-tower operands (fp16 gradients underflow)");
         // the head blocks keep n extra [B,K,h,w] fp32 plane sets for their backward: only callers that ask for it (flags bit 4) pay for them
         if (cfg.arch_option != 0 && !(cfg.flags & 16))
@@ -89,6 +91,8 @@ int Engine::bind_grad(const char* key, float* p) {
     auto it = bound_.find(key);
     if (it == bound_.end()) return set_error(LSEG_ERR_MISSING_PARAM, "bind_grad: parameter '%s' was never bound", key);
     if (frozen_ && is_encoder_key(key)) return set_error(LSEG_ERR_INVALID, "bind_grad: '%s' is not trainable (frozen encoder)", key);
+    if (resnet_ && strncmp(key, "pretrained.", 11) == 0)
+        return set_error(LSEG_ERR_INVALID, "bind_grad: '%s' is not trainable (the ResNet-101 tower has no backward)", key);
     GradSlot& s = grads_[key];
     s.ptr = p; s.n = it->second.numel(); s.bound = true;
     optimizer_dirty();
@@ -179,7 +183,12 @@ int Engine::train_alloc() {
         TALLOC(v.r1, uint16_t, Mr * Cp);
         if (c.resample_kind[l] == LSEG_RS_CONV_S2) TALLOC(v.tmp, uint16_t, B * (gh_ + 2) * (gw_ + 2) * Cp);
         const size_t pp = B * (lh_[l] + 2) * (lw_[l] + 2);
-        TALLOC(drn_[l], uint16_t, pp * F); TALLOC(dL_[l], uint16_t, pp * Cp);
+        TALLOC(drn_[l], uint16_t, pp * F);
+        if (!resnet_) TALLOC(dL_[l], uint16_t, pp * Cp);        // (ResNet-101 tower: the backward stops at the stage outputs)
+        if (resnet_) {
+            const size_t wd = (size_t)64 << l;
+            TALLOC(rs_t2l_[l], uint16_t, pp * wd); TALLOC(rs_c3l_[l], uint16_t, pp * 4 * wd); TALLOC(rs_dsl_[l], uint16_t, pp * 4 * wd);
+        }
         TALLOC(dmapA_[l], uint16_t, pp * F); TALLOC(dmapB_[l], uint16_t, pp * F); TALLOC(dmapC_[l], uint16_t, pp * F); TALLOC(dmapD_[l], uint16_t, pp * F);
         for (int u = 0; u < 2; ++u) {
             Rcu& U = u == 0 ? refine_[l].u1 : refine_[l].u2;
@@ -254,11 +263,13 @@ int Engine::finalize_train(hipStream_t st) {
     };
     if (!frozen_) for (auto& b : blocks_) { wts.push_back(&b.qkv); wts.push_back(&b.proj); wts.push_back(&b.fc1); wts.push_back(&b.fc2); }
     for (int l = 0; l < 4; ++l) {
-        if (!frozen_) wts.push_back(&readout_[l]);       // (frozen encoder: the readout's dgrad never runs)
-        wts.push_back(&r1x1_[l]);
-        if (c.resample_kind[l] == LSEG_RS_CONVT) wts.push_back(&rsmp_[l]);
-        else if (c.resample_kind[l] == LSEG_RS_CONV_S2) TRY(make_wd(rsmp_[l], cp_[l], cp_[l]));
-        TRY(make_wd(layer_rn_[l], F, cp_[l]));
+        if (!resnet_) {                                  // (ResNet-101 tower: no reassemble stack, no dgrad below layerN_rn)
+            if (!frozen_) wts.push_back(&readout_[l]);       // (frozen encoder: the readout's dgrad never runs)
+            wts.push_back(&r1x1_[l]);
+            if (c.resample_kind[l] == LSEG_RS_CONVT) wts.push_back(&rsmp_[l]);
+            else if (c.resample_kind[l] == LSEG_RS_CONV_S2) TRY(make_wd(rsmp_[l], cp_[l], cp_[l]));
+            TRY(make_wd(layer_rn_[l], F, cp_[l]));
+        }
         Refine& R = refine_[l];
         wts.push_back(&R.out_conv);
         for (int u = 0; u < 2; ++u) {
@@ -297,7 +308,131 @@ int Engine::finalize_train(hipStream_t st) {
     TRY(launch_transpose16_multi(wt_table_, wt_n_, wt_blocks_, st));
     for (Lin* L : wts)
         if ((L->n & 7) || (L->k & 7)) TRY(launch_transpose16(L->w, L->wt, L->n, L->k, L->k, L->n, st));
+    if (resnet_ && !partial_pack_) TRY(finalize_train_resnet(st));      // (the tower is not trainable: an optimizer step leaves its packs alone)
     if (!partial_pack_) LSEG_HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---- torchvision ResNet-101 tower in train() mode (flags bit 6) --------------------------------------------------------------------
+// The reference trains LSegRNNetZS with the whole module in train(): every one of the tower's 104 BatchNorms normalises with batch
+// statistics and moves its running buffers, whether or not its parameters get a gradient.  Here they get none (the backward stops at
+// the four stage outputs): the tower's intermediate maps are reused as in inference.
+// Unfolded packs: 1x1 convs are the fp32 weights rounded to the operand type as they lie, 3x3 convs and the stem go through the
+// BN-folding packers with no / an identity BatchNorm; gamma / beta are read from the caller's bound tensors.
+int Engine::finalize_train_resnet(hipStream_t st) {
+    if (!ones_) {
+        TALLOC(ones_, float, 64);
+        const std::vector<float> one(64, 1.f);
+        LSEG_HIP_TRY(hipMemcpy(ones_, one.data(), 64 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    auto affine = [&](const std::string& bnp, int C, const float*& g, const float*& b) -> int {
+        BoundParam a, bb;
+        TRY(need(bnp + ".weight", a, {C})); TRY(need(bnp + ".bias", bb, {C}));
+        if (a.dtype != LSEG_F32 || bb.dtype != LSEG_F32) return set_error(LSEG_ERR_UNSUPPORTED, "BatchNorm '%s' must be fp32", bnp.c_str());
+        g = (const float*)a.ptr; b = (const float*)bb.ptr;
+        return 0;
+    };
+    auto raw1 = [&](const std::string& wkey, int co, int ci, Lin& out) -> int {
+        BoundParam w;
+        TRY(need(wkey, w, {co, ci, 1, 1}));
+        if (!out.w) TALLOC(out.w, uint16_t, (size_t)co * ci);
+        out.n = co; out.k = ci; out.b = zeros_;
+        return launch_convert(w.ptr, w.dtype, out.w, img_dt_, (size_t)co * ci, st);
+    };
+    {
+        BoundParam w;
+        TRY(need("pretrained.layer1.0.weight", w, {64, 3, 7, 7}));
+        if (w.dtype != LSEG_F32) return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet stem (pretrained.layer1.0) must be fp32");
+        if (!rs_stem_wraw_) TALLOC(rs_stem_wraw_, float, 147 * 64 + 64);         // [147][64] + the (zero) bias the packer writes
+        if (!rs_stem_st_) TALLOC(rs_stem_st_, float, 128);
+        TRY(launch_pack_rn_stem((const float*)w.ptr, ones_, zeros_, zeros_, ones_, 0.f, rs_stem_wraw_, rs_stem_wraw_ + 147 * 64, st));
+        TRY(affine("pretrained.layer1.1", 64, rs_stem_ga_, rs_stem_be_));
+    }
+    int cin = 64;
+    for (int l = 0; l < 4; ++l) {
+        const int wd = 64 << l;
+        for (size_t j = 0; j < rs_blocks_[l].size(); ++j) {
+            RnBlock& k = rs_blocks_[l][j];
+            char buf[64];
+            if (l == 0) snprintf(buf, sizeof(buf), "pretrained.layer1.4.%d.", (int)j);
+            else snprintf(buf, sizeof(buf), "pretrained.layer%d.%d.", l + 1, (int)j);
+            k.key = buf;
+            TRY(raw1(k.key + "conv1.weight", wd, cin, k.r1));
+            TRY(pack_conv3(k.key + "conv2.weight", "", "", wd, wd, wd, wd, k.r2, st));
+            TRY(raw1(k.key + "conv3.weight", 4 * wd, wd, k.r3));
+            if (k.has_ds) TRY(raw1(k.key + "downsample.0.weight", 4 * wd, cin, k.rds));
+            static const char* bn[4] = {"bn1", "bn2", "bn3", "downsample.1"};
+            for (int i = 0; i < (k.has_ds ? 4 : 3); ++i) {
+                const int C = i < 2 ? wd : 4 * wd;
+                TRY(affine(k.key + bn[i], C, k.ga[i], k.be[i]));
+                if (!k.st[i]) TALLOC(k.st[i], float, 2 * C);
+            }
+            cin = 4 * wd;
+        }
+    }
+    return 0;
+}
+
+// BatchNorm i of block k in train() mode: batch sums of the conv output x (padded map, zero border; with res_bn also of the downsample
+// output `res`), the running-statistics update in the caller's bound tensors (momentum 0.1, unbiased variance: nn.BatchNorm2d), then
+// y = [relu](bn_i(x) [+ res | + bn_d(res)]) in one pass
+int Engine::rn_bn(const uint16_t* x, uint16_t* y, RnBlock& k, int i, const uint16_t* res, int res_bn, int relu, int B, int H, int W, int C,
+                  hipStream_t st) {
+    static const char* bn[4] = {"bn1", "bn2", "bn3", "downsample.1"};
+    const double cnt = (double)B * H * W;
+    auto stats = [&](const uint16_t* map, int which) -> int {
+        float* s = k.st[which];
+        TRY(launch_bn_stats(map, s, B, H, W, C, img_dt_, st, ws_det_ ? 1 : zero_note(zero_fwd_, s, (size_t)2 * C) ? 1 : 0, ws_det_, ws_det_n_));
+        auto m = bound_.find(k.key + bn[which] + ".running_mean"), v = bound_.find(k.key + bn[which] + ".running_var");
+        if (m == bound_.end() || v == bound_.end() || m->second.dtype != LSEG_F32 || v->second.dtype != LSEG_F32) return 0;
+        return launch_bn_running_update(s, (float*)m->second.ptr, (float*)v->second.ptr, C, cnt, 0.1f, st);
+    };
+    TRY(stats(x, i));
+    if (res_bn) TRY(stats(res, 3));
+    return launch_bn_apply_res(x, y, k.st[i], k.ga[i], k.be[i], res, res_bn ? k.st[3] : nullptr, res_bn ? k.ga[3] : nullptr,
+                               res_bn ? k.be[3] : nullptr, B, H, W, C, 1e-5f, cnt, relu, img_dt_, st);
+}
+
+// Engine::resnet_forward with every BatchNorm on batch statistics: conv (unfolded weights, no bias) -> batch sums -> normalise
+// [+ identity] [ReLU].  conv1's output is normalised in place in rs_t1_ / rs_t1in_ (their zero border is conv2's padding), conv2's and
+// conv3's / the downsample's go through per-stage maps with a zero border of their own geometry (the sums run over the padded map);
+// blocks 1.. write relu(bn3(conv3 t) + x) over x = L_[l] as the inference path does.
+int Engine::resnet_forward_train(const float* x, int B, hipStream_t st) {
+    const int H2 = cfg.img_h / 2, W2 = cfg.img_w / 2;
+    TRY(launch_rn_stem(x, rs_stem_wraw_, rs_stem_wraw_ + 147 * 64, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, st, 0));
+    {
+        const double cnt = (double)B * H2 * W2;
+        TRY(launch_bn_stats(rs_stem_, rs_stem_st_, B, H2, W2, 64, img_dt_, st, ws_det_ ? 1 : zero_note(zero_fwd_, rs_stem_st_, 128) ? 1 : 0, ws_det_,
+                            ws_det_n_));
+        auto m = bound_.find("pretrained.layer1.1.running_mean"), v = bound_.find("pretrained.layer1.1.running_var");
+        if (m != bound_.end() && v != bound_.end() && m->second.dtype == LSEG_F32 && v->second.dtype == LSEG_F32)
+            TRY(launch_bn_running_update(rs_stem_st_, (float*)m->second.ptr, (float*)v->second.ptr, 64, cnt, 0.1f, st));
+        // relu(bn1(.)) in place: the max-pool's input stays non-negative (its bit-pattern ordering argument holds)
+        TRY(launch_bn_apply_res(rs_stem_, rs_stem_, rs_stem_st_, rs_stem_ga_, rs_stem_be_, nullptr, nullptr, nullptr, nullptr, B, H2, W2, 64, 1e-5f, cnt,
+                                1, img_dt_, st));
+    }
+    TRY(launch_rn_maxpool(rs_stem_, rs_pool_, B, H2, W2, 64, img_dt_, st));
+    const uint16_t* in = rs_pool_;
+    int h = lh_[0], w = lw_[0];
+    for (int l = 0; l < 4; ++l) {
+        const int wd = 64 << l, ho = lh_[l], wo = lw_[l];
+        for (size_t j = 0; j < rs_blocks_[l].size(); ++j) {
+            RnBlock& k = rs_blocks_[l][j];
+            uint16_t* t1 = (j == 0 && l > 0) ? rs_t1in_[l] : rs_t1_[l];
+            TRY(conv3x3(in, k.r1, nullptr, nullptr, t1, B, h, w, 1, 0, 0, st, nullptr, nullptr, 1, 0));
+            TRY(rn_bn(t1, t1, k, 0, nullptr, 0, 1, B, h, w, wd, st));                                       // relu(bn1(conv1 x))
+            TRY(conv3x3(t1, k.r2, nullptr, nullptr, rs_t2l_[l], B, h, w, k.stride, 0, 0, st));
+            TRY(rn_bn(rs_t2l_[l], rs_t2l_[l], k, 1, nullptr, 0, 1, B, ho, wo, wd, st));                     // relu(bn2(conv2 .))
+            TRY(conv3x3(rs_t2l_[l], k.r3, nullptr, nullptr, rs_c3l_[l], B, ho, wo, 1, 0, 0, st, nullptr, nullptr, 1, 0));
+            if (k.has_ds) {                                                                                 // relu(bn3(conv3 .) + bn_d(downsample.0 x))
+                TRY(conv3x3(in, k.rds, nullptr, nullptr, rs_dsl_[l], B, h, w, k.stride, 0, 0, st, nullptr, nullptr, 1, 0));
+                TRY(rn_bn(rs_c3l_[l], L_[l], k, 2, rs_dsl_[l], 1, 1, B, ho, wo, 4 * wd, st));
+            } else {                                                                                        // relu(bn3(conv3 .) + x), over x
+                TRY(rn_bn(rs_c3l_[l], L_[l], k, 2, L_[l], 0, 1, B, ho, wo, 4 * wd, st));
+            }
+            in = L_[l]; h = ho; w = wo;
+        }
+    }
     return 0;
 }
 
@@ -348,8 +483,16 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     eval_stale_ = true;             // the BatchNorm running statistics move: the eval-mode (BN-folded) packs are refreshed by the next eval forward
     TRY(text_fork(st));
     TRY(zero_begin(zero_fwd_, st));
-    TRY(patch_embed(x_in, sv_[0].xin, B, st));
     GemmArgs g;
+    if (resnet_) {
+        if (bn_sync_fn && bn_world > 1)
+            return set_error(LSEG_ERR_UNSUPPORTED, "synchronised BatchNorm is not implemented for the ResNet-101 tower (per-GPU statistics only)");
+        TRY(resnet_forward_train(x_in, B, st));
+        for (int l = 0; l < 4; ++l)
+            TRY(conv3x3(L_[l], layer_rn_[l], nullptr, nullptr, rn_[l], B, lh_[l], lw_[l], 1, 0, 0, st, rnr_[l], &rn_relu_ok_[l]));
+    } else {
+        TRY(patch_embed(x_in, sv_[0].xin, B, st));
+    }
     for (int i = 0; i < c.depth; ++i) {
         VitBlock& b = blocks_[i];
         BlockSave& s = sv_[i];
@@ -617,7 +760,8 @@ int Engine::refine_backward(int r, int B, int acc, hipStream_t st) {
         d_rn = drn_[l];
     }
     snprintf(buf, sizeof(buf), "scratch.layer%d_rn.weight", r);
-    TRY(conv_bwd(d_rn, L_[l], 0, layer_rn_[l], dL_[l], grad(buf, (size_t)F * cfg.reassemble_ch[l] * 9), B, H, W, cp_[l], F,
+    // (ResNet-101 tower: the weight gradient from the held stage output, no dgrad into the tower)
+    TRY(conv_bwd(d_rn, L_[l], 0, layer_rn_[l], resnet_ ? nullptr : dL_[l], grad(buf, (size_t)F * cfg.reassemble_ch[l] * 9), B, H, W, cp_[l], F,
                  cfg.reassemble_ch[l], F, acc, st));
     return 0;
 }
@@ -797,6 +941,11 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
                 grad("scratch.head1.bias", c.out_c), acc, st));
     // ---- refinenet1..4, reassemble -------------------------------------------------------------------------------------------
     for (int r = 1; r <= 4; ++r) TRY(refine_backward(r, B, acc, st));
+    if (resnet_) {            // the backward stops at the four tower outputs: scratch.* is the whole trainable set, one bucket
+        bucket_done(0, st);
+        if (!acc) TRY(zero_end(zero_bwd_));
+        return 0;
+    }
     for (int l = 0; l < 4; ++l) TRY(reassemble_backward(l, B, acc, st));
     bucket_done(0, st);
     if (frozen_) {

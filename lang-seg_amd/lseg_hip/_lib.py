@@ -113,6 +113,7 @@ SIGNATURES = {
     "lseg_op_attention_backward_qkv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_quickgelu_backward": (_i, [_vp, _vp, _vp, C.c_int64, _i, _vp]),
     "lseg_op_bn_train_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "lseg_op_bn_apply_res": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp]),
     "lseg_op_bn_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_relu_backward": (_i, [_vp, _vp, _vp, C.c_int64, _vp]),
     "lseg_op_upsample2x_planes_backward_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -46,7 +46,8 @@ class _HipMemcpy:
 
 def to_c_config(cfg: LSegConfig, img_h: int, img_w: int, max_batch: int, max_labels: int,
                 image_dtype: str = "bf16", full_text_context: bool = False, exact_head_grad: bool = False,
-                batch_invariant: bool = False, deterministic: bool = False, head_block_training: bool = False) -> _lib.LSegConfigC:
+                batch_invariant: bool = False, deterministic: bool = False, head_block_training: bool = False,
+                train_resnet_decoder: bool = False) -> _lib.LSegConfigC:
     c = _lib.LSegConfigC()
     c.abi_version = _lib.ABI_VERSION
     c.patch, c.dim, c.depth, c.heads = cfg.patch, cfg.dim, cfg.depth, cfg.heads
@@ -67,7 +68,8 @@ def to_c_config(cfg: LSegConfig, img_h: int, img_w: int, max_batch: int, max_lab
     c.image_dtype = {"bf16": _lib.LSEG_BF16, "fp16": _lib.LSEG_F16, "strict": _lib.LSEG_F16_SPLIT}[image_dtype]
     c.flags = ((1 if full_text_context else 0) | (2 if exact_head_grad else 0) | (4 if batch_invariant else 0)
                | (8 if deterministic else 0) | (16 if head_block_training else 0)
-               | (32 if cfg.tower == "resnet101" else 0))          # torchvision ResNet-101 image tower (the ViT fields are ignored)
+               | (32 if cfg.tower == "resnet101" else 0)           # torchvision ResNet-101 image tower (the ViT fields are ignored)
+               | (64 if train_resnet_decoder else 0))              # train the decoder above that tower (lseg_set_train is accepted)
     return c
 
 
@@ -77,13 +79,16 @@ class HipEngine:
     def __init__(self, cfg: LSegConfig, img_h: int, img_w: int, max_batch: int, max_labels: int,
                  device: Optional[torch.device] = None, image_dtype: str = "bf16",
                  full_text_context: bool = False, exact_head_grad: bool = False, batch_invariant: bool = False,
-                 deterministic: Optional[bool] = None, head_block_training: bool = False):
+                 deterministic: Optional[bool] = None, head_block_training: bool = False, train_resnet_decoder: bool = False):
         """deterministic: the training step's column sums (bias gradients, BatchNorm batch statistics) in a fixed order instead of
         fp32 atomics -- the same step twice gives bit-identical gradients (include/lseg_hip.h, flags bit 3).  None = the environment's
         LSEG_DETERMINISTIC, default ON: it costs nothing measurable (tools/train_bench.py, B = 8, two interleaved rounds: 41.0 / 41.2 ms
         with it, 41.2 / 41.2 ms on the atomics -- profiles/r05_train_bench.txt); LSEG_DETERMINISTIC=0 / deterministic=False = atomics.
         head_block_training: let set_train(True) accept arch_option 1/2 and train the head blocks (flags bit 4); it costs
-        max(block_depth - 1, 0) + 1 saved fp32 [max_batch, max_labels, h, w] plane sets."""
+        max(block_depth - 1, 0) + 1 saved fp32 [max_batch, max_labels, h, w] plane sets.
+        train_resnet_decoder: on a ResNet-101 tower config (clip_resnet101), let set_train(True) / enable_training train the decoder
+        above the tower (flags bit 6): the tower runs in train() mode -- batch-statistics BatchNorm, running buffers updated in the bound
+        tensors -- and gets no gradient; scratch.* is the trainable set.  On a ViT config the engine refuses it (LSEG_ERR_INVALID)."""
         import os
         if deterministic is None:
             deterministic = os.environ.get("LSEG_DETERMINISTIC", "1") not in ("", "0")
@@ -96,7 +101,8 @@ class HipEngine:
         self.img_h, self.img_w = img_h, img_w
         self.max_batch, self.max_labels = max_batch, max_labels
         self._c = to_c_config(cfg, img_h, img_w, max_batch, max_labels, image_dtype, full_text_context, exact_head_grad, batch_invariant,
-                               self.deterministic, head_block_training)
+                               self.deterministic, head_block_training, train_resnet_decoder)
+        self.train_resnet_decoder = bool(train_resnet_decoder)
         h = C.c_void_p()
         _lib.check(self.lib.lseg_create(C.byref(self._c), self.device.index or 0, C.byref(h)))
         self._h = h

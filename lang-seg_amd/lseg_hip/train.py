@@ -160,6 +160,9 @@ class DataParallelTrainer:
 
     def __init__(self, engine, state_dict: Dict[str, torch.Tensor], sync_bn: bool = True, group=None):
         self.eng = engine
+        if sync_bn and getattr(engine, "train_resnet_decoder", False):
+            raise NotImplementedError("DataParallelTrainer(sync_bn=True): synchronised BatchNorm is not implemented for the ResNet-101 tower "
+                                      "(cross-rank statistics of its 104 BatchNorms); pass sync_bn=False for per-GPU batch statistics")
         engine.enable_training(state_dict)
         self.exchange = BucketExchange(engine.grad_buckets, group)
         self.world = self.exchange.world

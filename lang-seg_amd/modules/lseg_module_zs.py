@@ -1,7 +1,7 @@
 """LSegModuleZS -- the reference's zero-shot module surface (modules/lseg_module_zs.py:20-73).
 
 `LSegModuleZS(data_path, dataset, batch_size, base_lr, max_epochs, **kwargs)` builds `self.net = LSegNetZS(label_list=...)`
-(`LSegRNNetZS` for backbone="clip_resnet101")
+(`LSegRNNetZS` for backbone="clip_resnet101"; `train_decoder=True` is passed through to it: the decoder above the ResNet-101 tower trains)
 from `label_files/fewshot_<dataset>.txt` (get_labels, :60-71) and forwards `(x, class_info)` to it
 (lsegmentation_module_zs.py:82-83).  Criterion, training_step and configure_optimizers come from LSegmentationModuleZS
 (modules/lsegmentation_module_zs.py), as in the reference, and so do validation_step / validation_epoch_end (the few-shot episode
@@ -26,7 +26,8 @@ class LSegModuleZS(LSegmentationModuleZS):
         if kwargs.get("backbone", "clip_vitl16_384") in ["clip_resnet101"]:         # :33-43
             self.net = LSegRNNetZS(label_list=label_list, backbone=kwargs["backbone"], features=kwargs.get("num_features", 256),
                                    aux=kwargs.get("aux", False), use_pretrained=use_pretrained, arch_option=kwargs.get("arch_option", 0),
-                                   block_depth=kwargs.get("block_depth", 0), activation=kwargs.get("activation", "lrelu"))
+                                   block_depth=kwargs.get("block_depth", 0), activation=kwargs.get("activation", "lrelu"),
+                                   train_decoder=bool(kwargs.get("train_decoder", False)))
         else:
             self.net = LSegNetZS(label_list=label_list, backbone=kwargs.get("backbone", "clip_vitl16_384"),
                                  features=kwargs.get("num_features", 256), aux=kwargs.get("aux", False),

@@ -79,8 +79,10 @@ class _EngineOptimizer:
                 # parameters the backward never reaches (pretrained.model.norm / head, refinenet4.resConfUnit1: DDP's find_unused_parameters
                 # in the reference) sit in the groups without a gradient: torch skips them, and so does the engine
                 ok = trainable and want0 <= groups[0] and want1 <= groups[1] and not (groups[0] & want1) and not (groups[1] & want0)
+                # (a decoder-only ResNet-101 engine: every pretrained.* parameter is in the group, inert -- its .grad stays None)
+                tower = bool(getattr(eng, "train_resnet_decoder", False))
                 ok = ok and all(k is None or k in eng.grads or not k.startswith(("pretrained.", "scratch.")) or self._never_has_grad(k)
-                                for k in (groups[0] | groups[1]))
+                                or (tower and k.startswith("pretrained.")) for k in (groups[0] | groups[1]))
             else:
                 # group 0 is the frozen encoder (no gradients in the engine, nothing to update); groups 1..4 the act_postprocess blocks,
                 # group 5 scratch: together exactly the engine's gradients, apart from what the backward never reaches

@@ -232,7 +232,8 @@ class LSeg(BaseModel):
                                 image_dtype="bf16" if train else self.image_dtype,
                                 exact_head_grad=bool(getattr(self, "exact_head_grad", False)),
                                 batch_invariant=bool(getattr(self, "batch_invariant", False)),
-                                head_block_training=self.cfg.arch_option in (1, 2))
+                                head_block_training=self.cfg.arch_option in (1, 2),
+                                train_resnet_decoder=bool(train and getattr(self, "train_decoder", False)))
                 eng._stamp = None
                 eng._tok = None
                 eng._ts = None
@@ -320,6 +321,9 @@ class LSeg(BaseModel):
             if world > 1 and not self.autograd_grads:
                 ts.exchange = BucketExchange(eng.grad_buckets)
                 eng.set_bucket_callback(ts.exchange.ready)
+            if world > 1 and self.sync_batchnorm and getattr(self, "train_decoder", False):
+                raise NotImplementedError("synchronised BatchNorm is not implemented for the ResNet-101 tower: build the network with "
+                                          "sync_batchnorm=False (per-GPU batch statistics)")
             if world > 1 and self.sync_batchnorm:
                 # SyncBatchNorm (utils.py:34) belongs to the FORWARD/backward arithmetic, not to the gradient exchange: it is installed in
                 # DDP-wrapper mode (autograd_grads=True, Lightning accelerator='ddp' reducing the gradients itself) as well -- there the
@@ -329,7 +333,9 @@ class LSeg(BaseModel):
                 ts.sync_bn = True
             eng._ts = ts
             eng._named = [(k, p) for k, p in self.named_parameters() if k in eng.grads]
-            eng._nbt = [b for k, b in self.named_buffers() if k.endswith("num_batches_tracked") and k.startswith("scratch.")
+            # (LSegRNNetZS(train_decoder=True): the tower's 104 BatchNorms run in train() mode too)
+            nbt_prefix = ("scratch.", "pretrained.") if getattr(eng, "train_resnet_decoder", False) else ("scratch.",)
+            eng._nbt = [b for k, b in self.named_buffers() if k.endswith("num_batches_tracked") and k.startswith(nbt_prefix)
                         and ".refinenet4.resConfUnit1." not in k]
             if eng._carried is not None and eng._carried[0] == "adam":
                 _, state, steps = eng._carried

@@ -12,8 +12,9 @@ as LSegNet's -- and `forward_loss(x, class_info, target)` is criterion(forward(x
 cross-entropy over the 2 label planes, no [B, 2, H, W] logits).
 
 LSegRNNetZS (lseg_net_zs.py:243-363) is the same network on the clip_resnet101 backbone: torchvision's ResNet-101 as the image
-tower (lseg_config.flags bit 5, csrc/resnet.hip), the neck, head and CLIP ViT-B/32 text tower as above.  Inference only: its
-train-mode forward raises.
+tower (lseg_config.flags bit 5, csrc/resnet.hip), the neck, head and CLIP ViT-B/32 text tower as above.  By default it is inference
+only and its train-mode forward raises; LSegRNNetZS(..., train_decoder=True) trains the decoder above the tower (scratch.*) with the
+tower in train() mode: batch-statistics BatchNorm, running buffers updated, no gradient for pretrained.* (their .grad stays None).
 """
 import numpy as np
 from collections import OrderedDict
@@ -165,9 +166,13 @@ class LSegNetZS(LSeg):
 class LSegRNNetZS(LSeg):
     """Zero-shot network on the CLIP-ResNet-101 backbone (lseg_net_zs.py:243-363): the reference's LSegRN module tree
     (clip_pretrained = CLIP ViT-B/32, pretrained.layer1..4 = torchvision ResNet-101, scratch with BN refinenets, head1, output_conv)
-    and `forward(x, class_info) -> float32 [B, 2, H, W]` through the HIP engine.  Inference only."""
+    and `forward(x, class_info) -> float32 [B, 2, H, W]` through the HIP engine.  Inference only unless built with train_decoder=True:
+    then `net.train()` forwards return logits with LSegNetZS's autograd node and `forward_loss` is offered -- the reference's few-shot
+    training step with the `pretrained` group inert: scratch.layerN_rn, the refinenets and head1 get gradients, the tower's BatchNorms
+    normalise with batch statistics and write the running buffers of this module's own nn.BatchNorm2d tensors."""
 
     def __init__(self, label_list=None, path=None, scale_factor=0.5, aux=False, use_relabeled=False, use_pretrained=True, **kwargs):
+        self.train_decoder = bool(kwargs.pop("train_decoder", False))
         if label_list is None:
             raise NotImplementedError("LSegRNNetZS needs a label_list (one ['others', label] token pair per class)")
         features = kwargs["features"] if "features" in kwargs else 256
@@ -186,10 +191,12 @@ class LSegRNNetZS(LSeg):
             self.load(path)
 
     def forward(self, x, class_info):
-        if self.training and torch.is_grad_enabled():
+        if self.training and torch.is_grad_enabled() and not self.train_decoder:
             raise NotImplementedError("LSegRNNetZS is inference only (the ResNet-101 tower has no train-mode BatchNorm / backward): "
                                       "call net.eval() or run under torch.no_grad()")
         return super().forward(x, class_info)
 
     def forward_loss(self, x, class_info, target, ignore_index=-100):
-        raise NotImplementedError("LSegRNNetZS is inference only")
+        if not self.train_decoder:
+            raise NotImplementedError("LSegRNNetZS is inference only")
+        return super().forward_loss(x, class_info, target, ignore_index)
