@@ -483,6 +483,51 @@ int lseg_op_bn_train_backward(const void* d_dy_pad, const void* d_x_pad, const f
                               float* d_dgamma_dbeta, int B, int H, int W, int C, float eps, void* stream);
 int lseg_op_relu_backward(const void* d_dy, const void* d_x, void* d_dx, int64_t n, void* stream);
 
+/* The training backward's data-movement kernels (ViT embedding / readout and the DPT neck's resamplers; autograd in the reference), one
+ * launch each, for the exact operator tests in tests/test_gpu_train_glue.py.  All refuse (LSEG_ERR_INVALID: NULL pointer or a size
+ * below 1; LSEG_ERR_UNSUPPORTED: a channel count the 16-byte lanes cannot cover) before anything is launched.  "16-bit" = bf16 or fp16.
+ *   pos_resize           d_out [1+gh*gw, D] fp32 = row 0 of d_pos [1+g_old^2, D] copied, the g_old x g_old grid resized bilinearly
+ *                        (align_corners=False, lseg_vit.py:149-163).  The source coordinate max(0, (i+0.5)*(g_old/g)-0.5) is
+ *                        evaluated in fp32 as in PyTorch's fp32 resize: it, and so the tap fraction, is off by up to
+ *                        3 * 2^-24 * (src+0.5) absolute (not one rounding of the fraction); the tests hold it to that
+ *   pos_resize_backward  its transpose, d_dposemb [1+g_old^2, D] += ; d_dcls [D] += d_dpos[0] (d cls_token; may be NULL).  Fixed
+ *                        summation order (output y, then x ascending), bit-reproducible
+ *   embed_backward       d_gx [B,ntok,D] fp32 -> d_dtok [B*(ntok-1), D] 16-bit = the patch rows rounded to nearest-even,
+ *                        d_dpos [ntok, D] fp32 = sum over b (b ascending)
+ *   readout_cat          d_x [B,ntok,D] fp32 -> d_cat [B*(ntok-1), 2D] 16-bit = {patch row, cls row} (lseg_vit.py:87-88); D % 8 == 0
+ *   readout_cat_backward d_gx [B,ntok,D] fp32: patch rows += d_dcat[:, :D], cls row += sum_p d_dcat[:, D:] (32 interleaved partial
+ *                        sums over p, then those in order); D % 8 == 0
+ *   unpad_rows           padded NHWC [B,H+2,W+2,C] 16-bit -> rows [B*H*W, C]; C % 8 == 0
+ *   dilate2              d_dy_pad [B,Ho+2,Wo+2,C] (Ho = (H-1)/2+1, Wo alike) -> d_dyd_pad [B,H+2,W+2,C], ALL of it zeroed, then
+ *                        dyd[2y,2x] = dy[y,x]: the stride-2 3x3 conv's backward is the stride-1 one on dyd; C % 8 == 0
+ *   unpixshuf            d_dl_pad [B,gh*s+2,gw*s+2,C] -> d_dg [B*gh*gw, s*s*C], dg[(b,y,x), (i*s+j)*C+c] = dl[b, y*s+i, x*s+j, c]
+ *                        (interior coordinates): the ConvTranspose2d(kernel = stride = s) output as GEMM rows; C % 8 == 0
+ *   pack_convT           ConvTranspose2d weight [Ci,Co,s,s] fp32 -> GEMM weight d_wp [(i*s+j)*Cp+co, Cp(ci)] in `dtype`; only the
+ *                        Ci x Co real entries are written (the caller zeroes the padding once)
+ *   convT_wgrad_unpack   the GEMM weight gradient d_dw [s*s*Cp, Cp] fp32 -> d_dst [C,C,s,s] (= or +=), padded rows / columns ignored
+ *   conv_wgrad_unpack    d_dst OIHW [Co,Ci,3,3] (= or +=) sum over nsplit slabs of tap-major d_dw [Co_p, 9, Cip], slab s at
+ *                        d_dw + s*split_stride (floats), summed s ascending
+ *   fold_rows            d_dst[c] (= or +=) sum_{r<R} d_src[r*ld + c], c < C (the ConvTranspose bias gradient: R = s*s, ld = Cp)
+ *   sum_partials         d_dst[i] (= or +=) sum_{s<nsplit} d_part[s*stride + i], i < n; n and stride multiples of 4
+ *   bn_running_update    train-mode BatchNorm2d's running statistics from d_stats [2C] = {sum x, sum x^2} over `count` elements per
+ *                        channel: rmean = (1-m) rmean + m mean, rvar = (1-m) rvar + m var_unbiased, var = max(E[x^2] - mean^2, 0)
+ *                        * count/(count-1); at count == 1 there is no unbiased estimate and the (zero) biased variance is used */
+int lseg_op_pos_resize(const float* d_pos, float* d_out, int g_old, int gh, int gw, int D, void* stream);
+int lseg_op_pos_resize_backward(const float* d_dpos, float* d_dposemb, float* d_dcls, int g_old, int gh, int gw, int D, void* stream);
+int lseg_op_embed_backward(const float* d_gx, void* d_dtok, float* d_dpos, int B, int ntok, int D, int dtype, void* stream);
+int lseg_op_readout_cat(const float* d_x, void* d_cat, int B, int ntok, int D, int dtype, void* stream);
+int lseg_op_readout_cat_backward(const void* d_dcat, float* d_gx, int B, int ntok, int D, int dtype, void* stream);
+int lseg_op_unpad_rows(const void* d_in_pad, void* d_rows, int B, int H, int W, int C, void* stream);
+int lseg_op_dilate2(const void* d_dy_pad, void* d_dyd_pad, int B, int H, int W, int C, void* stream);
+int lseg_op_unpixshuf(const void* d_dl_pad, void* d_dg, int B, int gh, int gw, int s, int C, void* stream);
+int lseg_op_pack_convT(const float* d_w, void* d_wp, int Ci, int Co, int Cp, int s, int dtype, void* stream);
+int lseg_op_convT_wgrad_unpack(const float* d_dw, float* d_dst, int C, int Cp, int s, int accumulate, void* stream);
+int lseg_op_conv_wgrad_unpack(const float* d_dw, float* d_dst, int Co, int Ci, int Cip, int accumulate, int nsplit, size_t split_stride,
+                              void* stream);
+int lseg_op_fold_rows(const float* d_src, float* d_dst, int R, int C, int ld, int accumulate, void* stream);
+int lseg_op_sum_partials(const float* d_part, float* d_dst, int nsplit, size_t n, size_t stride, int accumulate, void* stream);
+int lseg_op_bn_running_update(const float* d_stats, float* d_rmean, float* d_rvar, int C, double count, float momentum, void* stream);
+
 /* Head-side backward bricks (lseg_net.py:185-203 under autograd):
  *   upsample2x_planes_backward_rows  d_dout [B,K,2H,2W] fp32 (d of the output logits) -> d_rows [B*H*W, ldk] bf16/fp16, columns
  *                                    0..K-1 (the rest pre-zeroed by the caller): transpose of output_conv's x2 bilinear, already in

@@ -666,6 +666,116 @@ int lseg_op_relu_backward(const void* d_dy, const void* d_x, void* d_dx, int64_t
     return launch_relu_backward(d_dy, d_x, d_dx, (size_t)n, (hipStream_t)stream);
 }
 
+// ---- the training backward's data-movement ("glue") kernels, one launch each: what the whole-network runs reach only through 24 bf16
+// blocks is checked exactly (tests/test_gpu_train_glue.py).  Every wrapper refuses what its kernel cannot do and launches nothing.
+static int glue_dt16(int lseg_dt, int* out, const char* who) {
+    if (lseg_dt == LSEG_F16) { *out = DT_F16; return 0; }
+    if (lseg_dt == LSEG_BF16) { *out = DT_BF16; return 0; }
+    return set_error(LSEG_ERR_INVALID, "%s: dtype must be LSEG_BF16 or LSEG_F16", who);
+}
+
+int lseg_op_pos_resize(const float* d_pos, float* d_out, int g_old, int gh, int gw, int D, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_pos || !d_out || g_old < 1 || gh < 1 || gw < 1 || D < 1) return set_error(LSEG_ERR_INVALID, "pos_resize: bad arguments");
+    return launch_pos_resize(d_pos, d_out, g_old, gh, gw, D, (hipStream_t)stream);
+}
+
+int lseg_op_pos_resize_backward(const float* d_dpos, float* d_dposemb, float* d_dcls, int g_old, int gh, int gw, int D, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_dpos || !d_dposemb || g_old < 1 || gh < 1 || gw < 1 || D < 1) return set_error(LSEG_ERR_INVALID, "pos_resize_backward: bad arguments");
+    return launch_pos_resize_bwd(d_dpos, d_dposemb, d_dcls, g_old, gh, gw, D, (hipStream_t)stream);
+}
+
+int lseg_op_embed_backward(const float* d_gx, void* d_dtok, float* d_dpos, int B, int ntok, int D, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = glue_dt16(dtype, &dt, "embed_backward"))) return r;
+    if (!d_gx || !d_dtok || !d_dpos || B < 1 || ntok < 2 || D < 1) return set_error(LSEG_ERR_INVALID, "embed_backward: bad arguments (ntok >= 2)");
+    return launch_embed_bwd(d_gx, d_dtok, d_dpos, B, ntok, D, dt, (hipStream_t)stream);
+}
+
+int lseg_op_readout_cat(const float* d_x, void* d_cat, int B, int ntok, int D, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = glue_dt16(dtype, &dt, "readout_cat"))) return r;
+    if (!d_x || !d_cat || B < 1 || ntok < 2 || D < 1) return set_error(LSEG_ERR_INVALID, "readout_cat: bad arguments (ntok >= 2)");
+    if (D % 8) return set_error(LSEG_ERR_UNSUPPORTED, "readout_cat: D=%d must be a multiple of 8", D);
+    return launch_readout_cat(d_x, d_cat, B, ntok, D, dt, (hipStream_t)stream);
+}
+
+int lseg_op_readout_cat_backward(const void* d_dcat, float* d_gx, int B, int ntok, int D, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = glue_dt16(dtype, &dt, "readout_cat_backward"))) return r;
+    if (!d_dcat || !d_gx || B < 1 || ntok < 2 || D < 1) return set_error(LSEG_ERR_INVALID, "readout_cat_backward: bad arguments (ntok >= 2)");
+    if (D % 8) return set_error(LSEG_ERR_UNSUPPORTED, "readout_cat_backward: D=%d must be a multiple of 8", D);
+    return launch_readout_cat_bwd(d_dcat, d_gx, B, ntok, D, dt, (hipStream_t)stream);
+}
+
+int lseg_op_unpad_rows(const void* d_in_pad, void* d_rows, int B, int H, int W, int C, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_in_pad || !d_rows || B < 1 || H < 1 || W < 1 || C < 1) return set_error(LSEG_ERR_INVALID, "unpad_rows: bad arguments");
+    if (C % 8) return set_error(LSEG_ERR_UNSUPPORTED, "unpad_rows: C=%d must be a multiple of 8", C);
+    return launch_unpad_rows(d_in_pad, d_rows, B, H, W, C, (hipStream_t)stream);
+}
+
+int lseg_op_dilate2(const void* d_dy_pad, void* d_dyd_pad, int B, int H, int W, int C, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_dy_pad || !d_dyd_pad || B < 1 || H < 1 || W < 1 || C < 1) return set_error(LSEG_ERR_INVALID, "dilate2: bad arguments");
+    if (C % 8) return set_error(LSEG_ERR_UNSUPPORTED, "dilate2: C=%d must be a multiple of 8", C);
+    return launch_dilate2(d_dy_pad, d_dyd_pad, B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, H, W, C, (hipStream_t)stream);
+}
+
+int lseg_op_unpixshuf(const void* d_dl_pad, void* d_dg, int B, int gh, int gw, int s, int C, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_dl_pad || !d_dg || B < 1 || gh < 1 || gw < 1 || s < 1 || C < 1) return set_error(LSEG_ERR_INVALID, "unpixshuf: bad arguments");
+    if (C % 8) return set_error(LSEG_ERR_UNSUPPORTED, "unpixshuf: C=%d must be a multiple of 8", C);
+    return launch_unpixshuf(d_dl_pad, d_dg, B, gh, gw, s, C, (hipStream_t)stream);
+}
+
+int lseg_op_pack_convT(const float* d_w, void* d_wp, int Ci, int Co, int Cp, int s, int dtype, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (!d_w || !d_wp || Ci < 1 || Co < 1 || s < 1 || Cp < Ci || Cp < Co) return set_error(LSEG_ERR_INVALID, "pack_convT: bad arguments (Cp >= Ci, Co)");
+    return launch_pack_convT(d_w, d_wp, Ci, Co, Cp, s, dt, (hipStream_t)stream);
+}
+
+int lseg_op_convT_wgrad_unpack(const float* d_dw, float* d_dst, int C, int Cp, int s, int accumulate, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_dw || !d_dst || C < 1 || s < 1 || Cp < C) return set_error(LSEG_ERR_INVALID, "convT_wgrad_unpack: bad arguments (Cp >= C)");
+    return launch_convT_wgrad_unpack(d_dw, d_dst, C, Cp, s, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
+int lseg_op_conv_wgrad_unpack(const float* d_dw, float* d_dst, int Co, int Ci, int Cip, int accumulate, int nsplit, size_t split_stride,
+                              void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_dw || !d_dst || Co < 1 || Ci < 1 || Cip < Ci || nsplit < 1) return set_error(LSEG_ERR_INVALID, "conv_wgrad_unpack: bad arguments (Cip >= Ci)");
+    if (nsplit > 1 && split_stride < (size_t)Co * 9 * Cip)
+        return set_error(LSEG_ERR_INVALID, "conv_wgrad_unpack: split_stride=%zu is smaller than one slab", split_stride);
+    return launch_conv_wgrad_unpack(d_dw, d_dst, Co, Ci, Cip, accumulate ? 1 : 0, (hipStream_t)stream, nsplit, split_stride);
+}
+
+int lseg_op_fold_rows(const float* d_src, float* d_dst, int R, int C, int ld, int accumulate, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_src || !d_dst || R < 1 || C < 1 || ld < C) return set_error(LSEG_ERR_INVALID, "fold_rows: R, C >= 1, ld >= C");
+    return launch_fold_rows(d_src, d_dst, R, C, ld, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
+int lseg_op_sum_partials(const float* d_part, float* d_dst, int nsplit, size_t n, size_t stride, int accumulate, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_part || !d_dst || nsplit < 1 || n < 1) return set_error(LSEG_ERR_INVALID, "sum_partials: bad arguments");
+    if ((n & 3) || (stride & 3)) return set_error(LSEG_ERR_INVALID, "sum_partials: n and stride must be multiples of 4");
+    if (nsplit > 1 && stride < n) return set_error(LSEG_ERR_INVALID, "sum_partials: stride=%zu is smaller than n=%zu", stride, n);
+    return launch_sum_partials(d_part, d_dst, nsplit, n, stride, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
+int lseg_op_bn_running_update(const float* d_stats, float* d_rmean, float* d_rvar, int C, double count, float momentum, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_stats || !d_rmean || !d_rvar || C < 1 || !(count >= 1.0)) return set_error(LSEG_ERR_INVALID, "bn_running_update: C >= 1, count >= 1");
+    return launch_bn_running_update(d_stats, d_rmean, d_rvar, C, count, momentum, (hipStream_t)stream);
+}
+
 int lseg_op_upsample2x_planes_backward_rows(const float* d_dout, void* d_rows, int B, int K, int H, int W, int ldk, int out_dtype,
                                             void* stream) {
     int r = require_device(); if (r) return r;

@@ -132,6 +132,20 @@ SIGNATURES = {
     "lseg_op_softmax_ce_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lseg_op_conv3x3_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_layernorm_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "lseg_op_pos_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_pos_resize_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_embed_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_readout_cat": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_readout_cat_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_unpad_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_dilate2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_unpixshuf": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_pack_convT": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_convT_wgrad_unpack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_conv_wgrad_unpack": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _sz, _vp]),
+    "lseg_op_fold_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_sum_partials": (_i, [_vp, _vp, _i, _sz, _sz, _i, _vp]),
+    "lseg_op_bn_running_update": (_i, [_vp, _vp, _vp, _i, C.c_double, _f, _vp]),
 }
 
 # callback types of the training step (include/lseg_hip.h: lseg_reduce_cb, lseg_bucket_cb)
