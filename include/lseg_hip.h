@@ -195,6 +195,17 @@ int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out
  * LSEG_ERR_STATE until another forward has run.  K > 32767, train mode: LSEG_ERR_UNSUPPORTED. */
 int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, void* stream);
 
+/* The logits BEFORE scratch.output_conv (lseg_net.py:203), for callers that read them through the x2 bilinear themselves (the
+ * multi-scale evaluator's lseg_op_eval_accumulate_lowres): the inference forward exactly as lseg_forward runs it -- text cache, external
+ * text features, per-image label sets (Kout = labels per image), overflow sentinel, profiling and the arch_option 1/2 head blocks
+ * included -- with no [B,K,img_h,img_w] tensor written.
+ *   dev_low_out    fp32 [B, Kout, img_h/2, img_w/2]: lseg_op_upsample2x_planes of it is bit-identical to the logits lseg_forward writes
+ *                  for the same input (34.6 MB per image at K = 150, crop 480, instead of 138 MB)
+ * On the commuted schedule without head blocks the planes are formed straight in dev_low_out; the other schedules hold them in engine
+ * memory and copy them out.  Afterwards the engine is in the state an lseg_forward leaves: lseg_forward_stats, lseg_episode_stats and
+ * the "lowres" tap work.  Train mode: LSEG_ERR_UNSUPPORTED; a NULL output: LSEG_ERR_INVALID. */
+int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream);
+
 /* The metric / loss step after the path, without the full-resolution logits: statistics of the LAST lseg_forward's output against a
  * target mask -- replaces batch_pix_accuracy + batch_intersection_union on `pred` (lsegmentation_module.py:49-50,59-60) and the value
  * of the criterion (:72).  dev_target int64 [B,img_h,img_w]; dev_counts / dev_nll as in lseg_op_seg_stats. */
@@ -424,6 +435,14 @@ int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int heigh
 int lseg_op_eval_accumulate(const float* d_outs, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
                             int h_grids, int w_grids, int flip, void* stream);
 int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, void* stream);
+/* lseg_op_eval_accumulate on the logits lseg_forward_lowres leaves: d_low fp32 [(1+flip)*n, K, crop/2, crop/2] is read through
+ * output_conv's x2 bilinear (align_corners=True) on the fly, so the [(1+flip)*n, K, crop, crop] stack never exists.  Defined as -- and
+ * bit-identical to -- lseg_op_eval_accumulate(lseg_op_upsample2x_planes(d_low)): per covering box in (idh,idw) order
+ * v = up(low_b)[y-h0, x-w0] (+ up(low_twin_b)[y-h0, crop-1-(x-w0)], the twin's tap taken at the mirrored full-resolution coordinate),
+ * acc += v, then acc / count.  crop even and >= 4.  Arguments are checked before the device is touched: LSEG_ERR_INVALID for NULLs, an
+ * odd or too small crop, or boxes that do not cover the map. */
+int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                   int h_grids, int w_grids, int flip, void* stream);
 
 /* Backward of one Linear layer y = x W^T + b -- first brick of the training step (the reference gets
  * it from torch autograd under LSegmentationModule.training_step, lsegmentation_module.py:66-81).  bf16/fp16 operands,

@@ -98,6 +98,12 @@ int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_l
     return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out);
 }
 
+int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream) {
+    GUARD(h);
+    if (!dev_low_out) return set_error(LSEG_ERR_INVALID, "low-resolution logits output is NULL");
+    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, dev_low_out);
+}
+
 int lseg_forward_stats(lseg_handle h, const int64_t* dev_target, int ignore_index, int64_t* dev_counts, double* dev_nll, void* stream) {
     GUARD(h);
     return h->e->forward_stats(dev_target, ignore_index, dev_counts, dev_nll, (hipStream_t)stream);
@@ -481,6 +487,17 @@ int lseg_op_eval_accumulate(const float* d_outs, float* d_map, int K, int height
         (h_grids - 1) * stride + crop < ph || (w_grids - 1) * stride + crop < pw)
         return set_error(LSEG_ERR_INVALID, "eval_accumulate: the boxes do not cover the %dx%d map", ph, pw);
     return launch_eval_accumulate(d_outs, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
+}
+int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                   int h_grids, int w_grids, int flip, void* stream) {
+    if (!d_low || !d_map) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: NULL pointer");
+    if (crop < 4 || (crop & 1)) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: crop=%d must be even and >= 4 (the planes are crop/2 x crop/2)", crop);
+    if (K < 1 || height < 1 || width < 1 || height > ph || width > pw || stride < 1 || h_grids < 1 || w_grids < 1 ||
+        (long long)(h_grids - 1) * stride + crop < ph || (long long)(w_grids - 1) * stride + crop < pw)
+        return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: the boxes do not cover the %dx%d map", ph, pw);
+    if (((uintptr_t)d_low | (uintptr_t)d_map) & 3) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: pointers must be 4-byte aligned");
+    int r = require_device(); if (r) return r;
+    return launch_eval_accumulate_lowres(d_low, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
 }
 int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, void* stream) {
     int r = require_device(); if (r) return r;

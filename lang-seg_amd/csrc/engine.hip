@@ -939,7 +939,8 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
     return ns;
 }
 
-int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out) {
+int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
+                    float* low_out) {
     if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
     if (K_ < 1) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
@@ -951,6 +952,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     if (train_mode) {                    // net.train(): activations saved for lseg_backward, BatchNorm on batch statistics
         if (label_out) return set_error(LSEG_ERR_UNSUPPORTED, "label output is an inference feature (train mode is on)");
         if (argmax_out) return set_error(LSEG_ERR_UNSUPPORTED, "argmax output is an inference feature (train mode is on)");
+        if (low_out) return set_error(LSEG_ERR_UNSUPPORTED, "low-resolution logits output is an inference feature (train mode is on)");
         return forward_train(x_in, B, logits, st);
     }
     if (eval_stale_) TRY(finalize(st));  // optimizer steps refresh only the train-mode packs: fold BatchNorm / the commuted head again
@@ -1115,6 +1117,14 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
         }
+        // lseg_forward_lowres with nothing else wanted: the (2h, 2w) logits go straight into the caller's buffer; low_ stays pending, as
+        // after the one-pass x4 upsample (forward_stats / episode_stats / the "lowres" tap make it on demand from the same R and scale plane)
+        if (low_out && !logits && !argmax_out && !label_out && c.arch_option == 0) {
+            TRY(launch_upsample2x_planes_scaled(rpl_, nscale_, low_out, B * kk, kk, lh_[0], lw_[0], st));
+            last_low_ = low_; last_kout_ = kk;
+            prof_end(PF_FWD, fwd0, 0.0, st);
+            return 0;
+        }
         TRY(materialize_low(st));
     } else if (commuted) {
         // g = Wc t2 + bc on every row of the padded map (border rows are never read), fp32; then x2 bilinear + L2-norm + fp16 casts
@@ -1166,6 +1176,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     if (label_out) TRY(launch_seg_argmax16(low, B, Kout, h1, w1, label_out, score_out, st));      // the int16 form, on the planes in memory
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
     if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
+    // every other schedule (head blocks, the full-resolution correlation, debug / split-precision) has them in engine memory: a copy
+    if (low_out) LSEG_HIP_TRY(hipMemcpyAsync(low_out, low, (size_t)B * Kout * hw1 * sizeof(float), hipMemcpyDeviceToDevice, st));
     prof_end(PF_FWD, fwd0, 0.0, st);
     return 0;
 }

@@ -62,6 +62,112 @@ __global__ void eval_accumulate_kernel(const float* __restrict__ outs, float* __
     }
 }
 
+// The same from the (crop/2, crop/2) logits the engine holds before output_conv (lseg_forward_lowres): low [(1 + flip) * n, K, hl, hl],
+// hl = crop / 2, read through output_conv's x2 bilinear on the fly -- src_tap / bilerp (common.h), the arithmetic of upsample2x_planes_kernel,
+// so every value is the bit pattern eval_accumulate_kernel would have read from the materialised stack; the sum over the covering boxes
+// runs in the same (idh, idw) order from the same 0.f, and the division is the same.  The twin's value is the tap of the MIRRORED
+// full-resolution column crop - 1 - (x - w0) on the twin's planes (mirroring a value interpolated at x would round differently).
+//
+// One wave per output row (k, y), four rows per block; a lane produces runs of four consecutive x.  The runs are shifted so that
+// every interior one is a 16-byte aligned store whatever the width and the map's offset (the row's first / last run are partial: scalar
+// stores).  Per row, once and wave-uniform: the covering idh range and, per idh, the two source rows and ly.  Per run and covering
+// box: the eight taps of the four outputs lie in four consecutive low-resolution columns (r < 1/2: four consecutive outputs advance
+// the left tap by at most 2), so two rows x four columns are loaded once and feed all four outputs; likewise for the twin, whose
+// columns run backwards.  Bytes read per crop fall 4x against the full-resolution form and stay in L1 / L2 across neighbouring runs.
+__device__ __forceinline__ float pick4(const float (&w)[4], int j) { return j == 0 ? w[0] : (j == 1 ? w[1] : (j == 2 ? w[2] : w[3])); }
+
+// up(plane)[row taps ra / rb, ly][columns xl[0..3]]: xl non-decreasing (rev = 0) or non-increasing (rev = 1), neighbours at most 1 apart
+__device__ __forceinline__ void taps4(const float* __restrict__ ra, const float* __restrict__ rb, const int (&xl)[4], float r, int hl, float ly,
+                                      int rev, float (&v)[4]) {
+    int x0[4], x1[4];
+    float lx[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) src_tap(r, xl[e], hl, x0[e], x1[e], lx[e]);
+    const int c = rev ? x0[3] : x0[0];                   // the leftmost tap of the run; every other one is in [c, c + 3]
+    float wa[4], wb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = min(c + j, hl - 1);
+        wa[j] = ra[col];
+        wb[j] = rb[col];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        v[e] = bilerp(pick4(wa, x0[e] - c), pick4(wa, x1[e] - c), pick4(wb, x0[e] - c), pick4(wb, x1[e] - c), lx[e], ly);
+}
+
+__global__ __launch_bounds__(256) void eval_accumulate_lowres_kernel(const float* __restrict__ low, float* __restrict__ outputs, int K, int height,
+                                                                     int width, int crop, int stride, int h_grids, int w_grids, int flip) {
+    const int hl = crop >> 1;
+    const size_t rows = (size_t)K * height;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int k = (int)((unsigned)row / (unsigned)height);              // rows < 2^31 (launcher)
+    const int y = (int)((unsigned)row - (unsigned)k * (unsigned)height);
+    const float r = (float)(hl - 1) / (float)(crop - 1);              // upsample2x_planes_kernel's ry = rx for a (hl, hl) plane
+    const size_t plane = (size_t)hl * hl;
+    const size_t twin = (size_t)h_grids * w_grids * K * plane;
+    // covering boxes of the row: idh * stride <= y < idh * stride + crop (y < height <= ph: the clip to ph never cuts a map row)
+    const int h_lo = y < crop ? 0 : (y - crop) / stride + 1;
+    const int h_hi = min(y / stride, h_grids - 1);
+    float* orow = outputs + row * (size_t)width;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(orow) >> 2) & 3);      // run q covers x = 4 q - shift .. + 3
+    const int nq = (width + shift + 3) >> 2;
+    for (int q = lane; q < nq; q += 64) {
+        const int xb = 4 * q - shift;
+        int xs[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xs[e] = min(max(xb + e, 0), width - 1);     // partial runs compute a neighbour's value and do not store it
+        const int w_lo = xs[0] < crop ? 0 : (xs[0] - crop) / stride + 1;
+        const int w_hi = min(xs[3] / stride, w_grids - 1);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        int cnt[4] = {0, 0, 0, 0};
+        for (int idh = h_lo; idh <= h_hi; ++idh) {
+            int y0, y1;
+            float ly;
+            src_tap(r, y - idh * stride, hl, y0, y1, ly);
+            y0 = min(y0, hl - 1); y1 = min(y1, hl - 1);
+            for (int idw = w_lo; idw <= w_hi; ++idw) {
+                const int w0 = idw * stride;
+                const float* p = low + ((size_t)(idh * w_grids + idw) * K + k) * plane;
+                int xl[4];
+                bool in[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    in[e] = xs[e] >= w0 && xs[e] < w0 + crop;
+                    xl[e] = min(max(xs[e] - w0, 0), crop - 1);
+                }
+                float v[4];
+                taps4(p + (size_t)y0 * hl, p + (size_t)y1 * hl, xl, r, hl, ly, 0, v);
+                if (flip) {
+                    int xm[4];
+                    float t[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xm[e] = crop - 1 - xl[e];
+                    taps4(p + twin + (size_t)y0 * hl, p + twin + (size_t)y1 * hl, xm, r, hl, ly, 1, t);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] += t[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (in[e]) { acc[e] += v[e]; cnt[e] += 1; }
+            }
+        }
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = acc[e] / (float)cnt[e];
+        if (xb >= 0 && xb + 3 < width) {
+            const f32x4_t ov = {o[0], o[1], o[2], o[3]};
+            *reinterpret_cast<f32x4_t*>(orow + xb) = ov;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (xb + e >= 0 && xb + e < width) orow[xb + e] = o[e];
+        }
+    }
+}
+
 // dst [P, Ho, Wo] (+)= bilinear(src [P, Hi, Wi]), align_corners=True (F.interpolate / upsample_bilinear2d's arithmetic)
 __global__ void eval_resize_kernel(const float* __restrict__ src, float* __restrict__ dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate) {
     const size_t total = (size_t)P * Ho * Wo;
@@ -100,6 +206,15 @@ int launch_eval_accumulate(const float* outs, float* outputs, int K, int height,
                            int w_grids, int flip, hipStream_t st) {
     hipLaunchKernelGGL(eval_accumulate_kernel, dim3(grid_for((size_t)K * height * width)), dim3(256), 0, st, outs, outputs, K, height, width,
                        ph, pw, crop, stride, h_grids, w_grids, flip);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                  int h_grids, int w_grids, int flip, hipStream_t st) {
+    const size_t rows = (size_t)K * height;
+    if (rows > 0x7fffffffu) return set_error(LSEG_ERR_UNSUPPORTED, "eval_accumulate_lowres: too many rows");
+    hipLaunchKernelGGL(eval_accumulate_lowres_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, low, outputs, K, height, width, crop,
+                       stride, h_grids, w_grids, flip);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }

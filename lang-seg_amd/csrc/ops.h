@@ -206,6 +206,8 @@ int launch_eval_make_crops(const float* img, float* crops, int C, int height, in
                            int flip, const float* pad3, hipStream_t st);
 int launch_eval_accumulate(const float* outs, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
                            int w_grids, int flip, hipStream_t st);
+int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                  int h_grids, int w_grids, int flip, hipStream_t st);
 int launch_eval_resize(const float* src, float* dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, hipStream_t st);
 
 // ---- resnet.hip: the torchvision ResNet-101 image tower (lseg_config.flags bit 5) ----

@@ -60,6 +60,7 @@ SIGNATURES = {
     "lseg_overflow_seen": (_i, [_vp, _i]),
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "lseg_forward_lowres": (_i, [_vp, _vp, _i, _vp, _vp]),
     "lseg_forward_stats": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_episode_stats": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_get_intermediate": (_i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
@@ -120,6 +121,7 @@ SIGNATURES = {
     "lseg_op_upsample_ce_backward_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "lseg_op_eval_make_crops": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "lseg_op_eval_accumulate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_eval_accumulate_lowres": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_l2norm_scale_backward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "lseg_op_corr_group_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -207,6 +207,18 @@ class HipEngine:
         self._raise_callback_error()
         return (lab, score) if want_score else lab
 
+    def forward_lowres(self, x: torch.Tensor) -> torch.Tensor:
+        """fp32 [B,Kout,H/2,W/2]: the logits before output_conv's x2 bilinear (lseg_forward_lowres) -- lseg_op_upsample2x_planes of them is
+        bit-identical to forward(x); the [B,Kout,H,W] tensor is never written."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        Kout = self._group if self._group > 0 else self._K
+        low = torch.empty((B, Kout, H // 2, W // 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lseg_forward_lowres(self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(low.data_ptr()),
+                                                C.c_void_p(_stream_ptr(self.device))))
+        self._raise_callback_error()
+        return low
+
     def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):
         x = self._check_input(x)
         B, Cc, H, W = x.shape

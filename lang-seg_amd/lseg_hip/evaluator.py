@@ -10,6 +10,8 @@ schedule.  The data movement around the forwards -- resize / pad / crop / flip /
 the device in three kernels per scale (csrc/evaluator.hip through the C ABI: lseg_op_eval_make_crops / _accumulate /
 _resize) when the image lives on the GPU; the torch statement of the same steps below is the definition they are tested
 against and what runs for host tensors (tests/test_evaluator_ref_golden.py drives it with a toy module on the CPU).
+With lowres=True the forwards stop before the network's x2 output_conv and lseg_op_eval_accumulate_lowres reads the (crop/2, crop/2)
+logits through that bilinear on the fly: the same scores bit for bit, a quarter of the logits in memory (DESIGN par. 3.8).
 """
 import ctypes as C
 import math
@@ -67,6 +69,12 @@ class ModuleSurface(torch.nn.Module):
     def evaluate_random(self, x, labelset, target=None):
         return self.net(x, labelset)
 
+    def evaluate_lowres(self, x):
+        return self.net.forward_lowres(x)
+
+    def evaluate_random_lowres(self, x, labelset):
+        return self.net.forward_lowres(x, labelset)
+
 
 class BatchedMultiEval(torch.nn.Module):
     """Drop-in for `MultiEvalModule(module, nclass, scales=..., flip=...)` on one GPU.
@@ -74,8 +82,12 @@ class BatchedMultiEval(torch.nn.Module):
     `module` needs .evaluate(x) / .evaluate_random(x, labels), .base_size, .crop_size, .mean, .std,
     ._up_kwargs (the LSegModule surface, modules/lseg_module.py:29-93)."""
 
-    def __init__(self, module, nclass, flip=True, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), max_batch=36, cache_text=True):
-        """cache_text: encode a label set ONCE per evaluator call chain instead of once per crop batch (the reference re-runs the CLIP text
+    def __init__(self, module, nclass, flip=True, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), max_batch=36, cache_text=True, lowres=False):
+        """lowres: (device images only) the forwards stop before the network's output_conv (module.evaluate_lowres /
+        evaluate_random_lowres -> fp32 [n, K, crop/2, crop/2]) and lseg_op_eval_accumulate_lowres reads those logits through the x2 bilinear
+        on the fly: the same scores bit for bit, a quarter of the logits written, read and alive (DESIGN par. 3.8).  The module must
+        offer both *_lowres methods: there is no fallback to the full-resolution path.
+        cache_text: encode a label set ONCE per evaluator call chain instead of once per crop batch (the reference re-runs the CLIP text
         tower inside every one of its ~36 forwards per image, lseg_net.py:183 -- the same tokens through the same frozen weights: exact).
         Applied to the wrapped network (`module.net`, an LSegNet) for the duration of a forward and restored afterwards; the engine
         re-encodes whenever the tokens or the weights change (LSegNet._set_tokens / _stamp)."""
@@ -88,6 +100,14 @@ class BatchedMultiEval(torch.nn.Module):
         self.scales = list(scales)
         self.flip = flip
         self.max_batch = max_batch
+        self.lowres = bool(lowres)
+        if self.lowres:
+            missing = [m for m in ("evaluate_lowres", "evaluate_random_lowres") if not callable(getattr(module, m, None))]
+            if missing:
+                raise AttributeError(f"BatchedMultiEval(lowres=True) needs module.{' / module.'.join(missing)} "
+                                     f"({type(module).__name__} has no such method); there is no fallback to the full-resolution path")
+            if self.crop_size % 2 or self.crop_size < 4:
+                raise ValueError(f"BatchedMultiEval(lowres=True): crop_size={self.crop_size} must be even and >= 4")
 
     def _infer(self, crops: torch.Tensor, label_set) -> torch.Tensor:
         """module_inference (encoding_models.py:133-139) for a stack of crops: out = f(x) + flip(f(flip(x)))."""
@@ -108,10 +128,13 @@ class BatchedMultiEval(torch.nn.Module):
         return [self.forward(img.unsqueeze(0).cuda(), label_set) for img in inputs]
 
     def _module_eval(self, xs: torch.Tensor, label_set) -> torch.Tensor:
+        if self.lowres:
+            ev = self.module.evaluate_lowres if label_set is None else (lambda c: self.module.evaluate_random_lowres(c, label_set))
+        else:
+            ev = self.module.evaluate if label_set is None else (lambda c: self.module.evaluate_random(c, label_set))
         outs = []
         for i in range(0, xs.shape[0], self.max_batch):
-            chunk = xs[i:i + self.max_batch]
-            outs.append(self.module.evaluate(chunk) if label_set is None else self.module.evaluate_random(chunk, label_set))
+            outs.append(ev(xs[i:i + self.max_batch]))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     @torch.no_grad()
@@ -147,7 +170,10 @@ class BatchedMultiEval(torch.nn.Module):
         # ... grouped so that at most `max_stack` crops (and their [n, K, crop, crop] fp32 logits: 138 MB per crop at K = 150, crop 480) are
         # alive at once: consecutive scales share a forward while they fit -- a 4:3 ADE image (36 crops) is still ONE batch -- and a larger
         # image / longer scale list runs as several stacks instead of one unbounded allocation
-        max_stack = int(getattr(self, "max_stack", 48))
+        # (lowres: the logits of a crop are [K, crop/2, crop/2], 34.6 MB -- the same bound on memory admits four times the crops)
+        max_stack = int(getattr(self, "max_stack", 192 if self.lowres else 48))
+        side = crop // 2 if self.lowres else crop
+        accumulate = lib.lseg_op_eval_accumulate_lowres if self.lowres else lib.lseg_op_eval_accumulate
         groups, cur_g, cur_n = [], [], 0
         for i, g_ in enumerate(geo):
             if cur_g and cur_n + g_[7] > max_stack:
@@ -160,15 +186,14 @@ class BatchedMultiEval(torch.nn.Module):
         for grp in groups:
             allc = torch.cat([stacks[i] for i in grp], dim=0) if len(grp) > 1 else stacks[grp[0]]
             outs_all = self._module_eval(allc, label_set).contiguous()
-            assert outs_all.shape == (allc.shape[0], nclass, crop, crop) and outs_all.dtype == torch.float32
+            assert outs_all.shape == (allc.shape[0], nclass, side, side) and outs_all.dtype == torch.float32
             o0 = 0
             for i in grp:
                 height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
                 outs = outs_all[o0:o0 + nc]                                   # a contiguous slice: this scale's crops (+ twins)
                 o0 += nc
                 smap = image.new_empty((nclass, height, width))
-                _lib.check(lib.lseg_op_eval_accumulate(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids,
-                                                       int(self.flip), st))
+                _lib.check(accumulate(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, int(self.flip), st))
                 _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, height, width, h, w, 1, st))
             del outs_all, allc
             for i in grp:

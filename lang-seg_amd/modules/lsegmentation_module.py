@@ -421,6 +421,14 @@ class LSegmentationModule(_Base):
         inter, union = batch_intersection_union(pred.data, target.data, self.nclass)
         return correct, labeled, inter, union
 
+    def evaluate_lowres(self, x):
+        """evaluate(x) stopped before the network's output_conv: fp32 [B,K,H/2,W/2] (LSegNet.forward_lowres), for the multi-scale
+        evaluator's lowres=True path, which reads them through the x2 bilinear on the fly."""
+        return self.net.forward_lowres(x)
+
+    def evaluate_random_lowres(self, x, labelset):
+        return self.net.forward_lowres(x, labelset)
+
     def _fused_criterion(self):
         """ignore_index when `self.criterion` is the plain cross-entropy the fused loss implements -- nn.CrossEntropyLoss / [3P] encoding
         SegmentationLosses(se_loss=False, aux=False), mean over pixels != ignore_index, no class weights, no label smoothing -- else None."""

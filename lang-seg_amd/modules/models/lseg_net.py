@@ -476,6 +476,26 @@ class LSeg(BaseModel):
             return self.forward(x, labelset, _want_logits)              # fell back to bf16: run again on a bf16 engine
         return out
 
+    def forward_lowres(self, x, labelset=""):
+        """forward(x, labelset) stopped before scratch.output_conv: fp32 [B,K,H/2,W/2], the logits its x2 bilinear (align_corners=True)
+        turns into forward's output bit for bit (lseg_forward_lowres) -- for callers that read them through that bilinear themselves
+        (BatchedMultiEval(lowres=True)).  Same label handling as forward; inference only."""
+        text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
+        if not x.is_cuda:
+            raise RuntimeError("LSegNet.forward_lowres needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("LSegNet.forward_lowres is an inference path: call it under net.eval() or torch.no_grad()")
+        B, _, H, W = x.shape
+        eng = self._engine(B, H, W, text.shape[0], x.device)
+        if eng.training:
+            eng.set_train(False)
+        self._set_tokens(eng, text, labelset)
+        self._last_engine = eng
+        out = eng.forward_lowres(x.float())
+        if self._range_guard(eng, x.device):
+            return self.forward_lowres(x, labelset)                     # fell back to bf16: run again on a bf16 engine
+        return out
+
 
 class LSegNet(LSeg):
     """Network for semantic segmentation (lseg_net.py:208-226)."""
