@@ -443,6 +443,24 @@ int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi,
  * odd or too small crop, or boxes that do not cover the map. */
 int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
                                    int h_grids, int w_grids, int flip, void* stream);
+/* The same accumulation for PART of a scale's grid, so that a scale with more crops than fit in memory runs as several forwards.
+ * A window is boxes [first_box, first_box + n_box) of the grid in row-major (idh,idw) order; d_outs fp32 [(1+flip)*n_box, K, crop, crop]
+ * holds only their logits (twins in the second half).  For every pixel of d_sum fp32 [K,height,width] that a box of the window covers,
+ * d_sum += out + flip(out_twin) per covering box of the window in ascending box order; no division.  Pixels no box of the window covers
+ * are neither read nor written, and the launch is sized by the window's footprint.  The caller zeroes d_sum before the first window,
+ * submits the windows of any partition of the grid in ascending order and then calls lseg_op_eval_finalize: the result is bit-identical
+ * to lseg_op_eval_accumulate on the whole stack (the same fp32 additions from 0 in the same order, then the same division).
+ *   lseg_op_eval_accumulate_window_lowres  the same over d_low fp32 [(1+flip)*n_box, K, crop/2, crop/2], read through the x2 bilinear
+ *                                          with lseg_op_eval_accumulate_lowres' tap arithmetic (crop even and >= 4)
+ *   lseg_op_eval_finalize                  d_map = d_sum / (number of boxes of the whole grid covering the pixel); d_map == d_sum allowed
+ * Arguments are checked before the device is touched: LSEG_ERR_INVALID for NULLs, n_box <= 0, a window outside the grid, boxes that do
+ * not cover the map, or (lowres) an odd or too small crop. */
+int lseg_op_eval_accumulate_window(const float* d_outs, float* d_sum, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                   int h_grids, int w_grids, int flip, int first_box, int n_box, void* stream);
+int lseg_op_eval_accumulate_window_lowres(const float* d_low, float* d_sum, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                          int h_grids, int w_grids, int flip, int first_box, int n_box, void* stream);
+int lseg_op_eval_finalize(const float* d_sum, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
+                          int w_grids, void* stream);
 
 /* Backward of one Linear layer y = x W^T + b -- first brick of the training step (the reference gets
  * it from torch autograd under LSegmentationModule.training_step, lsegmentation_module.py:66-81).  bf16/fp16 operands,

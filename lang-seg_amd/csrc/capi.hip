@@ -499,6 +499,46 @@ int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int 
     int r = require_device(); if (r) return r;
     return launch_eval_accumulate_lowres(d_low, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
 }
+// the checks shared by the windowed forms, all before the device is touched
+static int eval_window_check(const char* what, const void* d_a, const void* d_b, int K, int height, int width, int ph, int pw, int crop, int stride,
+                             int h_grids, int w_grids, int lowres) {
+    if (!d_a || !d_b) return set_error(LSEG_ERR_INVALID, "%s: NULL pointer", what);
+    if (lowres && (crop < 4 || (crop & 1)))
+        return set_error(LSEG_ERR_INVALID, "%s: crop=%d must be even and >= 4 (the planes are crop/2 x crop/2)", what, crop);
+    if (K < 1 || height < 1 || width < 1 || height > ph || width > pw || crop < 1 || stride < 1 || h_grids < 1 || w_grids < 1 ||
+        (long long)h_grids * w_grids > 0x3fffffff || (long long)(h_grids - 1) * stride + crop < ph || (long long)(w_grids - 1) * stride + crop < pw)
+        return set_error(LSEG_ERR_INVALID, "%s: the boxes do not cover the %dx%d map", what, ph, pw);
+    if (((uintptr_t)d_a | (uintptr_t)d_b) & 3) return set_error(LSEG_ERR_INVALID, "%s: pointers must be 4-byte aligned", what);
+    return 0;
+}
+static int eval_accumulate_window(const char* what, const float* d_outs, float* d_sum, int K, int height, int width, int ph, int pw, int crop,
+                                  int stride, int h_grids, int w_grids, int flip, int first_box, int n_box, int lowres, void* stream) {
+    int r = eval_window_check(what, d_outs, d_sum, K, height, width, ph, pw, crop, stride, h_grids, w_grids, lowres);
+    if (r) return r;
+    if (n_box < 1 || first_box < 0 || (long long)first_box + n_box > (long long)h_grids * w_grids)
+        return set_error(LSEG_ERR_INVALID, "%s: boxes [%d, %d + %d) are not a window of the %dx%d grid", what, first_box, first_box, n_box, h_grids,
+                         w_grids);
+    r = require_device(); if (r) return r;
+    return launch_eval_accumulate_window(d_outs, d_sum, K, height, width, crop, stride, w_grids, flip ? 1 : 0, first_box, n_box, lowres,
+                                         (hipStream_t)stream);
+}
+int lseg_op_eval_accumulate_window(const float* d_outs, float* d_sum, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                   int h_grids, int w_grids, int flip, int first_box, int n_box, void* stream) {
+    return eval_accumulate_window("eval_accumulate_window", d_outs, d_sum, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip,
+                                  first_box, n_box, 0, stream);
+}
+int lseg_op_eval_accumulate_window_lowres(const float* d_low, float* d_sum, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                          int h_grids, int w_grids, int flip, int first_box, int n_box, void* stream) {
+    return eval_accumulate_window("eval_accumulate_window_lowres", d_low, d_sum, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip,
+                                  first_box, n_box, 1, stream);
+}
+int lseg_op_eval_finalize(const float* d_sum, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
+                          int w_grids, void* stream) {
+    int r = eval_window_check("eval_finalize", d_sum, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, 0);
+    if (r) return r;
+    r = require_device(); if (r) return r;
+    return launch_eval_finalize(d_sum, d_map, K, height, width, crop, stride, h_grids, w_grids, (hipStream_t)stream);
+}
 int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, void* stream) {
     int r = require_device(); if (r) return r;
     if (!d_src || !d_dst) return set_error(LSEG_ERR_INVALID, "eval_resize: NULL pointer");

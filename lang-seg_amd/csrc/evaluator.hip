@@ -7,6 +7,8 @@
 //   accumulate  : the stack of logits -> count-normalised score map of the scale (flip-add, overlap-add in the reference's box order,
 //                 divide, crop to the un-padded size), one pass, no atomics
 //   resize_add  : scores (+)= bilinear(map) at the input resolution (also used for the image resize itself)
+#include <algorithm>
+
 #include "ops.h"
 #include "../../include/lseg_hip.h"
 
@@ -168,6 +170,170 @@ __global__ __launch_bounds__(256) void eval_accumulate_lowres_kernel(const float
     }
 }
 
+// A WINDOW of a scale's grid: boxes [first, first + nbox) in (idh, idw) order, outs [(1 + flip) * nbox, K, side, side] holding only their
+// logits (LOW: side = crop / 2, read through the x2 bilinear exactly as eval_accumulate_lowres_kernel does; else side = crop).  For every
+// map pixel some box of the window covers, sum[k, y, x] takes, in ascending box order, += out + flip_x(twin) -- the additions the
+// one-launch kernels make from 0.f, continued from the fp32 partial sum in memory, so windows submitted in ascending order leave the bits
+// of their un-divided acc (eval_finalize_kernel divides).  A pixel no box of the window covers is neither read nor written.
+//
+// Work comes from the window's footprint: rows y_lo .. y_lo + ny - 1 and columns [x_lo, x_hi) are the bounding rectangle of its boxes
+// on the map (the launcher), one wave per (k, y), four rows per block, a lane produces runs of four consecutive x shifted so that every
+// interior run is a 16-byte aligned load + store of sum.  Per run and box the four logits (and the twin's, at the mirrored columns
+// crop - 1 - (x - w0), descending) are one 16-byte load each where the address allows, four 4-byte loads otherwise.
+template <bool LOW>
+__global__ __launch_bounds__(256) void eval_accumulate_window_kernel(const float* __restrict__ outs, float* __restrict__ sum, int K, int height,
+                                                                     int width, int crop, int stride, int w_grids, int flip, int first, int nbox,
+                                                                     int y_lo, int ny, int x_lo, int x_hi) {
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (size_t)K * ny) return;
+    const int lane = threadIdx.x & 63;
+    const int k = (int)((unsigned)row / (unsigned)ny);                  // K * ny < 2^31 (launcher)
+    const int y = y_lo + (int)((unsigned)row - (unsigned)k * (unsigned)ny);
+    const int side = LOW ? crop >> 1 : crop;
+    const float r = (float)(side - 1) / (float)(crop - 1);            // LOW only: upsample2x_planes_kernel's ry = rx
+    const size_t plane = (size_t)side * side;
+    const size_t twin = (size_t)nbox * K * plane;
+    const int last = first + nbox - 1;
+    const int ih_a = first / w_grids, ih_b = last / w_grids;
+    const int iw_a = first - ih_a * w_grids, iw_b = last - ih_b * w_grids;
+    // the window's grid rows covering y: idh * stride <= y < idh * stride + crop (y < height <= ph: the clip to ph never cuts a map row)
+    const int h_lo = max(y < crop ? 0 : (y - crop) / stride + 1, ih_a);
+    const int h_hi = min(y / stride, ih_b);
+    if (h_lo > h_hi) return;
+    float* orow = sum + ((size_t)k * height + y) * (size_t)width;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(orow + x_lo) >> 2) & 3);      // run q covers x = x_lo + 4 q - shift .. + 3
+    const int nq = (x_hi - x_lo + shift + 3) >> 2;
+    for (int q = lane; q < nq; q += 64) {
+        const int xb = x_lo + 4 * q - shift;
+        int xs[4];
+        bool valid[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            valid[e] = xb + e >= x_lo && xb + e < x_hi;
+            xs[e] = min(max(xb + e, 0), width - 1);
+        }
+        const int w_lo = xs[0] < crop ? 0 : (xs[0] - crop) / stride + 1;
+        const int w_hi = min(xs[3] / stride, w_grids - 1);
+        // which of the four pixels the window covers at all: only those touch sum
+        bool cov[4] = {false, false, false, false};
+        for (int idh = h_lo; idh <= h_hi; ++idh) {
+            const int a = max(w_lo, idh == ih_a ? iw_a : 0), b = min(w_hi, idh == ih_b ? iw_b : w_grids - 1);
+            for (int idw = a; idw <= b; ++idw) {
+                const int w0 = idw * stride;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) cov[e] = cov[e] || (valid[e] && xs[e] >= w0 && xs[e] < w0 + crop);
+            }
+        }
+        if (!(cov[0] || cov[1] || cov[2] || cov[3])) continue;
+        const bool whole = cov[0] && cov[1] && cov[2] && cov[3];           // then xb .. xb + 3 lie in the row and the run is 16-byte aligned
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (whole) {
+            const f32x4_t sv = *reinterpret_cast<const f32x4_t*>(orow + xb);
+            acc[0] = sv[0]; acc[1] = sv[1]; acc[2] = sv[2]; acc[3] = sv[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (cov[e]) acc[e] = orow[xb + e];
+        }
+        for (int idh = h_lo; idh <= h_hi; ++idh) {
+            const int a = max(w_lo, idh == ih_a ? iw_a : 0), b = min(w_hi, idh == ih_b ? iw_b : w_grids - 1);
+            int y0 = y - idh * stride, y1 = y0;
+            float ly = 0.f;
+            if (LOW) {
+                src_tap(r, y - idh * stride, side, y0, y1, ly);
+                y0 = min(y0, side - 1); y1 = min(y1, side - 1);
+            }
+            for (int idw = a; idw <= b; ++idw) {
+                const int w0 = idw * stride;
+                const float* p = outs + ((size_t)(idh * w_grids + idw - first) * K + k) * plane;
+                bool in[4];
+                int xl[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    in[e] = valid[e] && xs[e] >= w0 && xs[e] < w0 + crop;
+                    xl[e] = min(max(xs[e] - w0, 0), crop - 1);
+                }
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (LOW) {
+                    taps4(p + (size_t)y0 * side, p + (size_t)y1 * side, xl, r, side, ly, 0, v);
+                    if (flip) {
+                        int xm[4];
+                        float t[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) xm[e] = crop - 1 - xl[e];
+                        taps4(p + twin + (size_t)y0 * side, p + twin + (size_t)y1 * side, xm, r, side, ly, 1, t);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] += t[e];
+                    }
+                } else {
+                    const float* s = p + (size_t)y0 * crop;
+                    if (in[0] && in[1] && in[2] && in[3]) {                 // xl[e] = xl[0] + e: four consecutive logits
+                        const float* a4 = s + xl[0];
+                        if ((reinterpret_cast<uintptr_t>(a4) & 15) == 0) {
+                            const f32x4_t t = *reinterpret_cast<const f32x4_t*>(a4);
+                            v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = a4[e];
+                        }
+                        if (flip) {
+                            const float* m4 = s + twin + (crop - 1 - xl[3]);   // the mirrored columns of e = 3, 2, 1, 0
+                            if ((reinterpret_cast<uintptr_t>(m4) & 15) == 0) {
+                                const f32x4_t t = *reinterpret_cast<const f32x4_t*>(m4);
+                                v[0] += t[3]; v[1] += t[2]; v[2] += t[1]; v[3] += t[0];
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) v[e] += m4[3 - e];
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (in[e]) {
+                                v[e] = s[xl[e]];
+                                if (flip) v[e] += s[twin + (crop - 1 - xl[e])];
+                            }
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (in[e]) acc[e] += v[e];
+            }
+        }
+        if (whole) {
+            const f32x4_t ov = {acc[0], acc[1], acc[2], acc[3]};
+            *reinterpret_cast<f32x4_t*>(orow + xb) = ov;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (cov[e]) orow[xb + e] = acc[e];
+        }
+    }
+}
+
+// map = sum / (number of boxes of the WHOLE grid covering the pixel): the division of the one-launch kernels (their count as a float).
+// Element-wise, so map == sum is fine; 16 bytes per lane where both pointers allow.
+__device__ __forceinline__ float eval_cover_count(size_t i, int height, int width, int crop, int stride, int h_grids, int w_grids) {
+    const int x = (int)(i % width);
+    const int y = (int)((i / width) % height);
+    const int nh = min(y / stride, h_grids - 1) - (y < crop ? 0 : (y - crop) / stride + 1) + 1;
+    const int nw = min(x / stride, w_grids - 1) - (x < crop ? 0 : (x - crop) / stride + 1) + 1;
+    return (float)(nh * nw);
+}
+__global__ void eval_finalize_kernel(const float* sum, float* map, size_t total, int height, int width, int crop, int stride, int h_grids,
+                                     int w_grids, int vec) {
+    const size_t n4 = vec ? total / 4 : 0;
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < n4; j += (size_t)gridDim.x * blockDim.x) {
+        const f32x4_t s = reinterpret_cast<const f32x4_t*>(sum)[j];
+        f32x4_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = s[e] / eval_cover_count(4 * j + e, height, width, crop, stride, h_grids, w_grids);
+        reinterpret_cast<f32x4_t*>(map)[j] = o;
+    }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        map[i] = sum[i] / eval_cover_count(i, height, width, crop, stride, h_grids, w_grids);
+}
+
 // dst [P, Ho, Wo] (+)= bilinear(src [P, Hi, Wi]), align_corners=True (F.interpolate / upsample_bilinear2d's arithmetic)
 __global__ void eval_resize_kernel(const float* __restrict__ src, float* __restrict__ dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate) {
     const size_t total = (size_t)P * Ho * Wo;
@@ -215,6 +381,40 @@ int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int h
     if (rows > 0x7fffffffu) return set_error(LSEG_ERR_UNSUPPORTED, "eval_accumulate_lowres: too many rows");
     hipLaunchKernelGGL(eval_accumulate_lowres_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, low, outputs, K, height, width, crop,
                        stride, h_grids, w_grids, flip);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+// the bounding rectangle of boxes [first, first + nbox) on the [height, width] map is the launch; a window wholly in the padding launches nothing
+int launch_eval_accumulate_window(const float* outs, float* sum, int K, int height, int width, int crop, int stride, int w_grids, int flip,
+                                  int first, int nbox, int lowres, hipStream_t st) {
+    const int last = first + nbox - 1;
+    const int ih_a = first / w_grids, ih_b = last / w_grids;
+    const long long y_lo = (long long)ih_a * stride, y_hi = std::min<long long>((long long)ih_b * stride + crop, height);
+    long long x_lo = 0, x_hi = width;
+    if (ih_a == ih_b) {
+        x_lo = (long long)(first - ih_a * w_grids) * stride;
+        x_hi = std::min<long long>((long long)(last - ih_b * w_grids) * stride + crop, width);
+    }
+    if (y_lo >= y_hi || x_lo >= x_hi) return 0;
+    const int ny = (int)(y_hi - y_lo);
+    const size_t rows = (size_t)K * ny;
+    if (rows > 0x7fffffffu) return set_error(LSEG_ERR_UNSUPPORTED, "eval_accumulate_window: too many rows");
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (lowres)
+        hipLaunchKernelGGL(eval_accumulate_window_kernel<true>, grid, dim3(256), 0, st, outs, sum, K, height, width, crop, stride, w_grids, flip,
+                           first, nbox, (int)y_lo, ny, (int)x_lo, (int)x_hi);
+    else
+        hipLaunchKernelGGL(eval_accumulate_window_kernel<false>, grid, dim3(256), 0, st, outs, sum, K, height, width, crop, stride, w_grids, flip,
+                           first, nbox, (int)y_lo, ny, (int)x_lo, (int)x_hi);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_eval_finalize(const float* sum, float* map, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,
+                         hipStream_t st) {
+    const size_t total = (size_t)K * height * width;
+    const int vec = ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(map)) & 15) == 0;
+    hipLaunchKernelGGL(eval_finalize_kernel, dim3(grid_for((total + 3) / 4)), dim3(256), 0, st, sum, map, total, height, width, crop, stride,
+                       h_grids, w_grids, vec);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -208,6 +208,10 @@ int launch_eval_accumulate(const float* outs, float* outputs, int K, int height,
                            int w_grids, int flip, hipStream_t st);
 int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride,
                                   int h_grids, int w_grids, int flip, hipStream_t st);
+int launch_eval_accumulate_window(const float* outs, float* sum, int K, int height, int width, int crop, int stride, int w_grids, int flip,
+                                  int first, int nbox, int lowres, hipStream_t st);
+int launch_eval_finalize(const float* sum, float* map, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,
+                         hipStream_t st);
 int launch_eval_resize(const float* src, float* dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, hipStream_t st);
 
 // ---- resnet.hip: the torchvision ResNet-101 image tower (lseg_config.flags bit 5) ----

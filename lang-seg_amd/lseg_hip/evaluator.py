@@ -40,6 +40,16 @@ def scale_geometry(h: int, w: int, scale: float, base_size: int, crop_size: int)
     return height, width, ph, pw, h_grids, w_grids, stride
 
 
+def window_partition(n_box: int, max_crops: int, flip: bool):
+    """Split the n_box boxes of one scale's grid (row-major (idh, idw) order) into windows [(first_box, n_box), ...] of whole boxes --
+    ascending, disjoint, covering -- of at most `max_crops` crops each, a box's mirrored twin (flip) counting with it.  ValueError when
+    not even one box (with its twin) fits."""
+    per = int(max_crops) // (2 if flip else 1)
+    if per < 1:
+        raise ValueError(f"max_stack={max_crops} holds no box{' with its mirrored twin' if flip else ''}: it must be at least {2 if flip else 1}")
+    return [(first, min(per, n_box - first)) for first in range(0, n_box, per)]
+
+
 def _pad_image(img, mean, std, crop_size):          # encoding_models.py:144-155
     b, c, h, w = img.shape
     padh = crop_size - h if h < crop_size else 0
@@ -82,8 +92,13 @@ class BatchedMultiEval(torch.nn.Module):
     `module` needs .evaluate(x) / .evaluate_random(x, labels), .base_size, .crop_size, .mean, .std,
     ._up_kwargs (the LSegModule surface, modules/lseg_module.py:29-93)."""
 
-    def __init__(self, module, nclass, flip=True, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), max_batch=36, cache_text=True, lowres=False):
-        """lowres: (device images only) the forwards stop before the network's output_conv (module.evaluate_lowres /
+    def __init__(self, module, nclass, flip=True, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), max_batch=36, cache_text=True, lowres=False,
+                 max_stack=None):
+        """max_stack: (device images only) the most crops, mirrored twins included, whose logits are alive at once; None = 48 (192 with
+        lowres).  Scales share a forward while they fit; a scale with more crops than that runs as windows of whole boxes through
+        lseg_op_eval_accumulate_window(_lowres) + lseg_op_eval_finalize -- the same scores bit for bit (DESIGN par. 3.8).  An attribute
+        `max_stack` set on the evaluator afterwards overrides it.
+        lowres: (device images only) the forwards stop before the network's output_conv (module.evaluate_lowres /
         evaluate_random_lowres -> fp32 [n, K, crop/2, crop/2]) and lseg_op_eval_accumulate_lowres reads those logits through the x2 bilinear
         on the fly: the same scores bit for bit, a quarter of the logits written, read and alive (DESIGN par. 3.8).  The module must
         offer both *_lowres methods: there is no fallback to the full-resolution path.
@@ -101,6 +116,7 @@ class BatchedMultiEval(torch.nn.Module):
         self.flip = flip
         self.max_batch = max_batch
         self.lowres = bool(lowres)
+        self._max_stack = None if max_stack is None else int(max_stack)
         if self.lowres:
             missing = [m for m in ("evaluate_lowres", "evaluate_random_lowres") if not callable(getattr(module, m, None))]
             if missing:
@@ -157,21 +173,31 @@ class BatchedMultiEval(torch.nn.Module):
         # max_batch -- a 4:3 ADE image is 36 crops = one batch-36 forward where the per-scale form ran six forwards of 2 .. 12 crops, each at
         # the low-occupancy end of the engine's batch sweep (DESIGN par. 3.8).  Crops are independent in the engine, so the per-crop logits
         # are those of the per-scale form (bit for bit under the batch-invariant schedule).
-        geo, stacks = [], []
+        twins = 2 if self.flip else 1
+        geo = []
         for scale in self.scales:
             height, width, ph, pw, h_grids, w_grids, stride = scale_geometry(h, w, scale, self.base_size, crop)
+            geo.append((height, width, ph, pw, h_grids, w_grids, stride, twins * h_grids * w_grids))
+
+        def make_crops(i):                   # a scale's crops exist from its group's turn on, not before
+            height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
             cur = image.new_empty((ch, height, width))
             _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, height, width, 0, st))
-            n = h_grids * w_grids
-            crops = image.new_empty(((2 if self.flip else 1) * n, ch, crop, crop))
+            crops = image.new_empty((nc, ch, crop, crop))
             _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, height, width, crop, stride, h_grids, w_grids, int(self.flip), pad, st))
-            geo.append((height, width, ph, pw, h_grids, w_grids, stride, crops.shape[0]))
-            stacks.append(crops)
+            return crops
         # ... grouped so that at most `max_stack` crops (and their [n, K, crop, crop] fp32 logits: 138 MB per crop at K = 150, crop 480) are
         # alive at once: consecutive scales share a forward while they fit -- a 4:3 ADE image (36 crops) is still ONE batch -- and a larger
         # image / longer scale list runs as several stacks instead of one unbounded allocation
         # (lowres: the logits of a crop are [K, crop/2, crop/2], 34.6 MB -- the same bound on memory admits four times the crops)
-        max_stack = int(getattr(self, "max_stack", 192 if self.lowres else 48))
+        # A scale that alone has more crops than max_stack (base_size / crop_size and the aspect ratio decide: base 2048 / crop 480 is an
+        # 11 x 6 grid at scale 1.75) is a group of its own and runs as WINDOWS of whole boxes, each one forward (at most max_batch crops
+        # where a box and its twin fit in that): lseg_op_eval_accumulate_window adds a window's logits into the scale's fp32 sum in box
+        # order, lseg_op_eval_finalize divides -- the additions and the division of the one-launch kernel, so the same bits.
+        max_stack = getattr(self, "max_stack", None)
+        if max_stack is None:
+            max_stack = self._max_stack if self._max_stack is not None else (192 if self.lowres else 48)
+        max_stack = int(max_stack)
         side = crop // 2 if self.lowres else crop
         accumulate = lib.lseg_op_eval_accumulate_lowres if self.lowres else lib.lseg_op_eval_accumulate
         groups, cur_g, cur_n = [], [], 0
@@ -183,7 +209,38 @@ class BatchedMultiEval(torch.nn.Module):
             cur_n += g_[7]
         if cur_g:
             groups.append(cur_g)
+        windows = {}                         # scale -> [(first_box, n_box), ...] for the scales that do not fit
         for grp in groups:
+            i = grp[0]
+            if geo[i][7] > max_stack:        # then the grouping above left it alone
+                per_fwd = min(max_stack, self.max_batch)
+                windows[i] = window_partition(geo[i][4] * geo[i][5], per_fwd if per_fwd >= twins else max_stack, self.flip)
+        # the largest forward of this call, known before the first: the wrapped network sizes its engine once instead of growing it
+        # (closing and rebuilding it) when a later stack is larger than the first
+        largest = max(max(twins * nb for _, nb in windows[grp[0]]) if grp[0] in windows else sum(geo[i][7] for i in grp) for grp in groups)
+        net = getattr(self.module, "net", None)
+        if callable(getattr(net, "reserve_batch", None)):
+            net.reserve_batch(min(self.max_batch, largest), crop, crop, None if label_set is None else nclass, image.device)
+        for grp in groups:
+            if grp[0] in windows:
+                i = grp[0]
+                height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
+                n = h_grids * w_grids
+                crops = make_crops(i)
+                smap = image.new_zeros((nclass, height, width))
+                accumulate_window = lib.lseg_op_eval_accumulate_window_lowres if self.lowres else lib.lseg_op_eval_accumulate_window
+                for first, nb in windows[i]:
+                    xs = torch.cat([crops[first:first + nb], crops[n + first:n + first + nb]], dim=0) if self.flip else crops[first:first + nb]
+                    outs = self._module_eval(xs, label_set).contiguous()
+                    assert outs.shape == (xs.shape[0], nclass, side, side) and outs.dtype == torch.float32
+                    _lib.check(accumulate_window(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, int(self.flip),
+                                                 first, nb, st))
+                    del outs, xs
+                _lib.check(lib.lseg_op_eval_finalize(P(smap), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, st))
+                _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, height, width, h, w, 1, st))
+                del crops, smap
+                continue
+            stacks = {i: make_crops(i) for i in grp}
             allc = torch.cat([stacks[i] for i in grp], dim=0) if len(grp) > 1 else stacks[grp[0]]
             outs_all = self._module_eval(allc, label_set).contiguous()
             assert outs_all.shape == (allc.shape[0], nclass, side, side) and outs_all.dtype == torch.float32
@@ -195,9 +252,7 @@ class BatchedMultiEval(torch.nn.Module):
                 smap = image.new_empty((nclass, height, width))
                 _lib.check(accumulate(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, int(self.flip), st))
                 _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, height, width, h, w, 1, st))
-            del outs_all, allc
-            for i in grp:
-                stacks[i] = None
+            del outs_all, outs, allc, stacks, smap       # `outs` is a view of the stack: left bound, it keeps the logits alive into the next group
         return scores
 
     @torch.no_grad()

@@ -496,6 +496,19 @@ class LSeg(BaseModel):
             return self.forward_lowres(x, labelset)                     # fell back to bf16: run again on a bf16 engine
         return out
 
+    def reserve_batch(self, B, H, W, n_labels=None, device=None):
+        """Make the inference engine of (H, W) on `device` large enough for batches of B images and n_labels labels (None: this network's
+        own) now.  An engine grows by being closed and rebuilt (`_engine`), so a caller that knows its largest batch before its first --
+        BatchedMultiEval, whose stacks vary within a call -- pays for one build instead of one per larger batch."""
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if n_labels is None:
+            if getattr(self, "text", None) is None:                     # no label set of its own (the zero-shot networks): nothing to size for
+                return
+            n_labels = self.text.shape[0]
+        self._engine(int(B), int(H), int(W), int(n_labels), device)
+
 
 class LSegNet(LSeg):
     """Network for semantic segmentation (lseg_net.py:208-226)."""
