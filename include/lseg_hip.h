@@ -427,7 +427,9 @@ int lseg_op_corr_argmax_geometry(int* out8);
  *                            (= -mean/std, :144-155); with flip the second half holds the mirrored twins (:135-137)
  *   lseg_op_eval_accumulate  d_outs fp32 [(1+flip)*n, K, crop, crop] (the engine's logits for that stack) -> d_map fp32 [K,height,width]:
  *                            out + flip(out_twin) summed over the covering boxes in (idh,idw) order, divided by their count, cropped
- *                            to the un-padded size (:100-121); ph, pw = size of the padded image the boxes are clipped to
+ *                            to the un-padded size (:100-121); ph, pw = size of the padded image the boxes are clipped to.  Arguments
+ *                            are checked before the device is touched, as for every accumulate / finalize entry below:
+ *                            LSEG_ERR_INVALID for NULL or not 4-byte aligned pointers, or boxes that do not cover the map
  *   lseg_op_eval_resize      d_dst [P,Ho,Wo] (+)= bilinear(d_src [P,Hi,Wi]), align_corners=True (:78, :123: the image resize and
  *                            `scores += resize_image(outputs, h, w)`) */
 int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int height, int width, int crop, int stride, int h_grids, int w_grids,

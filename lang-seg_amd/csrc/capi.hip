@@ -479,29 +479,10 @@ int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int heigh
         return set_error(LSEG_ERR_INVALID, "eval_make_crops: bad geometry");
     return launch_eval_make_crops(d_img, d_crops, C, height, width, crop, stride, h_grids, w_grids, flip ? 1 : 0, host_pad3, (hipStream_t)stream);
 }
-int lseg_op_eval_accumulate(const float* d_outs, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
-                            int h_grids, int w_grids, int flip, void* stream) {
-    int r = require_device(); if (r) return r;
-    if (!d_outs || !d_map) return set_error(LSEG_ERR_INVALID, "eval_accumulate: NULL pointer");
-    if (K < 1 || height < 1 || width < 1 || height > ph || width > pw || crop < 1 || stride < 1 || h_grids < 1 || w_grids < 1 ||
-        (h_grids - 1) * stride + crop < ph || (w_grids - 1) * stride + crop < pw)
-        return set_error(LSEG_ERR_INVALID, "eval_accumulate: the boxes do not cover the %dx%d map", ph, pw);
-    return launch_eval_accumulate(d_outs, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
-}
-int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
-                                   int h_grids, int w_grids, int flip, void* stream) {
-    if (!d_low || !d_map) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: NULL pointer");
-    if (crop < 4 || (crop & 1)) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: crop=%d must be even and >= 4 (the planes are crop/2 x crop/2)", crop);
-    if (K < 1 || height < 1 || width < 1 || height > ph || width > pw || stride < 1 || h_grids < 1 || w_grids < 1 ||
-        (long long)(h_grids - 1) * stride + crop < ph || (long long)(w_grids - 1) * stride + crop < pw)
-        return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: the boxes do not cover the %dx%d map", ph, pw);
-    if (((uintptr_t)d_low | (uintptr_t)d_map) & 3) return set_error(LSEG_ERR_INVALID, "eval_accumulate_lowres: pointers must be 4-byte aligned");
-    int r = require_device(); if (r) return r;
-    return launch_eval_accumulate_lowres(d_low, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
-}
-// the checks shared by the windowed forms, all before the device is touched
-static int eval_window_check(const char* what, const void* d_a, const void* d_b, int K, int height, int width, int ph, int pw, int crop, int stride,
-                             int h_grids, int w_grids, int lowres) {
+// the geometry contract of the accumulate and finalize entries, checked before the device is touched: a [K, height, width] map inside the
+// padded (ph, pw) image that the h_grids x w_grids boxes cover; lowres: the logits are crop/2 x crop/2 planes
+static int eval_geometry_check(const char* what, const void* d_a, const void* d_b, int K, int height, int width, int ph, int pw, int crop, int stride,
+                               int h_grids, int w_grids, int lowres) {
     if (!d_a || !d_b) return set_error(LSEG_ERR_INVALID, "%s: NULL pointer", what);
     if (lowres && (crop < 4 || (crop & 1)))
         return set_error(LSEG_ERR_INVALID, "%s: crop=%d must be even and >= 4 (the planes are crop/2 x crop/2)", what, crop);
@@ -511,9 +492,23 @@ static int eval_window_check(const char* what, const void* d_a, const void* d_b,
     if (((uintptr_t)d_a | (uintptr_t)d_b) & 3) return set_error(LSEG_ERR_INVALID, "%s: pointers must be 4-byte aligned", what);
     return 0;
 }
+int lseg_op_eval_accumulate(const float* d_outs, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
+                            int h_grids, int w_grids, int flip, void* stream) {
+    int r = eval_geometry_check("eval_accumulate", d_outs, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, 0);
+    if (r) return r;
+    r = require_device(); if (r) return r;
+    return launch_eval_accumulate(d_outs, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
+}
+int lseg_op_eval_accumulate_lowres(const float* d_low, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
+                                   int h_grids, int w_grids, int flip, void* stream) {
+    int r = eval_geometry_check("eval_accumulate_lowres", d_low, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, 1);
+    if (r) return r;
+    r = require_device(); if (r) return r;
+    return launch_eval_accumulate_lowres(d_low, d_map, K, height, width, crop, stride, h_grids, w_grids, flip ? 1 : 0, (hipStream_t)stream);
+}
 static int eval_accumulate_window(const char* what, const float* d_outs, float* d_sum, int K, int height, int width, int ph, int pw, int crop,
                                   int stride, int h_grids, int w_grids, int flip, int first_box, int n_box, int lowres, void* stream) {
-    int r = eval_window_check(what, d_outs, d_sum, K, height, width, ph, pw, crop, stride, h_grids, w_grids, lowres);
+    int r = eval_geometry_check(what, d_outs, d_sum, K, height, width, ph, pw, crop, stride, h_grids, w_grids, lowres);
     if (r) return r;
     if (n_box < 1 || first_box < 0 || (long long)first_box + n_box > (long long)h_grids * w_grids)
         return set_error(LSEG_ERR_INVALID, "%s: boxes [%d, %d + %d) are not a window of the %dx%d grid", what, first_box, first_box, n_box, h_grids,
@@ -534,7 +529,7 @@ int lseg_op_eval_accumulate_window_lowres(const float* d_low, float* d_sum, int 
 }
 int lseg_op_eval_finalize(const float* d_sum, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
                           int w_grids, void* stream) {
-    int r = eval_window_check("eval_finalize", d_sum, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, 0);
+    int r = eval_geometry_check("eval_finalize", d_sum, d_map, K, height, width, ph, pw, crop, stride, h_grids, w_grids, 0);
     if (r) return r;
     r = require_device(); if (r) return r;
     return launch_eval_finalize(d_sum, d_map, K, height, width, crop, stride, h_grids, w_grids, (hipStream_t)stream);

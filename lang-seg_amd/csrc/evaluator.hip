@@ -64,21 +64,49 @@ __global__ void eval_accumulate_kernel(const float* __restrict__ outs, float* __
     }
 }
 
-// The same from the (crop/2, crop/2) logits the engine holds before output_conv (lseg_forward_lowres): low [(1 + flip) * n, K, hl, hl],
-// hl = crop / 2, read through output_conv's x2 bilinear on the fly -- src_tap / bilerp (common.h), the arithmetic of upsample2x_planes_kernel,
-// so every value is the bit pattern eval_accumulate_kernel would have read from the materialised stack; the sum over the covering boxes
-// runs in the same (idh, idw) order from the same 0.f, and the division is the same.  The twin's value is the tap of the MIRRORED
-// full-resolution column crop - 1 - (x - w0) on the twin's planes (mirroring a value interpolated at x would round differently).
-//
-// One wave per output row (k, y), four rows per block; a lane produces runs of four consecutive x.  The runs are shifted so that
-// every interior one is a 16-byte aligned store whatever the width and the map's offset (the row's first / last run are partial: scalar
-// stores).  Per row, once and wave-uniform: the covering idh range and, per idh, the two source rows and ly.  Per run and covering
-// box: the eight taps of the four outputs lie in four consecutive low-resolution columns (r < 1/2: four consecutive outputs advance
-// the left tap by at most 2), so two rows x four columns are loaded once and feed all four outputs; likewise for the twin, whose
-// columns run backwards.  Bytes read per crop fall 4x against the full-resolution form and stay in L1 / L2 across neighbouring runs.
+// ---- the run-of-four form of the same sum: eval_accumulate_lowres_kernel (a whole grid, from 0.f, counted and divided) and
+// eval_accumulate_window_kernel (a window of the grid, continued from the sum in memory, divided by eval_finalize_kernel).  One wave per
+// output row (k, y), four rows per block; a lane produces runs of four consecutive x.  Both add, per pixel, out + flip_x(twin) of the
+// covering boxes in ascending (idh, idw) order: the additions of eval_accumulate_kernel, so the same bits.
+// The boxes idx of one grid axis covering coordinate c of the map, idx * stride <= c < idx * stride + crop (the clip of the last box to
+// the padded size never cuts inside the map):
+struct CoverRange { int lo, hi; };
+__device__ __forceinline__ CoverRange cover_range(int c, int crop, int stride, int grids) {
+    return {c < crop ? 0 : (c - crop) / stride + 1, min(c / stride, grids - 1)};
+}
+
+// A row's columns [x_lo, x_hi) as nq runs of four: run q covers x = x_lo + 4 q - shift .. + 3, shifted so that every interior run is
+// 16 bytes aligned in memory whatever the width and the map's offset; the row's first / last run may be partial.
+__device__ __forceinline__ void run_frame(const float* row, int x_lo, int x_hi, int& shift, int& nq) {
+    shift = (int)((reinterpret_cast<uintptr_t>(row + x_lo) >> 2) & 3);
+    nq = (x_hi - x_lo + shift + 3) >> 2;
+}
+// the run at xb: valid[e] = inside [x_lo, x_hi); xs[e] clamped into the row (an invalid element computes a neighbour's value, not stored)
+__device__ __forceinline__ void run_columns(int xb, int x_lo, int x_hi, int width, int (&xs)[4], bool (&valid)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        valid[e] = xb + e >= x_lo && xb + e < x_hi;
+        xs[e] = min(max(xb + e, 0), width - 1);
+    }
+}
+__device__ __forceinline__ bool all4(const bool (&m)[4]) { return m[0] && m[1] && m[2] && m[3]; }
+// row[xb + e] = o[e] where m[e]: one 16-byte store when all four (then the run is interior, hence aligned), scalar stores otherwise
+__device__ __forceinline__ void store_run(float* row, int xb, const float (&o)[4], const bool (&m)[4]) {
+    if (all4(m)) {
+        const f32x4_t ov = {o[0], o[1], o[2], o[3]};
+        *reinterpret_cast<f32x4_t*>(row + xb) = ov;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (m[e]) row[xb + e] = o[e];
+    }
+}
+
 __device__ __forceinline__ float pick4(const float (&w)[4], int j) { return j == 0 ? w[0] : (j == 1 ? w[1] : (j == 2 ? w[2] : w[3])); }
 
-// up(plane)[row taps ra / rb, ly][columns xl[0..3]]: xl non-decreasing (rev = 0) or non-increasing (rev = 1), neighbours at most 1 apart
+// up(plane)[row taps ra / rb, ly][columns xl[0..3]]: xl non-decreasing (rev = 0) or non-increasing (rev = 1), neighbours at most 1 apart.
+// The eight taps of the four outputs lie in four consecutive low-resolution columns (r < 1/2: four consecutive outputs advance the left
+// tap by at most 2), so two rows x four columns are loaded once and feed all four outputs.
 __device__ __forceinline__ void taps4(const float* __restrict__ ra, const float* __restrict__ rb, const int (&xl)[4], float r, int hl, float ly,
                                       int rev, float (&v)[4]) {
     int x0[4], x1[4];
@@ -98,6 +126,80 @@ __device__ __forceinline__ void taps4(const float* __restrict__ ra, const float*
         v[e] = bilerp(pick4(wa, x0[e] - c), pick4(wa, x1[e] - c), pick4(wb, x0[e] - c), pick4(wb, x1[e] - c), lx[e], ly);
 }
 
+// the source rows of full-resolution row yb of a box: the row itself, or (LOW: planes of side = crop / 2, the logits the engine holds
+// before output_conv) the two taps and weight of output_conv's x2 bilinear -- src_tap / bilerp (common.h), the arithmetic of
+// upsample2x_planes_kernel with its ry = rx = r, so a LOW value is the bit pattern the materialised full-resolution plane would hold
+template <bool LOW>
+__device__ __forceinline__ void row_taps(float r, int yb, int side, int& y0, int& y1, float& ly) {
+    y0 = y1 = yb;
+    ly = 0.f;
+    if (LOW) {
+        src_tap(r, yb, side, y0, y1, ly);
+        y0 = min(y0, side - 1); y1 = min(y1, side - 1);
+    }
+}
+
+// One box (plane p [side, side], columns from w0 of the map; its mirrored twin's plane at p + twin) at the run's columns xs: in[e] = valid[e]
+// and the box covers xs[e]; v[e] = box + twin there, added before the pair meets the accumulator.  The twin's value is that of the MIRRORED
+// full-resolution column crop - 1 - (x - w0) (LOW: the tap of that column; mirroring a value interpolated at x would round differently).
+// !LOW: four covered columns are consecutive logits -- one 16-byte load each for box and twin (descending) where the address allows, four
+// 4-byte loads otherwise; a run the box covers in part reads element by element.
+template <bool LOW>
+__device__ __forceinline__ void box_values(const float* __restrict__ p, size_t twin, int y0, int y1, float ly, const int (&xs)[4],
+                                           const bool (&valid)[4], int w0, int crop, int side, float r, int flip, bool (&in)[4], float (&v)[4]) {
+    int xl[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        in[e] = valid[e] && xs[e] >= w0 && xs[e] < w0 + crop;
+        xl[e] = min(max(xs[e] - w0, 0), crop - 1);
+        v[e] = 0.f;
+    }
+    if (LOW) {
+        taps4(p + (size_t)y0 * side, p + (size_t)y1 * side, xl, r, side, ly, 0, v);
+        if (flip) {
+            int xm[4];
+            float t[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xm[e] = crop - 1 - xl[e];
+            taps4(p + twin + (size_t)y0 * side, p + twin + (size_t)y1 * side, xm, r, side, ly, 1, t);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += t[e];
+        }
+        return;
+    }
+    const float* s = p + (size_t)y0 * crop;
+    if (all4(in)) {                                       // xl[e] = xl[0] + e
+        const float* a4 = s + xl[0];
+        if ((reinterpret_cast<uintptr_t>(a4) & 15) == 0) {
+            const f32x4_t t = *reinterpret_cast<const f32x4_t*>(a4);
+            v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = a4[e];
+        }
+        if (flip) {
+            const float* m4 = s + twin + (crop - 1 - xl[3]);   // the mirrored columns of e = 3, 2, 1, 0
+            if ((reinterpret_cast<uintptr_t>(m4) & 15) == 0) {
+                const f32x4_t t = *reinterpret_cast<const f32x4_t*>(m4);
+                v[0] += t[3]; v[1] += t[2]; v[2] += t[1]; v[3] += t[0];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += m4[3 - e];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (in[e]) {
+                v[e] = s[xl[e]];
+                if (flip) v[e] += s[twin + (crop - 1 - xl[e])];
+            }
+    }
+}
+
+// The whole grid of a scale from its low-resolution logits, low [(1 + flip) * n, K, crop / 2, crop / 2]: outputs [K, height, width] =
+// sum / count, every in-row element stored.  Bytes read per crop fall 4x against the full-resolution form and stay in L1 / L2 across
+// neighbouring runs.
 __global__ __launch_bounds__(256) void eval_accumulate_lowres_kernel(const float* __restrict__ low, float* __restrict__ outputs, int K, int height,
                                                                      int width, int crop, int stride, int h_grids, int w_grids, int flip) {
     const int hl = crop >> 1;
@@ -107,50 +209,31 @@ __global__ __launch_bounds__(256) void eval_accumulate_lowres_kernel(const float
     const int lane = threadIdx.x & 63;
     const int k = (int)((unsigned)row / (unsigned)height);              // rows < 2^31 (launcher)
     const int y = (int)((unsigned)row - (unsigned)k * (unsigned)height);
-    const float r = (float)(hl - 1) / (float)(crop - 1);              // upsample2x_planes_kernel's ry = rx for a (hl, hl) plane
+    const float r = (float)(hl - 1) / (float)(crop - 1);
     const size_t plane = (size_t)hl * hl;
     const size_t twin = (size_t)h_grids * w_grids * K * plane;
-    // covering boxes of the row: idh * stride <= y < idh * stride + crop (y < height <= ph: the clip to ph never cuts a map row)
-    const int h_lo = y < crop ? 0 : (y - crop) / stride + 1;
-    const int h_hi = min(y / stride, h_grids - 1);
+    const CoverRange hc = cover_range(y, crop, stride, h_grids);
     float* orow = outputs + row * (size_t)width;
-    const int shift = (int)((reinterpret_cast<uintptr_t>(orow) >> 2) & 3);      // run q covers x = 4 q - shift .. + 3
-    const int nq = (width + shift + 3) >> 2;
+    const bool every[4] = {true, true, true, true};
+    int shift, nq;
+    run_frame(orow, 0, width, shift, nq);
     for (int q = lane; q < nq; q += 64) {
         const int xb = 4 * q - shift;
         int xs[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xs[e] = min(max(xb + e, 0), width - 1);     // partial runs compute a neighbour's value and do not store it
-        const int w_lo = xs[0] < crop ? 0 : (xs[0] - crop) / stride + 1;
-        const int w_hi = min(xs[3] / stride, w_grids - 1);
+        bool valid[4];
+        run_columns(xb, 0, width, width, xs, valid);
+        const int w_lo = cover_range(xs[0], crop, stride, w_grids).lo, w_hi = cover_range(xs[3], crop, stride, w_grids).hi;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         int cnt[4] = {0, 0, 0, 0};
-        for (int idh = h_lo; idh <= h_hi; ++idh) {
+        for (int idh = hc.lo; idh <= hc.hi; ++idh) {
             int y0, y1;
             float ly;
-            src_tap(r, y - idh * stride, hl, y0, y1, ly);
-            y0 = min(y0, hl - 1); y1 = min(y1, hl - 1);
+            row_taps<true>(r, y - idh * stride, hl, y0, y1, ly);
             for (int idw = w_lo; idw <= w_hi; ++idw) {
-                const int w0 = idw * stride;
-                const float* p = low + ((size_t)(idh * w_grids + idw) * K + k) * plane;
-                int xl[4];
                 bool in[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    in[e] = xs[e] >= w0 && xs[e] < w0 + crop;
-                    xl[e] = min(max(xs[e] - w0, 0), crop - 1);
-                }
                 float v[4];
-                taps4(p + (size_t)y0 * hl, p + (size_t)y1 * hl, xl, r, hl, ly, 0, v);
-                if (flip) {
-                    int xm[4];
-                    float t[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xm[e] = crop - 1 - xl[e];
-                    taps4(p + twin + (size_t)y0 * hl, p + twin + (size_t)y1 * hl, xm, r, hl, ly, 1, t);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += t[e];
-                }
+                box_values<true>(low + ((size_t)(idh * w_grids + idw) * K + k) * plane, twin, y0, y1, ly, xs, every, idw * stride, crop, hl, r,
+                                 flip, in, v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (in[e]) { acc[e] += v[e]; cnt[e] += 1; }
@@ -159,27 +242,15 @@ __global__ __launch_bounds__(256) void eval_accumulate_lowres_kernel(const float
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = acc[e] / (float)cnt[e];
-        if (xb >= 0 && xb + 3 < width) {
-            const f32x4_t ov = {o[0], o[1], o[2], o[3]};
-            *reinterpret_cast<f32x4_t*>(orow + xb) = ov;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (xb + e >= 0 && xb + e < width) orow[xb + e] = o[e];
-        }
+        store_run(orow, xb, o, valid);
     }
 }
 
 // A WINDOW of a scale's grid: boxes [first, first + nbox) in (idh, idw) order, outs [(1 + flip) * nbox, K, side, side] holding only their
-// logits (LOW: side = crop / 2, read through the x2 bilinear exactly as eval_accumulate_lowres_kernel does; else side = crop).  For every
-// map pixel some box of the window covers, sum[k, y, x] takes, in ascending box order, += out + flip_x(twin) -- the additions the
-// one-launch kernels make from 0.f, continued from the fp32 partial sum in memory, so windows submitted in ascending order leave the bits
-// of their un-divided acc (eval_finalize_kernel divides).  A pixel no box of the window covers is neither read nor written.
-//
-// Work comes from the window's footprint: rows y_lo .. y_lo + ny - 1 and columns [x_lo, x_hi) are the bounding rectangle of its boxes
-// on the map (the launcher), one wave per (k, y), four rows per block, a lane produces runs of four consecutive x shifted so that every
-// interior run is a 16-byte aligned load + store of sum.  Per run and box the four logits (and the twin's, at the mirrored columns
-// crop - 1 - (x - w0), descending) are one 16-byte load each where the address allows, four 4-byte loads otherwise.
+// logits (LOW: side = crop / 2, else side = crop).  For every map pixel some box of the window covers, sum[k, y, x] += the window's
+// covering boxes, so windows submitted in ascending order leave the bits of the one-launch kernels' un-divided acc.  A pixel no box of
+// the window covers is neither read nor written.  Rows y_lo .. y_lo + ny - 1 and columns [x_lo, x_hi) are the bounding rectangle of the
+// window's boxes on the map (the launcher).
 template <bool LOW>
 __global__ __launch_bounds__(256) void eval_accumulate_window_kernel(const float* __restrict__ outs, float* __restrict__ sum, int K, int height,
                                                                      int width, int crop, int stride, int w_grids, int flip, int first, int nbox,
@@ -190,30 +261,24 @@ __global__ __launch_bounds__(256) void eval_accumulate_window_kernel(const float
     const int k = (int)((unsigned)row / (unsigned)ny);                  // K * ny < 2^31 (launcher)
     const int y = y_lo + (int)((unsigned)row - (unsigned)k * (unsigned)ny);
     const int side = LOW ? crop >> 1 : crop;
-    const float r = (float)(side - 1) / (float)(crop - 1);            // LOW only: upsample2x_planes_kernel's ry = rx
+    const float r = (float)(side - 1) / (float)(crop - 1);            // LOW only
     const size_t plane = (size_t)side * side;
     const size_t twin = (size_t)nbox * K * plane;
     const int last = first + nbox - 1;
     const int ih_a = first / w_grids, ih_b = last / w_grids;
     const int iw_a = first - ih_a * w_grids, iw_b = last - ih_b * w_grids;
-    // the window's grid rows covering y: idh * stride <= y < idh * stride + crop (y < height <= ph: the clip to ph never cuts a map row)
-    const int h_lo = max(y < crop ? 0 : (y - crop) / stride + 1, ih_a);
-    const int h_hi = min(y / stride, ih_b);
+    const CoverRange hc = cover_range(y, crop, stride, ih_b + 1);       // the window's grid rows covering y: from ih_a, up to ih_b
+    const int h_lo = max(hc.lo, ih_a), h_hi = hc.hi;
     if (h_lo > h_hi) return;
     float* orow = sum + ((size_t)k * height + y) * (size_t)width;
-    const int shift = (int)((reinterpret_cast<uintptr_t>(orow + x_lo) >> 2) & 3);      // run q covers x = x_lo + 4 q - shift .. + 3
-    const int nq = (x_hi - x_lo + shift + 3) >> 2;
+    int shift, nq;
+    run_frame(orow, x_lo, x_hi, shift, nq);
     for (int q = lane; q < nq; q += 64) {
         const int xb = x_lo + 4 * q - shift;
         int xs[4];
         bool valid[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            valid[e] = xb + e >= x_lo && xb + e < x_hi;
-            xs[e] = min(max(xb + e, 0), width - 1);
-        }
-        const int w_lo = xs[0] < crop ? 0 : (xs[0] - crop) / stride + 1;
-        const int w_hi = min(xs[3] / stride, w_grids - 1);
+        run_columns(xb, x_lo, x_hi, width, xs, valid);
+        const int w_lo = cover_range(xs[0], crop, stride, w_grids).lo, w_hi = cover_range(xs[3], crop, stride, w_grids).hi;
         // which of the four pixels the window covers at all: only those touch sum
         bool cov[4] = {false, false, false, false};
         for (int idh = h_lo; idh <= h_hi; ++idh) {
@@ -225,9 +290,8 @@ __global__ __launch_bounds__(256) void eval_accumulate_window_kernel(const float
             }
         }
         if (!(cov[0] || cov[1] || cov[2] || cov[3])) continue;
-        const bool whole = cov[0] && cov[1] && cov[2] && cov[3];           // then xb .. xb + 3 lie in the row and the run is 16-byte aligned
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (whole) {
+        if (all4(cov)) {                                                   // as store_run
             const f32x4_t sv = *reinterpret_cast<const f32x4_t*>(orow + xb);
             acc[0] = sv[0]; acc[1] = sv[1]; acc[2] = sv[2]; acc[3] = sv[3];
         } else {
@@ -237,88 +301,29 @@ __global__ __launch_bounds__(256) void eval_accumulate_window_kernel(const float
         }
         for (int idh = h_lo; idh <= h_hi; ++idh) {
             const int a = max(w_lo, idh == ih_a ? iw_a : 0), b = min(w_hi, idh == ih_b ? iw_b : w_grids - 1);
-            int y0 = y - idh * stride, y1 = y0;
-            float ly = 0.f;
-            if (LOW) {
-                src_tap(r, y - idh * stride, side, y0, y1, ly);
-                y0 = min(y0, side - 1); y1 = min(y1, side - 1);
-            }
+            int y0, y1;
+            float ly;
+            row_taps<LOW>(r, y - idh * stride, side, y0, y1, ly);
             for (int idw = a; idw <= b; ++idw) {
-                const int w0 = idw * stride;
-                const float* p = outs + ((size_t)(idh * w_grids + idw - first) * K + k) * plane;
                 bool in[4];
-                int xl[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    in[e] = valid[e] && xs[e] >= w0 && xs[e] < w0 + crop;
-                    xl[e] = min(max(xs[e] - w0, 0), crop - 1);
-                }
-                float v[4] = {0.f, 0.f, 0.f, 0.f};
-                if (LOW) {
-                    taps4(p + (size_t)y0 * side, p + (size_t)y1 * side, xl, r, side, ly, 0, v);
-                    if (flip) {
-                        int xm[4];
-                        float t[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) xm[e] = crop - 1 - xl[e];
-                        taps4(p + twin + (size_t)y0 * side, p + twin + (size_t)y1 * side, xm, r, side, ly, 1, t);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += t[e];
-                    }
-                } else {
-                    const float* s = p + (size_t)y0 * crop;
-                    if (in[0] && in[1] && in[2] && in[3]) {                 // xl[e] = xl[0] + e: four consecutive logits
-                        const float* a4 = s + xl[0];
-                        if ((reinterpret_cast<uintptr_t>(a4) & 15) == 0) {
-                            const f32x4_t t = *reinterpret_cast<const f32x4_t*>(a4);
-                            v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = a4[e];
-                        }
-                        if (flip) {
-                            const float* m4 = s + twin + (crop - 1 - xl[3]);   // the mirrored columns of e = 3, 2, 1, 0
-                            if ((reinterpret_cast<uintptr_t>(m4) & 15) == 0) {
-                                const f32x4_t t = *reinterpret_cast<const f32x4_t*>(m4);
-                                v[0] += t[3]; v[1] += t[2]; v[2] += t[1]; v[3] += t[0];
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] += m4[3 - e];
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (in[e]) {
-                                v[e] = s[xl[e]];
-                                if (flip) v[e] += s[twin + (crop - 1 - xl[e])];
-                            }
-                    }
-                }
+                float v[4];
+                box_values<LOW>(outs + ((size_t)(idh * w_grids + idw - first) * K + k) * plane, twin, y0, y1, ly, xs, valid, idw * stride, crop,
+                                side, r, flip, in, v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (in[e]) acc[e] += v[e];
             }
         }
-        if (whole) {
-            const f32x4_t ov = {acc[0], acc[1], acc[2], acc[3]};
-            *reinterpret_cast<f32x4_t*>(orow + xb) = ov;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (cov[e]) orow[xb + e] = acc[e];
-        }
+        store_run(orow, xb, acc, cov);
     }
 }
 
 // map = sum / (number of boxes of the WHOLE grid covering the pixel): the division of the one-launch kernels (their count as a float).
 // Element-wise, so map == sum is fine; 16 bytes per lane where both pointers allow.
 __device__ __forceinline__ float eval_cover_count(size_t i, int height, int width, int crop, int stride, int h_grids, int w_grids) {
-    const int x = (int)(i % width);
-    const int y = (int)((i / width) % height);
-    const int nh = min(y / stride, h_grids - 1) - (y < crop ? 0 : (y - crop) / stride + 1) + 1;
-    const int nw = min(x / stride, w_grids - 1) - (x < crop ? 0 : (x - crop) / stride + 1) + 1;
-    return (float)(nh * nw);
+    const CoverRange hc = cover_range((int)((i / width) % height), crop, stride, h_grids);
+    const CoverRange wc = cover_range((int)(i % width), crop, stride, w_grids);
+    return (float)((hc.hi - hc.lo + 1) * (wc.hi - wc.lo + 1));
 }
 __global__ void eval_finalize_kernel(const float* sum, float* map, size_t total, int height, int width, int crop, int stride, int h_grids,
                                      int w_grids, int vec) {
@@ -375,8 +380,8 @@ int launch_eval_accumulate(const float* outs, float* outputs, int K, int height,
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }
-int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride,
-                                  int h_grids, int w_grids, int flip, hipStream_t st) {
+int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,
+                                  int flip, hipStream_t st) {
     const size_t rows = (size_t)K * height;
     if (rows > 0x7fffffffu) return set_error(LSEG_ERR_UNSUPPORTED, "eval_accumulate_lowres: too many rows");
     hipLaunchKernelGGL(eval_accumulate_lowres_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, low, outputs, K, height, width, crop,

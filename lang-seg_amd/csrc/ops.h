@@ -206,8 +206,8 @@ int launch_eval_make_crops(const float* img, float* crops, int C, int height, in
                            int flip, const float* pad3, hipStream_t st);
 int launch_eval_accumulate(const float* outs, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
                            int w_grids, int flip, hipStream_t st);
-int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int ph, int pw, int crop, int stride,
-                                  int h_grids, int w_grids, int flip, hipStream_t st);
+int launch_eval_accumulate_lowres(const float* low, float* outputs, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,
+                                  int flip, hipStream_t st);
 int launch_eval_accumulate_window(const float* outs, float* sum, int K, int height, int width, int crop, int stride, int w_grids, int flip,
                                   int first, int nbox, int lowres, hipStream_t st);
 int launch_eval_finalize(const float* sum, float* map, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,

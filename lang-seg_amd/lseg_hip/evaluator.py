@@ -15,16 +15,31 @@ logits through that bilinear on the fly: the same scores bit for bit, a quarter 
 """
 import ctypes as C
 import math
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 
-def scale_geometry(h: int, w: int, scale: float, base_size: int, crop_size: int):
-    """Sizes of one scale of MultiEvalModule.forward (encoding_models.py:66-99): the resized image (height, width), the padded image
-    the sliding window runs over (ph, pw), the crop grid (h_grids, w_grids) and the stride.  One crop when the long side fits."""
+class ScaleGeometry(NamedTuple):
+    """Sizes of one scale: the resized image (height, width), the padded image the sliding window runs over (ph, pw), the crop grid
+    (h_grids, w_grids) and the stride."""
+    height: int
+    width: int
+    ph: int
+    pw: int
+    h_grids: int
+    w_grids: int
+    stride: int
+
+    @property
+    def n_box(self) -> int:
+        return self.h_grids * self.w_grids
+
+
+def scale_geometry(h: int, w: int, scale: float, base_size: int, crop_size: int) -> ScaleGeometry:
+    """The sizes of one scale of MultiEvalModule.forward (encoding_models.py:66-99).  One crop when the long side fits."""
     stride = int(crop_size * 2.0 / 3.0)
     long_size = int(math.ceil(base_size * scale))
     if h > w:
@@ -37,7 +52,7 @@ def scale_geometry(h: int, w: int, scale: float, base_size: int, crop_size: int)
     else:
         h_grids = int(math.ceil(1.0 * (ph - crop_size) / stride)) + 1
         w_grids = int(math.ceil(1.0 * (pw - crop_size) / stride)) + 1
-    return height, width, ph, pw, h_grids, w_grids, stride
+    return ScaleGeometry(height, width, ph, pw, h_grids, w_grids, stride)
 
 
 def window_partition(n_box: int, max_crops: int, flip: bool):
@@ -48,6 +63,41 @@ def window_partition(n_box: int, max_crops: int, flip: bool):
     if per < 1:
         raise ValueError(f"max_stack={max_crops} holds no box{' with its mirrored twin' if flip else ''}: it must be at least {2 if flip else 1}")
     return [(first, min(per, n_box - first)) for first in range(0, n_box, per)]
+
+
+class Step(NamedTuple):
+    """One step of the device evaluator's schedule: `scales` (consecutive indices) go through the network as one stack, or -- `windows`
+    not None, one scale -- that scale's grid goes through as windows [(first_box, n_box), ...], one forward group each."""
+    scales: List[int]
+    windows: Optional[List[Tuple[int, int]]] = None
+
+
+def plan_schedule(geo: Sequence[ScaleGeometry], flip: bool, max_stack: int, max_batch: int) -> Tuple[List[Step], int]:
+    """The schedule of one image: (steps, crops of the largest forward group).  EVERY crop of EVERY scale is crop x crop, so consecutive
+    scales share a stack while at most `max_stack` crops (mirrored twins included; their [K, crop, crop] fp32 logits are 138 MB per crop
+    at K = 150, crop 480 -- a quarter of that with lowres) are alive at once: a 4:3 ADE image (36 crops) is ONE batch-36 forward where a
+    forward per scale ran six of 2 .. 12 crops, each at the low-occupancy end of the engine's batch sweep, and a larger image / longer
+    scale list runs as several stacks instead of one unbounded allocation (DESIGN par. 3.8).  A scale that alone has more crops than
+    max_stack (base 2048 / crop 480 is an 11 x 6 grid at scale 1.75) is a step of its own and runs as windows of whole boxes, each at
+    most max_batch crops -- one forward -- where a box and its twin fit in that."""
+    twins = 2 if flip else 1
+    crops = [twins * g.n_box for g in geo]
+    steps, cur, cur_n = [], [], 0
+    for i, nc in enumerate(crops):
+        if cur and cur_n + nc > max_stack:
+            steps.append(Step(cur))
+            cur, cur_n = [], 0
+        cur.append(i)
+        cur_n += nc
+    if cur:
+        steps.append(Step(cur))
+    per_fwd = min(max_stack, max_batch)
+    for s, step in enumerate(steps):
+        i = step.scales[0]
+        if crops[i] > max_stack:             # then the grouping above left it alone
+            steps[s] = Step([i], window_partition(geo[i].n_box, per_fwd if per_fwd >= twins else max_stack, flip))
+    largest = max(sum(crops[i] for i in st.scales) if st.windows is None else max(twins * nb for _, nb in st.windows) for st in steps)
+    return steps, largest
 
 
 def _pad_image(img, mean, std, crop_size):          # encoding_models.py:144-155
@@ -128,12 +178,7 @@ class BatchedMultiEval(torch.nn.Module):
     def _infer(self, crops: torch.Tensor, label_set) -> torch.Tensor:
         """module_inference (encoding_models.py:133-139) for a stack of crops: out = f(x) + flip(f(flip(x)))."""
         xs = torch.cat([crops, torch.flip(crops, dims=[3])], dim=0) if self.flip else crops
-        outs = []
-        for i in range(0, xs.shape[0], self.max_batch):
-            chunk = xs[i:i + self.max_batch].contiguous()
-            outs.append(self.module.evaluate(chunk) if label_set is None
-                        else self.module.evaluate_random(chunk, label_set))
-        out = torch.cat(outs, dim=0)
+        out = self._chunked(xs, label_set, lowres=False)
         if self.flip:
             n = crops.shape[0]
             out = out[:n] + torch.flip(out[n:], dims=[3])
@@ -143,15 +188,18 @@ class BatchedMultiEval(torch.nn.Module):
         """list of [3,h,w] images in, list of [1,nclass,h,w] score maps out (encoding_models.py:35-52)."""
         return [self.forward(img.unsqueeze(0).cuda(), label_set) for img in inputs]
 
-    def _module_eval(self, xs: torch.Tensor, label_set) -> torch.Tensor:
-        if self.lowres:
-            ev = self.module.evaluate_lowres if label_set is None else (lambda c: self.module.evaluate_random_lowres(c, label_set))
+    def _chunked(self, xs: torch.Tensor, label_set, lowres: bool) -> torch.Tensor:
+        """The module's logits of a stack of crops, max_batch crops per forward."""
+        suffix = "_lowres" if lowres else ""
+        if label_set is None:
+            ev = getattr(self.module, "evaluate" + suffix)
         else:
-            ev = self.module.evaluate if label_set is None else (lambda c: self.module.evaluate_random(c, label_set))
-        outs = []
-        for i in range(0, xs.shape[0], self.max_batch):
-            outs.append(ev(xs[i:i + self.max_batch]))
+            ev = lambda c: getattr(self.module, "evaluate_random" + suffix)(c, label_set)      # noqa: E731
+        outs = [ev(xs[i:i + self.max_batch].contiguous()) for i in range(0, xs.shape[0], self.max_batch)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    def _module_eval(self, xs: torch.Tensor, label_set) -> torch.Tensor:
+        return self._chunked(xs, label_set, self.lowres)
 
     @torch.no_grad()
     def _forward_device(self, image: torch.Tensor, label_set=None) -> torch.Tensor:
@@ -169,90 +217,68 @@ class BatchedMultiEval(torch.nn.Module):
         pad = (C.c_float * 3)(*[float(v) for v in (-np.array(self.module.mean) / np.array(self.module.std))])
         image = image.contiguous()
         scores = image.new_zeros((1, nclass, h, w))
-        # EVERY crop of EVERY scale is crop x crop: all of them (and their mirrored twins) go through the network as ONE stack, in chunks of
-        # max_batch -- a 4:3 ADE image is 36 crops = one batch-36 forward where the per-scale form ran six forwards of 2 .. 12 crops, each at
-        # the low-occupancy end of the engine's batch sweep (DESIGN par. 3.8).  Crops are independent in the engine, so the per-crop logits
-        # are those of the per-scale form (bit for bit under the batch-invariant schedule).
-        twins = 2 if self.flip else 1
-        geo = []
-        for scale in self.scales:
-            height, width, ph, pw, h_grids, w_grids, stride = scale_geometry(h, w, scale, self.base_size, crop)
-            geo.append((height, width, ph, pw, h_grids, w_grids, stride, twins * h_grids * w_grids))
-
-        def make_crops(i):                   # a scale's crops exist from its group's turn on, not before
-            height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
-            cur = image.new_empty((ch, height, width))
-            _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, height, width, 0, st))
-            crops = image.new_empty((nc, ch, crop, crop))
-            _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, height, width, crop, stride, h_grids, w_grids, int(self.flip), pad, st))
-            return crops
-        # ... grouped so that at most `max_stack` crops (and their [n, K, crop, crop] fp32 logits: 138 MB per crop at K = 150, crop 480) are
-        # alive at once: consecutive scales share a forward while they fit -- a 4:3 ADE image (36 crops) is still ONE batch -- and a larger
-        # image / longer scale list runs as several stacks instead of one unbounded allocation
-        # (lowres: the logits of a crop are [K, crop/2, crop/2], 34.6 MB -- the same bound on memory admits four times the crops)
-        # A scale that alone has more crops than max_stack (base_size / crop_size and the aspect ratio decide: base 2048 / crop 480 is an
-        # 11 x 6 grid at scale 1.75) is a group of its own and runs as WINDOWS of whole boxes, each one forward (at most max_batch crops
-        # where a box and its twin fit in that): lseg_op_eval_accumulate_window adds a window's logits into the scale's fp32 sum in box
-        # order, lseg_op_eval_finalize divides -- the additions and the division of the one-launch kernel, so the same bits.
+        flip, twins = int(self.flip), 2 if self.flip else 1
+        side = crop // 2 if self.lowres else crop
+        geo = [scale_geometry(h, w, scale, self.base_size, crop) for scale in self.scales]
         max_stack = getattr(self, "max_stack", None)
         if max_stack is None:
             max_stack = self._max_stack if self._max_stack is not None else (192 if self.lowres else 48)
-        max_stack = int(max_stack)
-        side = crop // 2 if self.lowres else crop
-        accumulate = lib.lseg_op_eval_accumulate_lowres if self.lowres else lib.lseg_op_eval_accumulate
-        groups, cur_g, cur_n = [], [], 0
-        for i, g_ in enumerate(geo):
-            if cur_g and cur_n + g_[7] > max_stack:
-                groups.append(cur_g)
-                cur_g, cur_n = [], 0
-            cur_g.append(i)
-            cur_n += g_[7]
-        if cur_g:
-            groups.append(cur_g)
-        windows = {}                         # scale -> [(first_box, n_box), ...] for the scales that do not fit
-        for grp in groups:
-            i = grp[0]
-            if geo[i][7] > max_stack:        # then the grouping above left it alone
-                per_fwd = min(max_stack, self.max_batch)
-                windows[i] = window_partition(geo[i][4] * geo[i][5], per_fwd if per_fwd >= twins else max_stack, self.flip)
+        steps, largest = plan_schedule(geo, self.flip, int(max_stack), self.max_batch)
         # the largest forward of this call, known before the first: the wrapped network sizes its engine once instead of growing it
         # (closing and rebuilding it) when a later stack is larger than the first
-        largest = max(max(twins * nb for _, nb in windows[grp[0]]) if grp[0] in windows else sum(geo[i][7] for i in grp) for grp in groups)
         net = getattr(self.module, "net", None)
         if callable(getattr(net, "reserve_batch", None)):
             net.reserve_batch(min(self.max_batch, largest), crop, crop, None if label_set is None else nclass, image.device)
-        for grp in groups:
-            if grp[0] in windows:
-                i = grp[0]
-                height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
-                n = h_grids * w_grids
-                crops = make_crops(i)
-                smap = image.new_zeros((nclass, height, width))
-                accumulate_window = lib.lseg_op_eval_accumulate_window_lowres if self.lowres else lib.lseg_op_eval_accumulate_window
-                for first, nb in windows[i]:
+
+        def make_crops(g):                   # a scale's crops exist from its step's turn on, not before
+            cur = image.new_empty((ch, g.height, g.width))
+            _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, g.height, g.width, 0, st))
+            crops = image.new_empty((twins * g.n_box, ch, crop, crop))
+            _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip, pad, st))
+            return crops
+
+        def logits(xs):                      # crops are independent in the engine: the per-crop logits do not depend on the grouping
+            outs = self._module_eval(xs, label_set).contiguous()
+            assert outs.shape == (xs.shape[0], nclass, side, side) and outs.dtype == torch.float32
+            return outs
+
+        def dims(g):                         # the geometry arguments the accumulate and finalize entries share
+            return nclass, g.height, g.width, g.ph, g.pw, crop, g.stride, g.h_grids, g.w_grids
+
+        def add_resized(smap, g):            # scores += bilinear(map of the scale)
+            _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, g.height, g.width, h, w, 1, st))
+
+        accumulate = lib.lseg_op_eval_accumulate_lowres if self.lowres else lib.lseg_op_eval_accumulate
+        accumulate_window = lib.lseg_op_eval_accumulate_window_lowres if self.lowres else lib.lseg_op_eval_accumulate_window
+        for step in steps:
+            stacks = [make_crops(geo[i]) for i in step.scales]
+            if step.windows is None:         # one stack: every scale's slice of its logits through the one-launch kernel
+                xs = torch.cat(stacks, dim=0) if len(stacks) > 1 else stacks[0]
+                outs = logits(xs)
+                o0 = 0
+                for i in step.scales:
+                    g = geo[i]
+                    nc = twins * g.n_box
+                    smap = image.new_empty((nclass, g.height, g.width))
+                    _lib.check(accumulate(P(outs[o0:o0 + nc]), P(smap), *dims(g), flip, st))     # a contiguous slice: this scale's crops (+ twins)
+                    add_resized(smap, g)
+                    o0 += nc
+                del outs, xs
+            else:                            # windows add into the scale's fp32 sum in box order, finalize divides: the same bits
+                g, crops = geo[step.scales[0]], stacks[0]
+                n = g.n_box
+                smap = image.new_zeros((nclass, g.height, g.width))
+                for first, nb in step.windows:
                     xs = torch.cat([crops[first:first + nb], crops[n + first:n + first + nb]], dim=0) if self.flip else crops[first:first + nb]
-                    outs = self._module_eval(xs, label_set).contiguous()
-                    assert outs.shape == (xs.shape[0], nclass, side, side) and outs.dtype == torch.float32
-                    _lib.check(accumulate_window(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, int(self.flip),
-                                                 first, nb, st))
-                    del outs, xs
-                _lib.check(lib.lseg_op_eval_finalize(P(smap), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, st))
-                _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, height, width, h, w, 1, st))
-                del crops, smap
-                continue
-            stacks = {i: make_crops(i) for i in grp}
-            allc = torch.cat([stacks[i] for i in grp], dim=0) if len(grp) > 1 else stacks[grp[0]]
-            outs_all = self._module_eval(allc, label_set).contiguous()
-            assert outs_all.shape == (allc.shape[0], nclass, side, side) and outs_all.dtype == torch.float32
-            o0 = 0
-            for i in grp:
-                height, width, ph, pw, h_grids, w_grids, stride, nc = geo[i]
-                outs = outs_all[o0:o0 + nc]                                   # a contiguous slice: this scale's crops (+ twins)
-                o0 += nc
-                smap = image.new_empty((nclass, height, width))
-                _lib.check(accumulate(P(outs), P(smap), nclass, height, width, ph, pw, crop, stride, h_grids, w_grids, int(self.flip), st))
-                _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), nclass, height, width, h, w, 1, st))
-            del outs_all, outs, allc, stacks, smap       # `outs` is a view of the stack: left bound, it keeps the logits alive into the next group
+                    outs = logits(xs)
+                    _lib.check(accumulate_window(P(outs), P(smap), *dims(g), flip, first, nb, st))
+                    del outs, xs             # one window's logits alive at a time
+                _lib.check(lib.lseg_op_eval_finalize(P(smap), P(smap), *dims(g), st))
+                add_resized(smap, g)
+                del crops
+            # nothing of a step stays bound: a name (or a view of the stack) left over keeps its logits alive into the next step's forward
+            # (profiles/eval_window.txt: 13 454 MB against 10 553 MB)
+            del stacks, smap
         return scores
 
     @torch.no_grad()

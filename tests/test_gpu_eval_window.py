@@ -57,7 +57,16 @@ def _gather(outs, n, first, nb, flip):
     return (torch.cat([outs[first:first + nb], outs[n + first:n + first + nb]], dim=0) if flip else outs[first:first + nb]).contiguous()
 
 
-def _windowed(outs, geo, flip, part, lowres=False, in_place=True):
+def _one_float_past_16_bytes(t):
+    """The same values in memory that starts 4 bytes past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    view = buf[1:1 + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+    return view
+
+
+def _windowed(outs, geo, flip, part, lowres=False, in_place=True, misalign=False):
     _lib, lib = _lib_()
     (hg, wg), (height, width), (ph, pw) = geo
     n = hg * wg
@@ -67,6 +76,8 @@ def _windowed(outs, geo, flip, part, lowres=False, in_place=True):
     first = 0
     for nb in part:
         win = _gather(outs, n, first, nb, flip)
+        if misalign:
+            win = _one_float_past_16_bytes(win)
         _lib.check(fn(_P(win), _P(ssum), K, height, width, ph, pw, CROP, STRIDE, hg, wg, int(flip), first, nb, _stream()))
         first += nb
     out = ssum if in_place else torch.empty_like(ssum)
@@ -105,6 +116,21 @@ def test_lowres_windows_equal_the_lowres_kernel_and_the_full_resolution_windows(
     torch.cuda.synchronize()
     assert torch.equal(got, want_lowres), (got - want_lowres).abs().max().item()
     assert torch.equal(got, want_full), (got - want_full).abs().max().item()
+
+
+@pytest.mark.parametrize("lowres", [False, True])
+@pytest.mark.parametrize("flip", [0, 1])
+def test_windows_on_logits_one_float_past_a_16_byte_boundary(flip, lowres):
+    """Every window's logits start 4 bytes past a 16-byte boundary: the full-resolution box reads its four consecutive logits (and the
+    twin's) with four 4-byte loads wherever the address is not a multiple of 16, the low-resolution taps read unaligned rows.  The same
+    bits as the one-launch entry on an aligned copy of the values (the tests above move the sum's alignment, not the logits')."""
+    geo = GEOMETRIES["19x14"]
+    outs = _logits(geo[0][0] * geo[0][1], flip, CROP // 2 if lowres else CROP, seed=15)
+    want = _one_launch(outs, geo, flip, lowres=lowres)
+    got = _windowed(outs, geo, flip, (5, 5, 2), lowres=lowres, misalign=True)
+    torch.cuda.synchronize()
+    assert torch.isfinite(want).all()
+    assert torch.equal(got, want), (got - want).abs().max().item()
 
 
 def _footprint(geo, first, nb):
