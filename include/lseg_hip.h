@@ -195,6 +195,21 @@ int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out
  * LSEG_ERR_STATE until another forward has run.  K > 32767, train mode: LSEG_ERR_UNSUPPORTED. */
 int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, void* stream);
 
+/* lseg_forward_labels with a confidence: the runner-up and the log-sum-exp over all labels beside the arg-max, still without the logits.
+ * replaces: torch.topk(pred, 2, 1) and torch.logsumexp(pred, 1) on the logits of lseg_net.py:194-203 (what a caller needs for the softmax
+ *   probability of the winner, exp(score - lse), and the top-2 margin, score - score2) -- the [B,K,img_h,img_w] logits are not written.
+ *   dev_label_out / dev_score_out: as in lseg_forward_labels, bit for bit
+ *   dev_label2_out int16, dev_score2_out fp32 [B,img_h,img_w]: the largest logit among the labels != label and its label; equal values go
+ *                  to the lower label, so (label, label2) are entries 0 and 1 of a stable descending sort over the labels and a later
+ *                  label that EQUALS the winner is the runner-up.  One label (K = 1, or one label per image): label2 = -1, score2 = -inf
+ *   dev_lse_out    fp32 [B,img_h,img_w]: log(sum_k exp(logit_k)), accumulated online in fp32 as score + log(sum_k exp(logit_k - running max))
+ * Each of the last three may be NULL.  Streamed under the conditions of lseg_forward_labels (csrc/corr_argmax.hip, the CONF instantiation:
+ * the running state grows from (best, label) to (best, second, both labels, sum)); every other configuration reduces the low-resolution
+ * logits through the x2 bilinear on the fly.  State rules and errors as for lseg_forward_labels: after a STREAMED forward no
+ * low-resolution logits exist; K > 32767 and train mode: LSEG_ERR_UNSUPPORTED; a NULL x or label output: LSEG_ERR_INVALID. */
+int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, int16_t* dev_label2_out,
+                             float* dev_score2_out, float* dev_lse_out, void* stream);
+
 /* The logits BEFORE scratch.output_conv (lseg_net.py:203), for callers that read them through the x2 bilinear themselves (the
  * multi-scale evaluator's lseg_op_eval_accumulate_lowres): the inference forward exactly as lseg_forward runs it -- text cache, external
  * text features, per-image label sets (Kout = labels per image), overflow sentinel, profiling and the arch_option 1/2 head blocks
@@ -415,6 +430,16 @@ int lseg_op_corr_planes(const void* d_g16pad, const void* d_text16, float* d_pla
  * LSEG_ERR_UNSUPPORTED for other C, K > 32767 or maps beyond the kernel's 32-bit offsets. */
 int lseg_op_corr_argmax(const void* d_g16pad, const void* d_text16, const float* d_scale, int16_t* d_label, float* d_score, int B, int K,
                         int H, int W, int C, void* d_ws, size_t ws_bytes, void* stream);
+/* lseg_op_corr_argmax with the confidence outputs of lseg_forward_labels_conf, bare.
+ * replaces: torch.topk(pred, 2, 1) and torch.logsumexp(pred, 1) on the logits of lseg_net.py:194-203, for any K: d_label / d_score are
+ *   lseg_op_corr_argmax's bit for bit; (d_label2, d_score2) = entry 1 of a stable descending sort over k of the values
+ *   lseg_op_upsample4x_planes_scaled would write (K = 1: -1 / -inf); d_lse = their log-sum-exp (fp32, online).
+ * d_label2 int16, d_score2 / d_lse fp32 [B, 4H, 4W], each or NULL (all NULL = lseg_op_corr_argmax).  d_ws / ws_bytes: with 256 B H W bytes
+ * per part (16 per output pixel: five planes) the labels of a tile are split and merged in ascending order -- top-2 by the same rule
+ * (bit-equal), lse by log-add-exp (another summation order: equal within fp32 rounding).  Errors as lseg_op_corr_argmax. */
+int lseg_op_corr_argmax_conf(const void* d_g16pad, const void* d_text16, const float* d_scale, int16_t* d_label, float* d_score,
+                             int16_t* d_label2, float* d_score2, float* d_lse, int B, int K, int H, int W, int C, void* d_ws, size_t ws_bytes,
+                             void* stream);
 /* The tile geometry that kernel was compiled with (host memory, no device needed), for the CPU index model of its tile -> footprint
  * mapping: out8 = {mid rows/columns per tile band, mid rows/columns of its footprint, base rows/columns of its footprint, labels per
  * panel, LDS pitch of a text row in bytes, labels per interpolation chunk, output rows per wave, dynamic LDS bytes}. */

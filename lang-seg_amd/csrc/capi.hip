@@ -98,6 +98,14 @@ int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_l
     return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out);
 }
 
+int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, int16_t* dev_label2_out,
+                             float* dev_score2_out, float* dev_lse_out, void* stream) {
+    GUARD(h);
+    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
+    const Engine::LabelConf conf{dev_label2_out, dev_score2_out, dev_lse_out};
+    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out, nullptr, &conf);
+}
+
 int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream) {
     GUARD(h);
     if (!dev_low_out) return set_error(LSEG_ERR_INVALID, "low-resolution logits output is NULL");
@@ -411,6 +419,11 @@ int lseg_op_head_features(const void* x_bf16, const void* w_bf16, const float* b
 int lseg_op_corr_argmax(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int B, int K, int H, int W,
                         int C, void* d_ws, size_t ws_bytes, void* stream) {
     return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, d_label, d_score, B, K, H, W, C, (hipStream_t)stream, d_ws, ws_bytes);
+}
+int lseg_op_corr_argmax_conf(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int16_t* d_label2,
+                             float* d_score2, float* d_lse, int B, int K, int H, int W, int C, void* d_ws, size_t ws_bytes, void* stream) {
+    return launch_corr_argmax_conf(d_g16pad, d_tnorm, d_scale, d_label, d_score, d_label2, d_score2, d_lse, B, K, H, W, C, (hipStream_t)stream, d_ws,
+                                   ws_bytes);
 }
 
 size_t lseg_op_episode_stats_ws_bytes(int B, int H, int W) { return episode_stats_ws_bytes(B, H, W); }

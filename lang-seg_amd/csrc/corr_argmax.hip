@@ -24,6 +24,11 @@
 //   * a 120 x 120 map has 81 tiles per image for 256 CUs: given a workspace the launcher splits the labels of a tile over up to 8
 //     workgroups (whole panels each, the split that minimises rounds x panels), each writes its (score, label) plane, and a merge
 //     kernel takes them in ascending label order with the same strict `>` (6 B x pixels x splits through HBM, ~17 MB at B = 4).
+//   * label confidence (lseg_op_corr_argmax_conf, the CONF instantiation): the state grows to (best, second, arg | arg2 << 16, sum of
+//     exp(value - best)) -- 45 more registers per lane, 4 labels instead of 8 walk the rows together to make room (508 VGPRs, no
+//     scratch) -- and 16 B per pixel are written: label, score, runner-up label and score, lse = best + log(sum).  A label part writes
+//     the same five planes (16 B x pixels x splits) and the merge combines them in ascending order: top-2 by the same strict `>` rule,
+//     lse by log-add-exp.  The arg-max instantiation compiles to the instructions it had before the template parameter existed.
 // LDS: T 49 920 + Rs 49 920 + Lr 54 016 + row taps 1 024 = 154 880 B of the CU's 160 KB.
 // Traffic per image at 120 x 120, K = 1000 (81 tiles, 21 panels): g 21 MB (halo included) from HBM, T 81 x 1 MB from L2, 1.4 MB written --
 // against the 922 MB logits write (and read) this replaces.  The panel-outer alternative would read g 15 MB x 21 panels and carry the
@@ -68,10 +73,16 @@ __host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_o
     return o;
 }
 
+// CONF = the label-confidence instantiation (lseg_op_corr_argmax_conf): besides (best, arg) every owned pixel keeps the runner-up
+// (second, arg2) -- the largest value among the labels != arg, ties to the lower label, i.e. entry 1 of a stable descending sort over k
+// -- and the sum s of exp(value - best) over all labels seen, so that lse = best + log(s) (the running maximum of an online
+// log-sum-exp IS best: no separate m).  arg and arg2 share one register (16 bits each): 3 x 15 state registers on top of the arg-max's.
+template <bool CONF>
 __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ T,
                                                             const float* __restrict__ scale, int16_t* __restrict__ label,
                                                             float* __restrict__ score, int B, int K, int H, int W, int tiles_y, int tiles_x,
-                                                            int nsplit, int split_labels, size_t split_stride) {
+                                                            int nsplit, int split_labels, size_t split_stride, int16_t* __restrict__ label2,
+                                                            float* __restrict__ score2, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* tlds = lds;
     float* Rs = reinterpret_cast<float*>(lds + CA_P * CA_PITCH);
@@ -166,6 +177,10 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
     int arg[CA_ROWS];
 #pragma unroll
     for (int j = 0; j < CA_ROWS; ++j) { best[j] = -INFINITY; arg[j] = 0; }
+    constexpr int CA_CROWS = CONF ? CA_ROWS : 1;
+    float second[CA_CROWS], esum[CA_CROWS];                              // CONF; arg[j] = arg | arg2 << 16 there
+#pragma unroll
+    for (int j = 0; j < CA_CROWS; ++j) { second[j] = -INFINITY; esum[j] = 0.f; }
 
     for (int pb = k_lo; pb < k_hi; pb += CA_P) {
         // ---- T panel -> LDS (rows past K repeat the last label: computed, never compared) ------------------------------------------------
@@ -225,13 +240,15 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
             __syncthreads();
             // ---- stage 2: output_conv's bilinear + the running arg-max, labels in ascending order ----------------------------------------
             // CA_LU labels walk the rows together: the row pattern (which mid row is new) is the same for every label, so one uniform
-            // branch serves CA_LU independent interpolants and their 2 CA_LU LDS reads are in flight at once
-            for (int l0 = 0; l0 < CA_LC && pb + cb + l0 < K; l0 += CA_LU) {
+            // branch serves CA_LU independent interpolants and their 2 CA_LU LDS reads are in flight at once (CONF: 4 -- its 45 more state
+            // registers leave no room for 8 interpolant pairs, and its per-value arithmetic hides the LDS reads of 4)
+            constexpr int LU = CONF ? 4 : CA_LU;
+            for (int l0 = 0; l0 < CA_LC && pb + cb + l0 < K; l0 += LU) {
                 const float* Ll = Lr + l0 * CA_LP;
                 const int lab0 = pb + cb + l0;
-                float h0[CA_LU], h1[CA_LU];
+                float h0[LU], h1[LU];
 #pragma unroll
-                for (int u = 0; u < CA_LU; ++u) { h0[u] = 0.f; h1[u] = 0.f; }
+                for (int u = 0; u < LU; ++u) { h0[u] = 0.f; h1[u] = 0.f; }
                 int c0 = -1, c1 = -1;                                    // the mid rows h0 / h1 hold (wave-uniform)
 #pragma unroll
                 for (int j = 0; j < CA_ROWS; ++j) {
@@ -240,27 +257,41 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
                     if (y0 != c0) {
                         if (y0 == c1) {
 #pragma unroll
-                            for (int u = 0; u < CA_LU; ++u) h0[u] = h1[u];
+                            for (int u = 0; u < LU; ++u) h0[u] = h1[u];
                         } else {
 #pragma unroll
-                            for (int u = 0; u < CA_LU; ++u) h0[u] = hlerp(Ll[u * CA_LP + y0 + cx0], Ll[u * CA_LP + y0 + cx1], clx);
+                            for (int u = 0; u < LU; ++u) h0[u] = hlerp(Ll[u * CA_LP + y0 + cx0], Ll[u * CA_LP + y0 + cx1], clx);
                         }
                         c0 = y0;
                     }
                     if (y1 != c1) {
                         if (y1 == c0) {
 #pragma unroll
-                            for (int u = 0; u < CA_LU; ++u) h1[u] = h0[u];
+                            for (int u = 0; u < LU; ++u) h1[u] = h0[u];
                         } else {
 #pragma unroll
-                            for (int u = 0; u < CA_LU; ++u) h1[u] = hlerp(Ll[u * CA_LP + y1 + cx0], Ll[u * CA_LP + y1 + cx1], clx);
+                            for (int u = 0; u < LU; ++u) h1[u] = hlerp(Ll[u * CA_LP + y1 + cx0], Ll[u * CA_LP + y1 + cx1], clx);
                         }
                         c1 = y1;
                     }
 #pragma unroll
-                    for (int u = 0; u < CA_LU; ++u) {
+                    for (int u = 0; u < LU; ++u) {
                         const float v = vlerp(h0[u], h1[u], r_ly[j]);
-                        if (lab0 + u < K && v > best[j]) { best[j] = v; arg[j] = lab0 + u; }      // first maximum wins
+                        if constexpr (!CONF) {
+                            if (lab0 + u < K && v > best[j]) { best[j] = v; arg[j] = lab0 + u; }      // first maximum wins
+                        } else if (lab0 + u < K) {
+                            // one exp per value: exp(-|v - best|) rescales the sum when v is the new maximum and is v's own term otherwise
+                            // (best = -inf before the first label: exp(-inf) = 0 and the sum starts at 1)
+                            const float e = __expf(-fabsf(v - best[j]));
+                            if (v > best[j]) {                                                    // first maximum wins; the old one is the runner-up
+                                esum[j] = fmaf(esum[j], e, 1.f);
+                                second[j] = best[j]; best[j] = v;
+                                arg[j] = (int)((unsigned)arg[j] << 16) | (lab0 + u);
+                            } else {
+                                esum[j] += e;
+                                if (v > second[j]) { second[j] = v; arg[j] = (arg[j] & 0xffff) | ((lab0 + u) << 16); }   // a later equal of best lands here
+                            }
+                        }
                     }
                 }
             }
@@ -273,8 +304,16 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
         for (int j = 0; j < CA_ROWS; ++j) {
             if (j >= nrow) continue;
             const size_t o = (size_t)sp * split_stride + ((size_t)b * Ho + ys + j) * Wo + xo;
-            label[o] = (int16_t)arg[j];
-            if (score) score[o] = best[j];
+            if constexpr (!CONF) {
+                label[o] = (int16_t)arg[j];
+                if (score) score[o] = best[j];
+            } else {
+                label[o] = (int16_t)(arg[j] & 0xffff);
+                if (score) score[o] = best[j];
+                if (label2) label2[o] = second[j] == -INFINITY ? (int16_t)-1 : (int16_t)((unsigned)arg[j] >> 16);   // one label: no runner-up
+                if (score2) score2[o] = second[j];
+                if (lse) lse[o] = best[j] + logf(esum[j]);
+            }
         }
     }
 }
@@ -291,6 +330,41 @@ __global__ __launch_bounds__(256) void corr_argmax_merge_kernel(const int16_t* _
         }
         label[i] = a;
         if (score) score[i] = m;
+    }
+}
+
+// one more value (v, label k) into a pixel's running top-2, labels arriving in ascending order: the rule of the streamed kernel's CONF body,
+// shared by the merge and the fallback -- strict `>` twice, so equal values keep the lower label and a later equal of best is the runner-up
+__device__ inline void top2_push(float v, int k, float& best, int& arg, float& second, int& arg2) {
+    const bool nb = v > best, ns = !nb && v > second;                  // (selects, not branches: the state stays in registers)
+    second = nb ? best : (ns ? v : second);
+    arg2 = nb ? arg : (ns ? k : arg2);
+    best = nb ? v : best;
+    arg = nb ? k : arg;
+}
+
+// the five planes of the label parts -> the final outputs.  Parts in ascending order = labels in ascending order: a part's winner and then
+// its runner-up are pushed like single labels (the runner-up can only matter when the winner became the new best); lse by log-add-exp
+__global__ __launch_bounds__(256) void corr_argmax_conf_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc,
+                                                                     const int16_t* __restrict__ wl2, const float* __restrict__ wsc2,
+                                                                     const float* __restrict__ wlse, int nsplit, size_t n,
+                                                                     int16_t* __restrict__ label, float* __restrict__ score,
+                                                                     int16_t* __restrict__ label2, float* __restrict__ score2, float* __restrict__ lse) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float m = wsc[i], m2 = wsc2[i], l = wlse[i];
+        int a = wl[i], a2 = wl2[i];
+        for (int s = 1; s < nsplit; ++s) {
+            const size_t o = (size_t)s * n + i;
+            top2_push(wsc[o], wl[o], m, a, m2, a2);
+            top2_push(wsc2[o], wl2[o], m, a, m2, a2);                  // -inf (a part of one label) never enters
+            const float pl = wlse[o], hi = fmaxf(l, pl);
+            l = hi + log1pf(expf(-fabsf(l - pl)));
+        }
+        label[i] = (int16_t)a;
+        if (score) score[i] = m;
+        if (label2) label2[i] = (int16_t)a2;
+        if (score2) score2[i] = m2;
+        if (lse) lse[i] = l;
     }
 }
 
@@ -320,6 +394,41 @@ __global__ __launch_bounds__(256) void seg_argmax16_kernel(const float* __restri
         }
         label[i] = (int16_t)arg;
         if (score) score[i] = m;
+    }
+}
+
+// seg_argmax16_kernel with the confidence outputs: the same values in the same order through top2_push and an online log-sum-exp whose
+// running maximum is `best` (one exp per value, as in the streamed kernel).  K = 1: label2 = -1, score2 = -inf, lse = score
+__global__ __launch_bounds__(256) void seg_conf16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix, int16_t* __restrict__ label,
+                                                         float* __restrict__ score, int16_t* __restrict__ label2, float* __restrict__ score2,
+                                                         float* __restrict__ lse) {
+    const int Wo = 2 * w, HW = 4 * h * w;
+    const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
+    const size_t kstride = (size_t)h * w;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i % HW);
+        const size_t b = i / HW;
+        const int yo = p / Wo, xo = p - yo * Wo;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_tap(ry, yo, h, y0, y1, ly);
+        src_tap(rx, xo, w, x0, x1, lx);
+        const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
+        const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
+        float m = -INFINITY, m2 = -INFINITY, es = 0.f;
+        int arg = 0, arg2 = -1;
+        for (int k = 0; k < K; ++k) {
+            const float* cc = col + (size_t)k * kstride;
+            const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
+            const float e = __expf(-fabsf(v - m));
+            es = v > m ? fmaf(es, e, 1.f) : es + e;
+            top2_push(v, k, m, arg, m2, arg2);
+        }
+        label[i] = (int16_t)arg;
+        if (score) score[i] = m;
+        if (label2) label2[i] = m2 == -INFINITY ? (int16_t)-1 : (int16_t)arg2;
+        if (score2) score2[i] = m2;
+        if (lse) lse[i] = m + logf(es);
     }
 }
 
@@ -353,8 +462,12 @@ bool corr_argmax_supported(int K, int C) { return C == CA_C && K >= 1 && K <= 32
 // g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W]; label: int16 [B, 4H, 4W]; score: fp32 [B, 4H, 4W] or NULL
 // ws (optional, ws_bytes): with 6 bytes x B x 16 H W per split the labels of a tile are split over up to 8 workgroups (whole panels each)
 // and merged afterwards -- a 120 x 120 map has only 81 tiles per image for 256 CUs; without it one workgroup per tile streams all K
-int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
-                       hipStream_t st, void* ws, size_t ws_bytes) {
+// label2 / score2 / lse (each optional): any of them selects the CONF instantiation; a part then takes 16 bytes per output pixel of the
+// workspace (score, score2, lse fp32; label, label2 int16) instead of 6: 256 B H W bytes per part
+static int launch_corr_argmax_any(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2,
+                                  float* lse, int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes) {
+    const bool conf = label2 || score2 || lse;
+    const size_t part_bytes = conf ? 16 : 6;
     if (!g || !T || !scale || !label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
     if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
     if (!corr_argmax_supported(K, C)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: K=%d C=%d (C must be 512, K >= 1)", K, C);
@@ -370,7 +483,8 @@ int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t
     static std::atomic<unsigned long long> attr_done{0};             // per-device opt-in to > 64 KB of dynamic LDS (cf. corr.hip)
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_done.fetch_or(bit, std::memory_order_release);
     }
     // label splits: the fewest rounds x (panels per split + ~1 panel of set-up) over the CUs
@@ -381,23 +495,53 @@ int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t
     for (int s = 1; s <= 8 && s <= panels; ++s) {
         const int per = (panels + s - 1) / s;
         if ((per * (s - 1)) >= panels) continue;                       // the last split would be empty
-        if (s > 1 && (!ws || ws_bytes < (size_t)s * npix * 6 || ntiles * s >= (1L << 31))) break;
+        if (s > 1 && (!ws || ws_bytes < (size_t)s * npix * part_bytes || ntiles * s >= (1L << 31))) break;
         const long cost = ((ntiles * s + cus - 1) / cus) * (long)(per + 1);
         if (s == 1 || cost < best_cost) { best_cost = cost; nsplit = s; }
     }
     const int split_labels = (panels + nsplit - 1) / nsplit * CA_P;
+    const size_t pn = (size_t)nsplit * npix;                           // values per workspace plane
     float* wsc = reinterpret_cast<float*>(ws);
-    int16_t* wl = nsplit > 1 ? reinterpret_cast<int16_t*>(wsc + (size_t)nsplit * npix) : nullptr;
-    hipLaunchKernelGGL(corr_argmax_kernel, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
+    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+    if (conf) {
+        // workspace planes: score, score2, lse (fp32), label, label2 (int16), each [nsplit][npix]; a part always writes all five
+        float *wsc2 = wsc + pn, *wlse = wsc + 2 * pn;
+        int16_t *wl = reinterpret_cast<int16_t*>(wsc + 3 * pn), *wl2 = wl + pn;
+        if (nsplit > 1)
+            hipLaunchKernelGGL(corr_argmax_kernel<true>, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
+                               scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse);
+        else
+            hipLaunchKernelGGL(corr_argmax_kernel<true>, dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
+                               label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse);
+        LSEG_HIP_TRY(hipGetLastError());
+        if (nsplit > 1) {
+            hipLaunchKernelGGL(corr_argmax_conf_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, wl2, wsc2, wlse, nsplit, npix, label, score, label2,
+                               score2, lse);
+            LSEG_HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    }
+    int16_t* wl = nsplit > 1 ? reinterpret_cast<int16_t*>(wsc + pn) : nullptr;
+    hipLaunchKernelGGL(corr_argmax_kernel<false>, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
                        nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit, nsplit > 1 ? split_labels : K,
-                       nsplit > 1 ? npix : (size_t)0);
+                       nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr);
     LSEG_HIP_TRY(hipGetLastError());
     if (nsplit > 1) {
-        const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
         hipLaunchKernelGGL(corr_argmax_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, nsplit, npix, label, score);
         LSEG_HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
+                       hipStream_t st, void* ws, size_t ws_bytes) {
+    return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, nullptr, B, K, H, W, C, st, ws, ws_bytes);
+}
+
+// launch_corr_argmax + the runner-up (label2 int16 / score2 fp32) and lse fp32 = log-sum-exp over all K, each [B, 4H, 4W] or NULL
+int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
+                            int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes) {
+    return launch_corr_argmax_any(g, T, scale, label, score, label2, score2, lse, B, K, H, W, C, st, ws, ws_bytes);
 }
 
 // low: fp32 [B, K, h, w] (the (2h, 2w) logits of the engine); label int16 [B, 2h, 2w]; score fp32 [B, 2h, 2w] or NULL
@@ -408,6 +552,20 @@ int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* l
     const size_t npix = (size_t)B * 4 * h * w;
     const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(seg_argmax16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, label, score);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// launch_seg_argmax16 + label2 int16 / score2 fp32 / lse fp32 [B, 2h, 2w], each or NULL
+int launch_seg_conf16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
+                      hipStream_t st) {
+    if (!label2 && !score2 && !lse) return launch_seg_argmax16(low, B, K, h, w, label, score, st);
+    if (!low || !label) return set_error(LSEG_ERR_INVALID, "seg_conf16: NULL pointer");
+    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_conf16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
+    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_conf16: B=%d h=%d w=%d", B, h, w);
+    const size_t npix = (size_t)B * 4 * h * w;
+    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(seg_conf16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, label, score, label2, score2, lse);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }

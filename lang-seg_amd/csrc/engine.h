@@ -94,8 +94,10 @@ public:
     // label_out / score_out (int16 / fp32 [B,img_h,img_w], lseg_forward_labels): masks for any K <= 32767; with no other output wanted the
     // labels are streamed (corr_argmax.hip): no (2h, 2w) or full-resolution label plane is written
     // low_out (fp32 [B,Kout,img_h/2,img_w/2], lseg_forward_lowres): the logits output_conv would upsample, in the caller's buffer
+    // conf (lseg_forward_labels_conf; needs label_out): the runner-up and the log-sum-exp over the labels beside the arg-max, each optional
+    struct LabelConf { int16_t* label2; float* score2; float* lse; };
     int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
-                float* score_out = nullptr, float* low_out = nullptr);
+                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr);
     int get_text_features(void* out_f16, hipStream_t st);
     int forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st);
     // few-shot episode statistics of the last forward's 2 label planes (episode.hip), inference or train-mode forward alike

@@ -940,7 +940,9 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
 }
 
 int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
-                    float* low_out) {
+                    float* low_out, const LabelConf* conf) {
+    const LabelConf cf = conf ? *conf : LabelConf{nullptr, nullptr, nullptr};
+    if ((cf.label2 || cf.score2 || cf.lse) && !label_out) return set_error(LSEG_ERR_INVALID, "the confidence outputs need the label output");
     if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
     if (K_ < 1) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
@@ -1090,8 +1092,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         // nothing reads here: the two grams differ in the last bits and the score would no longer equal logits.max), above from pixel_gram
         if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
             // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
-            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, label_out, score_out, B, K_, lh_[0], lw_[0], c.out_c, st, low_,
-                                   (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
+            TRY(launch_corr_argmax_conf(g16pad_, tnorm_, nscale_, label_out, score_out, cf.label2, cf.score2, cf.lse, B, K_, lh_[0], lw_[0], c.out_c, st,
+                                        low_, (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
             labels_only_ = true; last_low_ = nullptr; last_kout_ = K_;
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
@@ -1173,7 +1175,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     last_low_ = low; last_kout_ = Kout;
     if (argmax_out && Kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", Kout);
     if (argmax_out) TRY(launch_seg_stats_ex(low, nullptr, B, Kout, 4 * hw1, -1, nullptr, nullptr, argmax_out, 1, h1, w1, st));
-    if (label_out) TRY(launch_seg_argmax16(low, B, Kout, h1, w1, label_out, score_out, st));      // the int16 form, on the planes in memory
+    // the int16 form, on the planes in memory (with the runner-up and the log-sum-exp when lseg_forward_labels_conf asks for them)
+    if (label_out) TRY(launch_seg_conf16(low, B, Kout, h1, w1, label_out, score_out, cf.label2, cf.score2, cf.lse, st));
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
     if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
     // every other schedule (head blocks, the full-resolution correlation, debug / split-precision) has them in engine memory: a copy

@@ -111,6 +111,12 @@ int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t
                        hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);   // ws: label-split planes, 6 B x B x 16 H W each (optional)
 // the int16 form of launch_seg_stats_ex's mask output (up = 1, no target): low fp32 [B, K, h, w] -> label / score (optional) [B, 2h, 2w]
 int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st);
+// label confidence: the two above + the runner-up (label2 int16 / score2 fp32: entry 1 of a stable descending sort over k; -1 / -inf when
+// K = 1) and lse fp32 = log-sum-exp over all K, each the outputs' shape or NULL.  ws: 16 B x B x 16 H W per label part
+int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
+                            int B, int K, int H, int W, int C, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
+int launch_seg_conf16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
+                      hipStream_t st);
 // episode.hip -- few-shot episode evaluation (Evaluator.classify_prediction + AverageMeter.update + the 2-class criterion): scores fp32
 // [B,2,H,W] (up = 0) or low-resolution logits [B,2,H/2,W/2] read through the x2 bilinear (up = 1), target int64 / ignore uint8 (or NULL)
 // [B,H,W] -> areas int64 [B,6], nll double [B,2], flags int64 [2], optional scatter into the meter's int64 [2,nclass] buffers

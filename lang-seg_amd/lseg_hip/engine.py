@@ -207,6 +207,24 @@ class HipEngine:
         self._raise_callback_error()
         return (lab, score) if want_score else lab
 
+    def forward_labels_conf(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """forward_labels with a confidence (lseg_forward_labels_conf), still without the [B,K,H,W] logits: a dict of [B,H,W] tensors --
+        "label" int16 / "score" fp32 = torch.max(logits, 1); "label2" int16 / "score2" fp32 = the runner-up, entry 1 of
+        torch.sort(logits, 1, descending=True, stable=True) (-1 / -inf with a single label); "lse" fp32 = torch.logsumexp(logits, 1).
+        The winner's softmax probability is exp(score - lse), the top-2 margin score - score2."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        out = {"label": torch.empty((B, H, W), dtype=torch.int16, device=self.device),
+               "score": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
+               "label2": torch.empty((B, H, W), dtype=torch.int16, device=self.device),
+               "score2": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
+               "lse": torch.empty((B, H, W), dtype=torch.float32, device=self.device)}
+        _lib.check(self.lib.lseg_forward_labels_conf(
+            self._h, C.c_void_p(x.data_ptr()), B, *(C.c_void_p(out[k].data_ptr()) for k in ("label", "score", "label2", "score2", "lse")),
+            C.c_void_p(_stream_ptr(self.device))))
+        self._raise_callback_error()
+        return out
+
     def forward_lowres(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 [B,Kout,H/2,W/2]: the logits before output_conv's x2 bilinear (lseg_forward_lowres) -- lseg_op_upsample2x_planes of them is
         bit-identical to forward(x); the [B,Kout,H,W] tensor is never written."""

@@ -392,9 +392,10 @@ class LSegmentationModule(_Base):
     def forward(self, x):
         return self.net(x)
 
-    def predict_labels(self, x, labelset=""):
-        """The mask torch.max(pred, 1)[1] (:114-117; lseg_app.py:350-355) as torch.long [B,H,W] for any label set, without the logits."""
-        return self.net.predict_labels(x, labelset)
+    def predict_labels(self, x, labelset="", confidence=False):
+        """The mask torch.max(pred, 1)[1] (:114-117; lseg_app.py:350-355) as torch.long [B,H,W] for any label set, without the logits;
+        confidence=True: the dict of LSegNet.predict_labels (label, prob, label2, margin)."""
+        return self.net.predict_labels(x, labelset, confidence)
 
     def evaluate(self, x, target=None):                       # :43-52
         if target is not None and hasattr(self.net, "forward_metrics"):

@@ -285,9 +285,12 @@ class LSeg(BaseModel):
         finally:
             self.train(was)
 
-    def predict_labels(self, x, labelset=""):
+    def predict_labels(self, x, labelset="", confidence=False):
         """torch.max(self.forward(x, labelset), 1)[1] (what lseg_app.py:350-355 and every caller of the reference do with the logits) as
-        torch.long [B,H,W], for any K <= 32767, without the [B,K,H,W] logits (lseg_forward_labels)."""
+        torch.long [B,H,W], for any K <= 32767, without the [B,K,H,W] logits (lseg_forward_labels).
+        confidence=True (lseg_forward_labels_conf) returns a dict instead: "label" (that mask), "prob" = the winner's softmax
+        probability over the label set, exp(score - logsumexp), "label2" = the runner-up label (torch.long; -1 with a single label) and
+        "margin" = the top-2 logit margin (inf with a single label) -- what softmax / topk on the logits would give, without them."""
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet.predict_labels needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
@@ -301,10 +304,13 @@ class LSeg(BaseModel):
                     eng.set_train(False)
                 self._set_tokens(eng, text, labelset)
                 self._last_engine = eng
-                lab = eng.forward_labels(x.float())
+                r = eng.forward_labels_conf(x.float()) if confidence else eng.forward_labels(x.float())
                 if self._range_guard(eng, x.device):
-                    return self.predict_labels(x, labelset)         # fell back to bf16: run again on a bf16 engine
-                return lab.long()
+                    return self.predict_labels(x, labelset, confidence)         # fell back to bf16: run again on a bf16 engine
+                if not confidence:
+                    return r.long()
+                return {"label": r["label"].long(), "prob": torch.exp(r["score"] - r["lse"]), "label2": r["label2"].long(),
+                        "margin": r["score"] - r["score2"]}
         finally:
             self.train(was)
 
