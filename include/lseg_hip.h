@@ -354,9 +354,23 @@ int lseg_op_upsample2x_planes(const float* d_in, float* d_out, int P, int H, int
 /* The tail of the commuted head (DESIGN.md par. 3.4) in one pass: label planes R at the quarter resolution, d_in_padded fp32 [B*K, H+2, W+2]
  * (1-pixel border), per-pixel scale s/||u|| d_scale fp32 [B, 2H, 2W] -> logits d_out fp32 [B, K, 4H, 4W] =
  * output_conv(fp16(scale * bilinear_x2(R))) (lseg_net.py:194-196 rounding, :203 upsample).  two_stage != 0 runs the two materialising
- * kernels instead (d_low_scratch fp32 [B,K,2H,2W]): same bits. */
+ * kernels instead (d_low_scratch fp32 [B,K,2H,2W]): same bits.  LSEG_ERR_UNSUPPORTED for an odd W and for a W whose row band does not
+ * fit the 160 KB LDS (184 bytes per column in one pass: W <= 890; 32 in the two-stage form). */
 int lseg_op_upsample4x_planes_scaled(const float* d_in_padded, const float* d_scale, float* d_out, int B, int K, int H, int W, int two_stage,
                                      float* d_low_scratch, void* stream);
+/* The other kernels of the output tail, one launch each, for the fp64 operator tests in tests/test_gpu_output_tail.py.  All refuse
+ * (LSEG_ERR_INVALID: NULL pointer, B / H / W < 1, H or W < 2 where a bilinear is taken; LSEG_ERR_UNSUPPORTED: C % 8 != 0 or C > 1024)
+ * before anything is launched.
+ *   pixel_gram         d_g16pad fp16 padded NHWC [B, H+2, W+2, C] (finite border: it enters the last row's and column's records)
+ *                      -> d_gram fp32 [B, H, W, 5], the records of lseg_op_corr_planes for any C (the generic schedule's producer)
+ *   norm_scale_plane   d_gram [B, H, W, 5] -> d_scale fp32 [B, 2H, 2W] = s / ||u||, ||u||^2 the 10-term quadratic form of the x2
+ *                      bilinear's (align_corners=True) four weights over the cell's dot products.  d_flag (may be NULL): set to 1 when
+ *                      a squared norm is not finite, never cleared
+ *   upsample_norm_f16  d_g32pad fp32 padded NHWC [B, H+2, W+2, C] (border never read) -> d_a16 fp16 [B, 2H, 2W, C] =
+ *                      fp16(scale * fp16(u / ||u||)), u = the x2 bilinear of g (strict mode and label sets beyond the LDS limit) */
+int lseg_op_pixel_gram(const void* d_g16pad, float* d_gram, int B, int H, int W, int C, void* stream);
+int lseg_op_norm_scale_plane(const float* d_gram, float* d_scale, int B, int H, int W, float s, unsigned* d_flag, void* stream);
+int lseg_op_upsample_norm_f16(const float* d_g32pad, void* d_a16, int B, int H, int W, int C, float scale, void* stream);
 /* pixel x text correlation (lseg_net.py:187-196): feat fp32 [M,C]; text fp16 [K,C]
  * (already L2-normalised); logits fp32 [B,K,P] with M = B*P.  Internally:
  * a = fp16(scale * fp16(feat/||feat||)); logits = fp16(a @ text^T). */

@@ -382,6 +382,25 @@ int lseg_op_upsample4x_planes_scaled(const float* in_padded, const float* scale,
     return launch_upsample2x_planes(low_scratch, out, B * K, 2 * H, 2 * W, (hipStream_t)stream);
 }
 
+// ---- the output tail's remaining kernels, one launch each (tests/test_gpu_output_tail.py holds them to fp64 references) ----------------
+int lseg_op_pixel_gram(const void* d_g16pad, float* d_gram, int B, int H, int W, int C, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_g16pad || !d_gram || B < 1 || H < 1 || W < 1 || C < 1) return set_error(LSEG_ERR_INVALID, "pixel_gram: bad arguments");
+    return launch_pixel_gram(d_g16pad, d_gram, B, H, W, C, (hipStream_t)stream);
+}
+
+int lseg_op_norm_scale_plane(const float* d_gram, float* d_scale, int B, int H, int W, float s, unsigned* d_flag, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_gram || !d_scale || B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "norm_scale_plane: bad arguments (H, W >= 2)");
+    return launch_norm_scale_plane(d_gram, d_scale, B, H, W, s, (hipStream_t)stream, d_flag);
+}
+
+int lseg_op_upsample_norm_f16(const float* d_g32pad, void* d_a16, int B, int H, int W, int C, float scale, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!d_g32pad || !d_a16 || B < 1 || H < 2 || W < 2 || C < 1) return set_error(LSEG_ERR_INVALID, "upsample_norm_f16: bad arguments (H, W >= 2)");
+    return launch_upsample_norm_f16(d_g32pad, d_a16, B, H, W, C, scale, (hipStream_t)stream);
+}
+
 int lseg_op_correlation(const float* feat, const void* text_f16, float* logits, int B, int P, int C, int K,
                         float logit_scale, void* stream) {
     int r = require_device(); if (r) return r;

@@ -5,6 +5,8 @@
 #include "ops.h"
 #include "../../include/lseg_hip.h"
 
+#include <atomic>
+
 namespace lseg {
 namespace {
 
@@ -595,10 +597,13 @@ __global__ void norm_scale_plane_kernel(const float* __restrict__ gram, float* _
     const float ry = (float)(H - 1) / (float)(Ho - 1), rx = (float)(W - 1) / (float)(Wo - 1);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), b = (int)(i / ((size_t)Wo * Ho));
-        const float sy = ry * (float)yo, sx = rx * (float)xo;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = y0 + (y0 < H - 1), x1 = x0 + (x0 < W - 1);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        // src_tap: the product is ROUNDED before the subtraction, so the last row / column gets l = 0 exactly.  Written out here, the
+        // compiler fused l = fma(r, i, -i0) = the exact product's remainder: up to 2^-24 (n - 1), of either sign, on a tap whose records
+        // belong to the pixel itself -- a.(border) entered the last row's and column's norm (tests/test_gpu_output_tail.py, rough g)
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_tap(ry, yo, H, y0, y1, ly);
+        src_tap(rx, xo, W, x0, x1, lx);
         const float wa = (1.f - ly) * (1.f - lx), wb = (1.f - ly) * lx, wc = ly * (1.f - lx), wd = ly * lx;
         const float* ra = gram + (((size_t)b * H + y0) * W + x0) * 5;          // a = (y0, x0): right -> a.b, down -> a.c, diag -> a.d, anti -> b.c
         const float* rb = gram + (((size_t)b * H + y0) * W + x1) * 5;          // b = (y0, x1): down -> b.d
@@ -2711,11 +2716,29 @@ int launch_norm_scale_plane(const float* gram, float* scale, int B, int H, int W
     CHECK_LAUNCH();
     return 0;
 }
+// The banded upsamples size their dynamic LDS from W: the limit, and the per-device opt-in beyond 64 KB, of corr.hip's LDS-resident text.
+// Refused before anything is launched.
+static int ups_lds_check(const void* kern, size_t lds, int W, std::atomic<unsigned long long>& attr_done) {
+    constexpr size_t UPS_LDS_MAX = 160u * 1024u;
+    if (lds > UPS_LDS_MAX)
+        return set_error(LSEG_ERR_UNSUPPORTED, "scaled upsample: W=%d needs %zu bytes of LDS per workgroup, the limit is %zu", W, lds, UPS_LDS_MAX);
+    if (lds <= 64u * 1024u) return 0;
+    int dev = 0;
+    LSEG_HIP_TRY(hipGetDevice(&dev));
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+        LSEG_HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPS_LDS_MAX));
+        attr_done.fetch_or(bit, std::memory_order_release);
+    }
+    return 0;
+}
 int launch_upsample2x_planes_scaled(const float* in_padded, const float* scale, float* out, int P, int K, int H, int W, hipStream_t st) {
     if (W % 2 != 0) return set_error(LSEG_ERR_UNSUPPORTED, "scaled upsample: W=%d must be even", W);
     const int bands = (2 * H + UPS_LB - 1) / UPS_LB;
-    hipLaunchKernelGGL(upsample2x_planes_scaled_kernel, dim3((unsigned)P * bands), dim3(256), (size_t)(UPS_LB / 2 + 4) * W * sizeof(float), st,
-                       in_padded, scale, out, P, K, H, W);
+    const size_t lds = (size_t)(UPS_LB / 2 + 4) * W * sizeof(float);
+    static std::atomic<unsigned long long> attr_done{0};
+    if (int r = ups_lds_check(reinterpret_cast<const void*>(upsample2x_planes_scaled_kernel), lds, W, attr_done)) return r;
+    hipLaunchKernelGGL(upsample2x_planes_scaled_kernel, dim3((unsigned)P * bands), dim3(256), lds, st, in_padded, scale, out, P, K, H, W);
     CHECK_LAUNCH();
     return 0;
 }
@@ -2724,6 +2747,8 @@ int launch_upsample4x_planes_scaled(const float* in_padded, const float* scale, 
     if (W % 2 != 0) return set_error(LSEG_ERR_UNSUPPORTED, "scaled upsample: W=%d must be even", W);
     const int bands = (2 * H + UPS4_LB - 1) / UPS4_LB;
     const size_t lds = ((size_t)(UPS4_LB / 2 + 4) * W + (size_t)(UPS4_LB + 1) * 2 * W) * sizeof(float);
+    static std::atomic<unsigned long long> attr_done{0};
+    if (int r = ups_lds_check(reinterpret_cast<const void*>(upsample4x_planes_scaled_kernel<UPS4_LB>), lds, W, attr_done)) return r;
     hipLaunchKernelGGL((upsample4x_planes_scaled_kernel<UPS4_LB>), dim3((unsigned)P * bands), dim3(256), lds, st, in_padded, scale, out, P, K, H, W);
     CHECK_LAUNCH();
     return 0;

@@ -105,6 +105,9 @@ SIGNATURES = {
     "lseg_op_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_upsample2x_planes": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "lseg_op_upsample4x_planes_scaled": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lseg_op_pixel_gram": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_norm_scale_plane": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "lseg_op_upsample_norm_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_correlation": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_head_features": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "lseg_op_seg_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
