@@ -168,6 +168,18 @@ int lseg_get_text_features(lseg_handle h, void* dev_out_f16 /* [K,out_c] fp16 */
  * [B,k,img_h,img_w] logits, lseg_train_loss / lseg_backward* take the loss over those k label planes per image (target values in
  * [0, k), anything else ignored) and back-propagate through the per-image correlation (LSegmentationModuleZS.training_step). */
 int lseg_set_text_grouping(lseg_handle h, int labels_per_image);
+/* Open-vocabulary batches: every image brings its own label list, of its OWN length (one list per request, lseg_app.py:350-355).
+ * host_counts int32 [B] on the host, each in [1, 32767]: image b owns host_counts[b] consecutive rows of the K = sum of counts token rows
+ * of lseg_set_text_tokens / lseg_set_text_features (K <= max_labels as always), image 0's rows first.  NULL or B = 0 clears it.  Takes
+ * effect at the next forward; setting either grouping clears the other (any lseg_set_text_grouping call clears this one).
+ * While set, lseg_forward_labels and lseg_forward_labels_conf run ONE batched forward and stream every image against its own rows
+ * (csrc/corr_argmax.hip, the ragged instantiations; labels index the image's own list; a list of one label: label2 = -1, score2 = -inf)
+ * under the conditions the shared set streams under: commuted schedule, out_c = 512, arch_option 0, no LSEG_CORR_GENERIC.  Everything
+ * else -- lseg_forward (logits, uint8 masks), lseg_forward_lowres, train mode, other widths, head blocks, split precision -- returns
+ * LSEG_ERR_UNSUPPORTED before any kernel runs; nothing falls back.  A forward whose B differs from the B given here, or whose K differs
+ * from the sum of the counts, returns LSEG_ERR_INVALID.  Afterwards the state is that of a streamed forward: lseg_forward_stats and the
+ * "lowres" tap return LSEG_ERR_STATE.  Text cache, external text features, the overflow sentinel and profiling are unchanged. */
+int lseg_set_text_groups(lseg_handle h, const int32_t* host_counts, int B);
 
 /* ---- forward -----------------------------------------------------------------------
  * replaces: LSeg.forward(x, labelset) (lseg_net.py:160-205).
@@ -454,6 +466,27 @@ int lseg_op_corr_argmax(const void* d_g16pad, const void* d_text16, const float*
 int lseg_op_corr_argmax_conf(const void* d_g16pad, const void* d_text16, const float* d_scale, int16_t* d_label, float* d_score,
                              int16_t* d_label2, float* d_score2, float* d_lse, int B, int K, int H, int W, int C, void* d_ws, size_t ws_bytes,
                              void* stream);
+/* lseg_op_corr_argmax(_conf) for RAGGED per-image label sets, bare: image b is correlated with host_counts[b] consecutive rows of d_text16
+ * (fp16 [sum of counts, C]: image 0's rows first) only, and every label output indexes the image's OWN list, 0 .. host_counts[b] - 1.
+ * Image b's five planes are bit-equal to lseg_op_corr_argmax_conf with B = 1 on its slices of the inputs (with a workspace: lse within
+ * fp32 rounding, as there).  A list of one label behaves as K = 1: label2 = -1, score2 = -inf, lse = score.
+ *   host_counts int32 [B] in HOST memory: the launcher validates them without a device round trip and forms the offsets itself (a device
+ *              array of offsets could not be checked before the launch; this is the design chosen of the two, so there is no caller-made
+ *              offsets[0] to be wrong)
+ *   d_offsets  int32 [B + 1] device scratch: filled on the stream with the prefix sum of the counts (the values travel as kernel
+ *              arguments: host_counts may be freed as soon as the call returns) and read by the kernels behind it
+ *   d_label2 / d_score2 / d_lse: all NULL = the plain arg-max instantiation, any of them = the confidence one
+ *   d_ws / ws_bytes: as lseg_op_corr_argmax(_conf); the label parts (whole panels) are sized from the LARGEST count, a part beyond an
+ *              image's own count is neither written nor merged
+ * LSEG_ERR_INVALID, before anything is launched: a count < 1 or > 32767, a NULL required pointer (inputs, host_counts, d_offsets,
+ * d_label), B < 1, H or W < 2.  LSEG_ERR_UNSUPPORTED: C != 512, maps or text tables beyond the kernel's 32-bit offsets. */
+int lseg_op_corr_argmax_ragged(const void* d_g16pad, const void* d_text16, const float* d_scale, const int32_t* host_counts, int32_t* d_offsets,
+                               int16_t* d_label, float* d_score, int16_t* d_label2, float* d_score2, float* d_lse, int B, int H, int W, int C,
+                               void* d_ws, size_t ws_bytes, void* stream);
+/* The label split that launch takes when it plans for `cus` compute units and a workspace of ws_bytes (0 = none), host only: out2 =
+ * {parts, labels per part (a multiple of the panel)}.  Part s of image b holds its labels [s * out2[1], min((s + 1) * out2[1], count_b))
+ * and exists only when that range is not empty.  conf != 0: the confidence instantiation (16 instead of 6 bytes per pixel and part). */
+int lseg_op_corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2);
 /* The tile geometry that kernel was compiled with (host memory, no device needed), for the CPU index model of its tile -> footprint
  * mapping: out8 = {mid rows/columns per tile band, mid rows/columns of its footprint, base rows/columns of its footprint, labels per
  * panel, LDS pitch of a text row in bytes, labels per interpolation chunk, output rows per wave, dynamic LDS bytes}. */

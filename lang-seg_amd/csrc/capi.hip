@@ -79,7 +79,12 @@ int lseg_set_text_grouping(lseg_handle h, int labels_per_image) {
     if (labels_per_image < 0 || labels_per_image > h->e->cfg.max_labels)
         return set_error(LSEG_ERR_INVALID, "labels_per_image=%d outside [0, max_labels]", labels_per_image);
     h->e->group_k = labels_per_image;
+    h->e->clear_text_groups();               // either grouping clears the other
     return LSEG_OK;
+}
+int lseg_set_text_groups(lseg_handle h, const int32_t* host_counts, int B) {
+    GUARD(h);
+    return h->e->set_text_groups(host_counts, B);
 }
 int lseg_get_text_features(lseg_handle h, void* dev_out, void* stream) {
     GUARD(h);
@@ -455,6 +460,15 @@ int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const 
                                 d_nll, d_flags, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+int lseg_op_corr_argmax_ragged(const void* d_g16pad, const void* d_text16, const float* d_scale, const int32_t* host_counts, int32_t* d_offsets,
+                               int16_t* d_label, float* d_score, int16_t* d_label2, float* d_score2, float* d_lse, int B, int H, int W, int C,
+                               void* d_ws, size_t ws_bytes, void* stream) {
+    return launch_corr_argmax_ragged(d_g16pad, d_text16, d_scale, host_counts, d_offsets, d_label, d_score, d_label2, d_score2, d_lse, B, H, W, C,
+                                     (hipStream_t)stream, d_ws, ws_bytes);
+}
+int lseg_op_corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2) {
+    return corr_argmax_ragged_split(host_counts, B, H, W, conf, ws_bytes, cus, out2);
+}
 int lseg_op_corr_argmax_geometry(int* out8) {
     if (!out8) return set_error(LSEG_ERR_INVALID, "corr_argmax_geometry: NULL pointer");
     corr_argmax_geometry(out8);

@@ -38,6 +38,7 @@
 #include "../../include/lseg_hip.h"
 
 #include <atomic>
+#include <vector>
 
 namespace lseg {
 namespace {
@@ -77,12 +78,18 @@ __host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_o
 // (second, arg2) -- the largest value among the labels != arg, ties to the lower label, i.e. entry 1 of a stable descending sort over k
 // -- and the sum s of exp(value - best) over all labels seen, so that lse = best + log(s) (the running maximum of an online
 // log-sum-exp IS best: no separate m).  arg and arg2 share one register (16 bits each): 3 x 15 state registers on top of the arg-max's.
-template <bool CONF>
-__global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ T,
+//
+// RAGGED = per-image label sets of any size (lseg_op_corr_argmax_ragged): `offsets` int32 [B + 1] is the prefix sum of the images' label
+// counts; image b streams rows [offsets[b], offsets[b + 1]) of T_all only and reports labels local to its own list, and the kernel's K
+// (unused by the launcher there) gives way to the image's count.  A label part that lies beyond its image's count returns before it
+// touches anything: the merge kernels skip it (they read the same offsets), no identity element is ever written.  With RAGGED = false
+// nothing of this is compiled: the shared-set instantiations keep their instructions and registers.
+template <bool CONF, bool RAGGED>
+__global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ T_all,
                                                             const float* __restrict__ scale, int16_t* __restrict__ label,
-                                                            float* __restrict__ score, int B, int K, int H, int W, int tiles_y, int tiles_x,
+                                                            float* __restrict__ score, int B, int K_all, int H, int W, int tiles_y, int tiles_x,
                                                             int nsplit, int split_labels, size_t split_stride, int16_t* __restrict__ label2,
-                                                            float* __restrict__ score2, float* __restrict__ lse) {
+                                                            float* __restrict__ score2, float* __restrict__ lse, const int* __restrict__ offsets) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* tlds = lds;
     float* Rs = reinterpret_cast<float*>(lds + CA_P * CA_PITCH);
@@ -95,9 +102,15 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
 
     // label split `sp` of tile `ut` covers labels [k_lo, k_hi) (whole panels) and writes plane `sp` of the (label, score) workspace
     const unsigned ut = blockIdx.x / (unsigned)nsplit, sp = blockIdx.x - ut * (unsigned)nsplit;
-    const int k_lo = (int)sp * split_labels, k_hi = k_lo + split_labels < K ? k_lo + split_labels : K;
     const unsigned q = ut / (unsigned)tiles_x, tx = ut - q * (unsigned)tiles_x;
     const unsigned b = q / (unsigned)tiles_y, ty = q - b * (unsigned)tiles_y;
+    const int row0 = RAGGED ? offsets[b] : 0;                            // (workgroup-uniform: scalar loads)
+    const int K = RAGGED ? offsets[b + 1] - row0 : K_all;
+    const uint16_t* __restrict__ T = T_all + (size_t)row0 * CA_C;
+    const int k_lo = (int)sp * split_labels, k_hi = k_lo + split_labels < K ? k_lo + split_labels : K;
+    if constexpr (RAGGED) {
+        if (k_lo >= K) return;                                           // an empty part of a short list (before the first barrier)
+    }
     const int Ya = (int)ty * CA_LB, Xa = (int)tx * CA_LB;
     const int Yb = Ya + CA_LB < Hl - 1 ? Ya + CA_LB : Hl - 1, Xb = Xa + CA_LB < Wl - 1 ? Xa + CA_LB : Wl - 1;   // last mid row / column read
     const int nmy = Yb - Ya + 1, nmx = Xb - Xa + 1;
@@ -319,12 +332,22 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
 }
 
 // (label, score) planes of the label splits -> the final pair: ascending splits = ascending labels, strict `>` = the first maximum wins
+// ragged label sets (offsets != NULL): image i / img_pix owns ceil(count / split_labels) parts, the rest were never written and are not read
+__device__ inline int ca_parts_of(const int* __restrict__ offsets, int split_labels, unsigned img_pix, size_t i, int nsplit) {
+    if (!offsets) return nsplit;
+    const size_t b = i / img_pix;
+    const int parts = (offsets[b + 1] - offsets[b] + split_labels - 1) / split_labels;
+    return parts < nsplit ? parts : nsplit;
+}
+
 __global__ __launch_bounds__(256) void corr_argmax_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc, int nsplit, size_t n,
-                                                                int16_t* __restrict__ label, float* __restrict__ score) {
+                                                                int16_t* __restrict__ label, float* __restrict__ score,
+                                                                const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float m = wsc[i];
         int16_t a = wl[i];
-        for (int s = 1; s < nsplit; ++s) {
+        const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
+        for (int s = 1; s < parts; ++s) {
             const float v = wsc[(size_t)s * n + i];
             if (v > m) { m = v; a = wl[(size_t)s * n + i]; }
         }
@@ -349,11 +372,13 @@ __global__ __launch_bounds__(256) void corr_argmax_conf_merge_kernel(const int16
                                                                      const int16_t* __restrict__ wl2, const float* __restrict__ wsc2,
                                                                      const float* __restrict__ wlse, int nsplit, size_t n,
                                                                      int16_t* __restrict__ label, float* __restrict__ score,
-                                                                     int16_t* __restrict__ label2, float* __restrict__ score2, float* __restrict__ lse) {
+                                                                     int16_t* __restrict__ label2, float* __restrict__ score2, float* __restrict__ lse,
+                                                                     const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float m = wsc[i], m2 = wsc2[i], l = wlse[i];
         int a = wl[i], a2 = wl2[i];
-        for (int s = 1; s < nsplit; ++s) {
+        const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
+        for (int s = 1; s < parts; ++s) {
             const size_t o = (size_t)s * n + i;
             top2_push(wsc[o], wl[o], m, a, m2, a2);
             top2_push(wsc2[o], wl2[o], m, a, m2, a2);                  // -inf (a part of one label) never enters
@@ -459,14 +484,42 @@ void corr_argmax_geometry(int* out8) {
 
 bool corr_argmax_supported(int K, int C) { return C == CA_C && K >= 1 && K <= 32767; }
 
+namespace {
+
+// label splits: the fewest rounds x (panels per split + ~1 panel of set-up) over the CUs, each part whole panels
+int ca_pick_split(int panels, long ntiles, size_t npix, size_t part_bytes, bool has_ws, size_t ws_bytes, int cus) {
+    int nsplit = 1;
+    long best_cost = 0;
+    for (int s = 1; s <= 8 && s <= panels; ++s) {
+        const int per = (panels + s - 1) / s;
+        if ((per * (s - 1)) >= panels) continue;                       // the last split would be empty
+        if (s > 1 && (!has_ws || ws_bytes < (size_t)s * npix * part_bytes || ntiles * s >= (1L << 31))) break;
+        const long cost = ((ntiles * s + cus - 1) / cus) * (long)(per + 1);
+        if (s == 1 || cost < best_cost) { best_cost = cost; nsplit = s; }
+    }
+    return nsplit;
+}
+
+// the offsets of a ragged launch travel as kernel arguments, 64 per launch: nothing of the caller's host memory is read after the call returns
+struct CaOffsetChunk { int v[64]; };
+__global__ __launch_bounds__(64) void corr_argmax_offsets_kernel(int* __restrict__ dst, CaOffsetChunk c, int n) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
+}
+
+}  // namespace
+
 // g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W]; label: int16 [B, 4H, 4W]; score: fp32 [B, 4H, 4W] or NULL
 // ws (optional, ws_bytes): with 6 bytes x B x 16 H W per split the labels of a tile are split over up to 8 workgroups (whole panels each)
 // and merged afterwards -- a 120 x 120 map has only 81 tiles per image for 256 CUs; without it one workgroup per tile streams all K
 // label2 / score2 / lse (each optional): any of them selects the CONF instantiation; a part then takes 16 bytes per output pixel of the
 // workspace (score, score2, lse fp32; label, label2 int16) instead of 6: 256 B H W bytes per part
+// host_prefix / d_offsets (both or neither): ragged per-image label sets -- host_prefix int32 [B + 1] (host) is written to d_offsets (device)
+// on the stream once every check has passed, K is then the LARGEST count (it sizes the label parts) and T holds host_prefix[B] rows
 static int launch_corr_argmax_any(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2,
-                                  float* lse, int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes) {
+                                  float* lse, int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes,
+                                  const int* host_prefix = nullptr, int* d_offsets = nullptr) {
     const bool conf = label2 || score2 || lse;
+    const bool ragged = host_prefix != nullptr;
     const size_t part_bytes = conf ? 16 : 6;
     if (!g || !T || !scale || !label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
     if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
@@ -483,51 +536,70 @@ static int launch_corr_argmax_any(const void* g, const void* T, const float* sca
     static std::atomic<unsigned long long> attr_done{0};             // per-device opt-in to > 64 KB of dynamic LDS (cf. corr.hip)
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_done.fetch_or(bit, std::memory_order_release);
     }
-    // label splits: the fewest rounds x (panels per split + ~1 panel of set-up) over the CUs
     const size_t npix = (size_t)B * 16 * H * W;
     const int panels = (K + CA_P - 1) / CA_P, cus = device_cu_count(dev) > 0 ? device_cu_count(dev) : 1;
-    int nsplit = 1;
-    long best_cost = 0;
-    for (int s = 1; s <= 8 && s <= panels; ++s) {
-        const int per = (panels + s - 1) / s;
-        if ((per * (s - 1)) >= panels) continue;                       // the last split would be empty
-        if (s > 1 && (!ws || ws_bytes < (size_t)s * npix * part_bytes || ntiles * s >= (1L << 31))) break;
-        const long cost = ((ntiles * s + cus - 1) / cus) * (long)(per + 1);
-        if (s == 1 || cost < best_cost) { best_cost = cost; nsplit = s; }
-    }
+    const int nsplit = ca_pick_split(panels, ntiles, npix, part_bytes, ws != nullptr, ws_bytes, cus);
     const int split_labels = (panels + nsplit - 1) / nsplit * CA_P;
     const size_t pn = (size_t)nsplit * npix;                           // values per workspace plane
     float* wsc = reinterpret_cast<float*>(ws);
     const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+    const unsigned img_pix = (unsigned)(16 * H * W);
+    if (ragged) {
+        for (int i0 = 0; i0 <= B; i0 += 64) {
+            CaOffsetChunk ch;
+            const int n = std::min(64, B + 1 - i0);
+            for (int i = 0; i < 64; ++i) ch.v[i] = i < n ? host_prefix[i0 + i] : 0;
+            hipLaunchKernelGGL(corr_argmax_offsets_kernel, dim3(1), dim3(64), 0, st, d_offsets + i0, ch, n);
+            LSEG_HIP_TRY(hipGetLastError());
+        }
+    }
     if (conf) {
         // workspace planes: score, score2, lse (fp32), label, label2 (int16), each [nsplit][npix]; a part always writes all five
         float *wsc2 = wsc + pn, *wlse = wsc + 2 * pn;
         int16_t *wl = reinterpret_cast<int16_t*>(wsc + 3 * pn), *wl2 = wl + pn;
-        if (nsplit > 1)
-            hipLaunchKernelGGL(corr_argmax_kernel<true>, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
-                               scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse);
+        if (ragged && nsplit > 1)
+            hipLaunchKernelGGL((corr_argmax_kernel<true, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                               (const uint16_t*)T, scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse,
+                               (const int*)d_offsets);
+        else if (ragged)
+            hipLaunchKernelGGL((corr_argmax_kernel<true, true>), dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
+                               scale, label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse, (const int*)d_offsets);
+        else if (nsplit > 1)
+            hipLaunchKernelGGL((corr_argmax_kernel<true, false>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                               (const uint16_t*)T, scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse,
+                               (const int*)nullptr);
         else
-            hipLaunchKernelGGL(corr_argmax_kernel<true>, dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
-                               label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse);
+            hipLaunchKernelGGL((corr_argmax_kernel<true, false>), dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
+                               scale, label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse, (const int*)nullptr);
         LSEG_HIP_TRY(hipGetLastError());
         if (nsplit > 1) {
             hipLaunchKernelGGL(corr_argmax_conf_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, wl2, wsc2, wlse, nsplit, npix, label, score, label2,
-                               score2, lse);
+                               score2, lse, (const int*)d_offsets, split_labels, img_pix);
             LSEG_HIP_TRY(hipGetLastError());
         }
         return 0;
     }
     int16_t* wl = nsplit > 1 ? reinterpret_cast<int16_t*>(wsc + pn) : nullptr;
-    hipLaunchKernelGGL(corr_argmax_kernel<false>, dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T, scale,
-                       nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit, nsplit > 1 ? split_labels : K,
-                       nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr);
+    if (ragged)
+        hipLaunchKernelGGL((corr_argmax_kernel<false, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                           (const uint16_t*)T, scale, nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
+                           nsplit > 1 ? split_labels : K, nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr,
+                           (const int*)d_offsets);
+    else
+        hipLaunchKernelGGL((corr_argmax_kernel<false, false>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                           (const uint16_t*)T, scale, nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
+                           nsplit > 1 ? split_labels : K, nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr,
+                           (const int*)nullptr);
     LSEG_HIP_TRY(hipGetLastError());
     if (nsplit > 1) {
-        hipLaunchKernelGGL(corr_argmax_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, nsplit, npix, label, score);
+        hipLaunchKernelGGL(corr_argmax_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, nsplit, npix, label, score, (const int*)d_offsets,
+                           split_labels, img_pix);
         LSEG_HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -542,6 +614,55 @@ int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t
 int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
                             int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes) {
     return launch_corr_argmax_any(g, T, scale, label, score, label2, score2, lse, B, K, H, W, C, st, ws, ws_bytes);
+}
+
+// the counts of a ragged launch -> their prefix sum (B + 1 entries) and the largest; LSEG_ERR_INVALID for a count outside [1, 32767]
+static int ca_ragged_prefix(const int32_t* host_counts, int B, std::vector<int>& prefix, int& kmax) {
+    if (!host_counts) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: NULL counts");
+    if (B < 1) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: B=%d", B);
+    prefix.assign((size_t)B + 1, 0);
+    long total = 0;
+    kmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int k = host_counts[b];
+        if (k < 1 || k > 32767) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: image %d has %d labels, outside [1, 32767]", b, k);
+        total += k;
+        // the kernel's row origins are int32 and T + row * 512 must stay a valid 2^31-row table
+        if (total > 0x7fffffffL) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_ragged: %ld text rows exceed the kernel's 32-bit row offsets", total);
+        prefix[b + 1] = (int)total;
+        kmax = k > kmax ? k : kmax;
+    }
+    return 0;
+}
+
+// per-image label sets of any size: image b against rows [sum counts[0..b), + counts[b]) of T, labels local to its own list.
+// host_counts int32 [B] on the HOST (validated here, before anything is launched); d_offsets int32 [B + 1] device scratch the launch fills
+// with their prefix sum on the stream.  label2 / score2 / lse all NULL = the plain arg-max instantiation.
+int launch_corr_argmax_ragged(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
+                              float* score, int16_t* label2, float* score2, float* lse, int B, int H, int W, int C, hipStream_t st, void* ws,
+                              size_t ws_bytes) {
+    if (!g || !T || !scale || !label || !d_offsets || !host_counts) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: NULL pointer");
+    if (C != CA_C) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_ragged: C=%d (C must be 512)", C);
+    std::vector<int> prefix;
+    int kmax = 0;
+    if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
+    return launch_corr_argmax_any(g, T, scale, label, score, label2, score2, lse, B, kmax, H, W, C, st, ws, ws_bytes, prefix.data(), d_offsets);
+}
+
+// the label split a ragged launch of this shape would take, without a device: out2 = {parts, labels per part}.  Part s of image b covers the
+// image's labels [s * out2[1], min((s + 1) * out2[1], count_b)) and exists only when that range is not empty.  cus = compute units to plan for
+int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2) {
+    if (!out2) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged_split: NULL pointer");
+    std::vector<int> prefix;
+    int kmax = 0;
+    if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
+    if (H < 2 || W < 2 || cus < 1) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged_split: H=%d W=%d cus=%d", H, W, cus);
+    const long ntiles = (long)B * ((2 * H + CA_LB - 1) / CA_LB) * ((2 * W + CA_LB - 1) / CA_LB);
+    const int panels = (kmax + CA_P - 1) / CA_P;
+    const int nsplit = ca_pick_split(panels, ntiles, (size_t)B * 16 * H * W, conf ? 16 : 6, ws_bytes > 0, ws_bytes, cus);
+    out2[0] = nsplit;
+    out2[1] = (panels + nsplit - 1) / nsplit * CA_P;
+    return 0;
 }
 
 // low: fp32 [B, K, h, w] (the (2h, 2w) logits of the engine); label int16 [B, 2h, 2w]; score fp32 [B, 2h, 2w] or NULL

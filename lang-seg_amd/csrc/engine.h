@@ -136,6 +136,10 @@ public:
     int device;
     bool text_cache = false, text_valid = false, debug = false;
     int group_k = 0;              // > 0: per-image label sets of this size (LSegNetZS), see lseg_set_text_grouping
+    // ragged per-image label sets (lseg_set_text_groups): image b owns groups_[b] consecutive text rows; empty = none
+    int set_text_groups(const int32_t* host_counts, int B);
+    void clear_text_groups() { groups_.clear(); }
+    bool ragged() const { return !groups_.empty(); }
     std::string err;
 
 private:
@@ -161,6 +165,9 @@ private:
     int text_fork(hipStream_t st);
     int text_join(hipStream_t st);
     int check_grouping(int B);
+    int check_ragged(int B, bool labels_only);       // the refusals of a forward while ragged groups are set
+    std::vector<int32_t> groups_;
+    int* d_goff_ = nullptr;                          // [max_batch + 1] prefix sum of groups_, written by the ragged launch
     int flush_events();
     int materialize_low(hipStream_t st);
     bool low_pending_ = false; int low_planes_ = 0, low_k_ = 0;      // low_ = scaled x2 upsample of rpl_ not yet written (one-pass x4 upsample ran)

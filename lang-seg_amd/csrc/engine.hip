@@ -206,6 +206,7 @@ int Engine::init() {
     const size_t Kl = c.max_labels, L = c.text_ctx, W = c.text_width;
     ALLOC(d_tok_, int64_t, Kl * L);
     ALLOC(d_eot_, int, Kl);
+    ALLOC(d_goff_, int, c.max_batch + 1);
     ALLOC(tx_, uint16_t, Kl * L * W);
     ALLOC(tln_, uint16_t, Kl * L * W);
     ALLOC(tq_, uint16_t, Kl * c.text_heads * tnpad_ * 64);
@@ -673,6 +674,40 @@ int Engine::check_grouping(int B) {
     return 0;
 }
 
+// ragged per-image label sets (lseg_set_text_groups): image b against groups_[b] consecutive token rows, streamed only
+int Engine::set_text_groups(const int32_t* host_counts, int B) {
+    if (!host_counts || B == 0) { groups_.clear(); return 0; }
+    if (B < 0 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "text groups: B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
+    long total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (host_counts[b] < 1 || host_counts[b] > 32767)
+            return set_error(LSEG_ERR_INVALID, "text groups: image %d has %d labels, outside [1, 32767]", b, host_counts[b]);
+        total += host_counts[b];
+    }
+    if (total > cfg.max_labels) return set_error(LSEG_ERR_INVALID, "text groups: %ld labels in all > max_labels=%d", total, cfg.max_labels);
+    groups_.assign(host_counts, host_counts + B);
+    group_k = 0;                                     // either grouping clears the other
+    return 0;
+}
+
+// nothing but the streamed labels exists for ragged groups: every other request is refused before a kernel runs, nothing falls back
+int Engine::check_ragged(int B, bool labels_only) {
+    if (groups_.empty()) return 0;
+    if ((int)groups_.size() != B) return set_error(LSEG_ERR_INVALID, "ragged label sets: set for %d images, forward called with B=%d", (int)groups_.size(), B);
+    long total = 0;
+    for (int k : groups_) total += k;
+    if (total != K_) return set_error(LSEG_ERR_INVALID, "ragged label sets: %d token rows != %ld labels over the %d images", K_, total, B);
+    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets are an inference feature (train mode is on)");
+    if (!labels_only)
+        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no logits: only lseg_forward_labels / lseg_forward_labels_conf run with them");
+    const lseg_config& c = cfg;
+    const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
+    if (!commuted || getenv("LSEG_CORR_FULLRES") || (lw_[0] % 2) != 0 || getenv("LSEG_CORR_GENERIC") || c.arch_option != 0 || c.out_c != 512)
+        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets need the streamed kernel: the commuted schedule (no debug taps, no split precision), "
+                                               "out_c 512 (is %d), arch_option 0 (is %d), no LSEG_CORR_GENERIC / LSEG_CORR_FULLRES", c.out_c, c.arch_option);
+    return 0;
+}
+
 static bool splitk_enabled() {                           // LSEG_SPLITK=0 (tools) switches both split-K plans off
     static const int on = getenv("LSEG_SPLITK") ? atoi(getenv("LSEG_SPLITK")) : 1;
     return on != 0;
@@ -948,7 +983,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
     if (!x_in) return set_error(LSEG_ERR_INVALID, "x is NULL");
     if (score_out && !label_out) return set_error(LSEG_ERR_INVALID, "a score output needs the label output");
-    if (label_out && (group_k > 0 ? group_k : K_) > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "int16 labels need K <= 32767 (K=%d)", K_);
+    if (label_out && !ragged() && (group_k > 0 ? group_k : K_) > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "int16 labels need K <= 32767 (K=%d)", K_);
+    TRY(check_ragged(B, label_out && !logits && !argmax_out && !low_out));
     LSEG_HIP_TRY(hipSetDevice(device));
     labels_only_ = false;
     if (train_mode) {                    // net.train(): activations saved for lseg_backward, BatchNorm on batch statistics
@@ -1072,7 +1108,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         // the dedicated kernel (corr.hip): T resident in LDS, g streamed once, label planes and cell dot products from the same registers;
         // per-image label sets (zero-shot), other widths and label sets that do not fit the LDS take the generic GEMM + pixel_gram pair
         static const bool corr_generic = getenv("LSEG_CORR_GENERIC") != nullptr;    // A/B switch (tools, tests): the round-4 pair
-        const bool corr_fused = !corr_generic && group_k == 0 && corr_planes_supported(K_, c.out_c);
+        const bool corr_fused = !corr_generic && group_k == 0 && !ragged() && corr_planes_supported(K_, c.out_c);
         // "correlation" family = the dedicated kernel only (label planes + cell dot products; algorithmic BYTES in the flops slot): the generic
         // pair is not bracketed, so no event is taken that would never be paired (the pool is sized per family and forward)
         hipEvent_t pc = corr_fused ? prof_begin(PF_CORR, st) : nullptr;
@@ -1090,6 +1126,15 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         // full-resolution planes.  The scale plane must be the logits path's bit for bit, so the gram comes from where it comes there: for
         // K <= 157 from corr_planes_kernel (which also writes its quarter-resolution planes into rpl_, 8.9 MB per image at K = 150, that
         // nothing reads here: the two grams differ in the last bits and the score would no longer equal logits.max), above from pixel_gram
+        if (ragged()) {
+            // per-image label sets of any size (check_ragged let only the streamed labels through): the scale plane from pixel_gram, as for
+            // K > 157 above -- corr_planes has no per-image form; low_ is the workspace of the label parts, sized from the largest list
+            TRY(launch_corr_argmax_ragged(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.label2, cf.score2, cf.lse, B,
+                                          lh_[0], lw_[0], c.out_c, st, low_, (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
+            labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;
+            prof_end(PF_FWD, fwd0, 0.0, st);
+            return 0;
+        }
         if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
             // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
             TRY(launch_corr_argmax_conf(g16pad_, tnorm_, nscale_, label_out, score_out, cf.label2, cf.score2, cf.lse, B, K_, lh_[0], lw_[0], c.out_c, st,

@@ -117,6 +117,14 @@ int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, in
                             int B, int K, int H, int W, int C, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
 int launch_seg_conf16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
                       hipStream_t st);
+// ragged per-image label sets: image b against host_counts[b] consecutive rows of T, labels local to its list.  host_counts int32 [B] on
+// the host (each in [1, 32767]); d_offsets int32 [B + 1] device scratch, filled with their prefix sum on the stream.  label2 / score2 / lse
+// all NULL = the arg-max instantiation.  ws as above, the parts sized from the largest count
+int launch_corr_argmax_ragged(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
+                              float* score, int16_t* label2, float* score2, float* lse, int B, int H, int W, int C, hipStream_t st,
+                              void* ws = nullptr, size_t ws_bytes = 0);
+// host only: out2 = {label parts, labels per part} of that launch when it plans for `cus` compute units
+int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2);
 // episode.hip -- few-shot episode evaluation (Evaluator.classify_prediction + AverageMeter.update + the 2-class criterion): scores fp32
 // [B,2,H,W] (up = 0) or low-resolution logits [B,2,H/2,W/2] read through the x2 bilinear (up = 1), target int64 / ignore uint8 (or NULL)
 // [B,H,W] -> areas int64 [B,6], nll double [B,2], flags int64 [2], optional scatter into the meter's int64 [2,nclass] buffers

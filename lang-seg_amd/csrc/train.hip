@@ -45,6 +45,7 @@ static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 int Engine::set_train(bool on) {
     if (on) {
+        if (ragged()) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets (lseg_set_text_groups) are an inference feature: clear them before lseg_set_train");
         // flags bit 6 opts in to training the decoder above the tower (train-mode BatchNorm in the tower, no bottleneck backward)
         if (resnet_ && !rn_train_)
             return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only (no train-mode BatchNorm / bottleneck backward)");

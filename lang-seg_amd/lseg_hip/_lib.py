@@ -57,6 +57,7 @@ SIGNATURES = {
     "lseg_set_text_cache": (_i, [_vp, _i]),
     "lseg_get_text_features": (_i, [_vp, _vp, _vp]),
     "lseg_set_text_grouping": (_i, [_vp, _i]),
+    "lseg_set_text_groups": (_i, [_vp, _vp, _i]),
     "lseg_overflow_seen": (_i, [_vp, _i]),
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -89,6 +90,8 @@ SIGNATURES = {
     "lseg_op_corr_argmax_geometry": (_i, [_vp]),
     "lseg_op_corr_argmax": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_corr_argmax_conf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lseg_op_corr_argmax_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lseg_op_corr_argmax_ragged_split": (_i, [_vp, _i, _i, _i, _i, C.c_size_t, _i, _vp]),
     "lseg_op_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_vit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_res32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

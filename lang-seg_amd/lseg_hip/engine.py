@@ -108,6 +108,7 @@ class HipEngine:
         self._h = h
         self._K = 0
         self._group = 0
+        self._groups: Optional[List[int]] = None           # ragged per-image label sets (lseg_set_text_groups)
         self._keep: List[torch.Tensor] = []
         self.training = False
         self.image_dtype = image_dtype
@@ -150,9 +151,13 @@ class HipEngine:
         _lib.check(self.lib.lseg_finalize_params(self._h, C.c_void_p(st)))
 
     # ---- text -------------------------------------------------------------------------------------------
-    def set_tokens(self, tokens: torch.Tensor, labels_per_image: int = 0):
+    def set_tokens(self, tokens: torch.Tensor, labels_per_image: int = 0, group_sizes: Optional[Sequence[int]] = None):
         """tokens int64 [K, ctx].  labels_per_image = k > 0 (LSegNetZS, lseg_net_zs.py:177-214): the K = B*k rows are
-        per-image label sets, image b is correlated with rows [b*k, (b+1)*k) and forward returns [B, k, H, W]."""
+        per-image label sets, image b is correlated with rows [b*k, (b+1)*k) and forward returns [B, k, H, W].
+        group_sizes = [k_0, .., k_{B-1}] (lseg_set_text_groups): ragged per-image label sets -- image b owns k_b consecutive rows of the
+        K = sum(k_b); forward_labels / forward_labels_conf then return labels indexing each image's own list, every other forward raises."""
+        if group_sizes is not None and labels_per_image:
+            raise ValueError("labels_per_image and group_sizes are two different groupings: give one")
         tok = tokens.detach().to("cpu", torch.int64).contiguous()
         K, ctx = tok.shape
         arr = (C.c_int64 * (K * ctx)).from_buffer_copy(tok.numpy().tobytes())
@@ -160,17 +165,33 @@ class HipEngine:
         _lib.check(self.lib.lseg_set_text_grouping(self._h, int(labels_per_image)))
         self._K = K
         self._group = int(labels_per_image)
+        self._set_groups(group_sizes)
 
-    def set_text_features(self, feat: torch.Tensor):
+    def _set_groups(self, group_sizes: Optional[Sequence[int]]):
+        self._groups = None
+        if group_sizes is None:
+            _lib.check(self.lib.lseg_set_text_groups(self._h, None, 0))
+            return
+        sizes = [int(k) for k in group_sizes]
+        if not sizes or sum(sizes) != self._K:
+            raise ValueError(f"group_sizes {sizes} do not add up to the {self._K} text rows")
+        _lib.check(self.lib.lseg_set_text_groups(self._h, (C.c_int32 * len(sizes))(*sizes), len(sizes)))
+        self._groups = sizes
+
+    def set_text_features(self, feat: torch.Tensor, group_sizes: Optional[Sequence[int]] = None):
         """fp16 [K, out_c] text features computed elsewhere (un-normalised `encode_text` output or already normalised): replaces the
-        tokens; the engine's text tower is not run until set_tokens is called again (lseg_set_text_features)."""
+        tokens; the engine's text tower is not run until set_tokens is called again (lseg_set_text_features).  group_sizes: as in
+        set_tokens (ragged per-image label sets over the K rows)."""
         f = feat.detach().to(self.device, torch.float16).contiguous()
         if f.dim() != 2 or f.shape[1] != self.cfg.out_c:
             raise ValueError(f"text features must be [K, {self.cfg.out_c}], got {tuple(f.shape)}")
         _lib.check(self.lib.lseg_set_text_features(self._h, C.c_void_p(f.data_ptr()), f.shape[0], C.c_void_p(_stream_ptr(self.device))))
         self._keep = [f]
         self._K = f.shape[0]
+        if self._group:
+            _lib.check(self.lib.lseg_set_text_grouping(self._h, 0))
         self._group = 0
+        self._set_groups(group_sizes)
 
     def encode_text(self) -> torch.Tensor:
         _lib.check(self.lib.lseg_encode_text(self._h, C.c_void_p(_stream_ptr(self.device))))
@@ -192,7 +213,15 @@ class HipEngine:
             raise ValueError(f"engine was planned for 3x{self.img_h}x{self.img_w}, got {Cc}x{H}x{W}")
         if self._group > 0 and self._K != B * self._group:
             raise ValueError(f"per-image label sets: {self._K} token rows != batch {B} x {self._group}")
+        if self._groups is not None and len(self._groups) != B:
+            raise ValueError(f"ragged per-image label sets: {len(self._groups)} label lists != batch {B}")
         return x
+
+    def _refuse_ragged(self, x: torch.Tensor):
+        """ragged label sets have no logits: the C entry refuses before any kernel runs (LSEG_ERR_UNSUPPORTED), with its own message"""
+        if self._groups is not None:
+            _lib.check(self.lib.lseg_forward(self._h, C.c_void_p(x.data_ptr()), x.shape[0], None, None, C.c_void_p(_stream_ptr(self.device))))
+            raise RuntimeError("lseg_forward accepted ragged label sets")
 
     def forward_labels(self, x: torch.Tensor, want_score: bool = False):
         """Masks for any K <= 32767 (lseg_forward_labels): int16 [B,H,W] = torch.max(logits, 1)[1] of the logits forward() would return,
@@ -229,6 +258,7 @@ class HipEngine:
         """fp32 [B,Kout,H/2,W/2]: the logits before output_conv's x2 bilinear (lseg_forward_lowres) -- lseg_op_upsample2x_planes of them is
         bit-identical to forward(x); the [B,Kout,H,W] tensor is never written."""
         x = self._check_input(x)
+        self._refuse_ragged(x)
         B, _, H, W = x.shape
         Kout = self._group if self._group > 0 else self._K
         low = torch.empty((B, Kout, H // 2, W // 2), dtype=torch.float32, device=self.device)
@@ -239,6 +269,7 @@ class HipEngine:
 
     def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):
         x = self._check_input(x)
+        self._refuse_ragged(x)
         B, Cc, H, W = x.shape
         Kout = self._group if self._group > 0 else self._K
         if want_argmax and not want_logits and Kout > 256:

@@ -394,7 +394,8 @@ class LSegmentationModule(_Base):
 
     def predict_labels(self, x, labelset="", confidence=False):
         """The mask torch.max(pred, 1)[1] (:114-117; lseg_app.py:350-355) as torch.long [B,H,W] for any label set, without the logits;
-        confidence=True: the dict of LSegNet.predict_labels (label, prob, label2, margin)."""
+        confidence=True: the dict of LSegNet.predict_labels (label, prob, label2, margin).  labelset may be a list of one label list
+        per image (ragged per-image label sets): the labels then index each image's own list."""
         return self.net.predict_labels(x, labelset, confidence)
 
     def evaluate(self, x, target=None):                       # :43-52

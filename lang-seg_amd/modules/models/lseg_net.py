@@ -290,7 +290,16 @@ class LSeg(BaseModel):
         torch.long [B,H,W], for any K <= 32767, without the [B,K,H,W] logits (lseg_forward_labels).
         confidence=True (lseg_forward_labels_conf) returns a dict instead: "label" (that mask), "prob" = the winner's softmax
         probability over the label set, exp(score - logsumexp), "label2" = the runner-up label (torch.long; -1 with a single label) and
-        "margin" = the top-2 logit margin (inf with a single label) -- what softmax / topk on the logits would give, without them."""
+        "margin" = the top-2 logit margin (inf with a single label) -- what softmax / topk on the logits would give, without them.
+        labelset may also be a list of B label lists, one per image and of any lengths ([["cat", "grass"], ["road", "car", "sky"], ..]:
+        open-vocabulary requests batched into one forward, lseg_set_text_groups): the labels then index each image's OWN list.  A
+        string or a flat list keeps its meaning: one label set shared by the batch."""
+        groups = None
+        if isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset):
+            groups = [len(ls) for ls in labelset]
+            if len(groups) != x.shape[0] or min(groups) < 1:
+                raise ValueError(f"per-image label lists: {len(groups)} lists (sizes {groups}) for a batch of {x.shape[0]}; every image needs >= 1 label")
+            labelset = [lab for ls in labelset for lab in ls]               # encoded once per occurrence, image 0's labels first
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet.predict_labels needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
@@ -302,11 +311,13 @@ class LSeg(BaseModel):
                 eng = self._engine(B, H, W, text.shape[0], x.device)
                 if eng.training:
                     eng.set_train(False)
-                self._set_tokens(eng, text, labelset)
+                self._set_tokens(eng, text, labelset, groups)
                 self._last_engine = eng
                 r = eng.forward_labels_conf(x.float()) if confidence else eng.forward_labels(x.float())
-                if self._range_guard(eng, x.device):
-                    return self.predict_labels(x, labelset, confidence)         # fell back to bf16: run again on a bf16 engine
+                if self._range_guard(eng, x.device):                            # fell back to bf16: run again on a bf16 engine
+                    if groups is not None:
+                        labelset = [labelset[sum(groups[:b]):sum(groups[:b + 1])] for b in range(len(groups))]
+                    return self.predict_labels(x, labelset, confidence)
                 if not confidence:
                     return r.long()
                 return {"label": r["label"].long(), "prob": torch.exp(r["score"] - r["lse"]), "label2": r["label2"].long(),
@@ -360,10 +371,12 @@ class LSeg(BaseModel):
             eng.set_train(True)
         return eng
 
-    def _set_tokens(self, eng, text, labelset):
+    def _set_tokens(self, eng, text, labelset, groups=None):
         tkey = (tuple(text.shape), text.data_ptr() if labelset == "" else hash(text.numpy().tobytes()))
+        if groups is not None:
+            tkey = tkey + (tuple(groups),)
         if eng._tok != tkey:
-            eng.set_tokens(text)
+            eng.set_tokens(text, group_sizes=groups)
             eng._tok = tkey
         eng.set_text_cache(bool(self.cache_text))
 
