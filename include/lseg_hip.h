@@ -233,6 +233,34 @@ int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* 
  * the "lowres" tap work.  Train mode: LSEG_ERR_UNSUPPORTED; a NULL output: LSEG_ERR_INVALID. */
 int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream);
 
+/* Label panels over held image features: run the image tower once, keep what the correlation reads, score any slice of the label set
+ * from it later (the multi-scale evaluator's BatchedMultiEval.forward_labels: peak memory set by the panel, not by K).
+ *   lseg_features_bytes    the sizes of the two held buffers for B images at the engine's img_h / img_w: feat fp16
+ *                          [B, img_h/4 + 2, img_w/4 + 2, out_c] (the head feature map g before the x2 upsample, padded NHWC: 15.2 MB per
+ *                          480 x 480 image) and scale fp32 [B, img_h/2, img_w/2] (logit_scale / ||up(g)|| per low-resolution pixel)
+ *   lseg_forward_features  the inference forward of lseg_forward through the commuted head GEMM, the cell dot products and the scale
+ *                          plane, then both copied into the caller's buffers device to device.  No text is read (no label set needs to be
+ *                          set); the dot products always come from the stand-alone kernel -- the route lseg_forward_lowres takes for
+ *                          K > 157 -- whatever K is set.  Overflow sentinel and profiling as in lseg_forward.
+ *   lseg_score_features    dev_low_out fp32 [B, rows, img_h/2, img_w/2] = the low-resolution logits (lseg_forward_lowres' output) of text
+ *                          rows [row0, row0 + rows) of the CURRENT label set for the held images: the generic correlation GEMM on that
+ *                          slice of the text matrix, then the scaled x2 upsample with the held scale plane.  The text is encoded first
+ *                          under the rules of lseg_forward (text cache, external text features).  For a label set lseg_forward_lowres
+ *                          runs on the same route (K > 157 at out_c = 512, or LSEG_CORR_GENERIC) plane row0 + j equals its plane
+ *                          row0 + j bit for bit, for any row0 and rows: an output element is one chain of MFMAs over the 512 channels
+ *                          in ascending order whatever tile the row count picks, and nothing is split.  For smaller label sets the two
+ *                          differ in the last bits of the scale plane (the fused kernel's dot products).  Buffers 16-byte aligned.
+ * Both are accepted where the commuted correlation runs: the commuted schedule (no debug taps, no split precision), arch_option 0, an
+ * even img_w/4, no LSEG_CORR_FULLRES, one label set shared by the batch, inference mode (any out_c the engine accepts: at widths other
+ * than 512 lseg_forward_lowres takes the generic route for every K, so the planes are bit-identical for every K); per-image label sets of either
+ * kind, train mode and everything else return LSEG_ERR_UNSUPPORTED before any kernel runs -- nothing falls back.  rows < 1 or
+ * row0 + rows > K: LSEG_ERR_INVALID; B outside [1, max_batch]: LSEG_ERR_INVALID.  Afterwards the engine is in the state of a streamed
+ * forward: lseg_forward_stats, lseg_episode_stats and the "lowres" tap return LSEG_ERR_STATE until another forward has run. */
+int lseg_features_bytes(lseg_handle h, int B, size_t* feat_bytes, size_t* scale_bytes);
+int lseg_forward_features(lseg_handle h, const float* dev_x, int B, void* dev_feat_out, float* dev_scale_out, void* stream);
+int lseg_score_features(lseg_handle h, const void* dev_feat, const float* dev_scale, int B, int row0, int rows, float* dev_low_out,
+                        void* stream);
+
 /* The metric / loss step after the path, without the full-resolution logits: statistics of the LAST lseg_forward's output against a
  * target mask -- replaces batch_pix_accuracy + batch_intersection_union on `pred` (lsegmentation_module.py:49-50,59-60) and the value
  * of the criterion (:72).  dev_target int64 [B,img_h,img_w]; dev_counts / dev_nll as in lseg_op_seg_stats. */
@@ -535,6 +563,24 @@ int lseg_op_eval_accumulate_window_lowres(const float* d_low, float* d_sum, int 
                                           int h_grids, int w_grids, int flip, int first_box, int n_box, void* stream);
 int lseg_op_eval_finalize(const float* d_sum, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride, int h_grids,
                           int w_grids, void* stream);
+/* Label panels of the multi-scale evaluator (BatchedMultiEval.forward_labels): fold one panel of fused scores into a running per-pixel
+ * state, so that torch.max / torch.sort / torch.logsumexp over a [K,H,W] score tensor need no such tensor.
+ *   d_scores fp32 [rows,H,W]: the scores of labels row0 .. row0+rows-1, taken in ascending label order
+ *   d_label int16 / d_score fp32 [H,W]: the arg-max so far and its score (required)
+ *   d_label2 int16 / d_score2 fp32 [H,W]: the runner-up; d_sum fp32 [H,W]: the sum of exp(score_k - best) over the labels seen
+ * Per pixel and plane: `if v > best: (second, label2) = (best, label); (best, label) = (v, k)  elif v > second: (second, label2) = (v, k)`
+ * -- entries 0 and 1 of a stable descending sort over all labels submitted (equal values go to the lower label; a later label equal to
+ * the winner is the runner-up), the rules of lseg_forward_labels_conf -- and the online log-sum-exp of csrc/corr_argmax.hip's CONF
+ * instantiation, relative to the running best in fp32: a new best rescales, sum = sum * exp(old_best - new_best) + 1, any other value
+ * adds exp(v - best).  first = 1: the state is written without being read (no clear launch); last = 1: d_sum receives
+ * score + log(sum), the log-sum-exp.  One label in all: label2 = -1, score2 = -inf.  d_label2, d_score2, d_sum may each be NULL, on
+ * EVERY call of a sequence or on none (d_label2 needs d_score2, its running state); with all three NULL only (best, label) is kept and
+ * equals the first two outputs of the full form bit for bit.  Pointers aligned to their element; a lane owns four consecutive pixels
+ * and uses 16-byte accesses wherever an address allows.  row0 + rows > 32767: LSEG_ERR_UNSUPPORTED; NULL required pointers, rows < 1,
+ * row0 < 0: LSEG_ERR_INVALID. */
+int lseg_op_eval_merge_labels(const float* d_scores, int rows, int row0, int H, int W,
+                              int16_t* d_label, float* d_score, int16_t* d_label2, float* d_score2, float* d_sum,
+                              int first, int last, void* stream);
 
 /* Backward of one Linear layer y = x W^T + b -- first brick of the training step (the reference gets
  * it from torch autograd under LSegmentationModule.training_step, lsegmentation_module.py:66-81).  bf16/fp16 operands,

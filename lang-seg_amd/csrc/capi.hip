@@ -117,6 +117,25 @@ int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low
     return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, dev_low_out);
 }
 
+int lseg_features_bytes(lseg_handle h, int B, size_t* feat_bytes, size_t* scale_bytes) {
+    GUARD(h);
+    if (B < 1 || B > h->e->cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, h->e->cfg.max_batch);
+    h->e->features_bytes(B, feat_bytes, scale_bytes);
+    return LSEG_OK;
+}
+
+int lseg_forward_features(lseg_handle h, const float* dev_x, int B, void* dev_feat_out, float* dev_scale_out, void* stream) {
+    GUARD(h);
+    if (!dev_feat_out || !dev_scale_out) return set_error(LSEG_ERR_INVALID, "held-feature output is NULL");
+    const Engine::HeldOut held{dev_feat_out, dev_scale_out};
+    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, &held);
+}
+
+int lseg_score_features(lseg_handle h, const void* dev_feat, const float* dev_scale, int B, int row0, int rows, float* dev_low_out, void* stream) {
+    GUARD(h);
+    return h->e->score_features(dev_feat, dev_scale, B, row0, rows, dev_low_out, (hipStream_t)stream);
+}
+
 int lseg_forward_stats(lseg_handle h, const int64_t* dev_target, int ignore_index, int64_t* dev_counts, double* dev_nll, void* stream) {
     GUARD(h);
     return h->e->forward_stats(dev_target, ignore_index, dev_counts, dev_nll, (hipStream_t)stream);
@@ -579,6 +598,18 @@ int lseg_op_eval_finalize(const float* d_sum, float* d_map, int K, int height, i
     if (r) return r;
     r = require_device(); if (r) return r;
     return launch_eval_finalize(d_sum, d_map, K, height, width, crop, stride, h_grids, w_grids, (hipStream_t)stream);
+}
+int lseg_op_eval_merge_labels(const float* d_scores, int rows, int row0, int H, int W, int16_t* d_label, float* d_score, int16_t* d_label2,
+                              float* d_score2, float* d_sum, int first, int last, void* stream) {
+    if (!d_scores || !d_label || !d_score) return set_error(LSEG_ERR_INVALID, "eval_merge_labels: NULL pointer (scores, label and score are required)");
+    if (rows < 1 || row0 < 0 || H < 1 || W < 1) return set_error(LSEG_ERR_INVALID, "eval_merge_labels: bad shape");
+    if ((long long)row0 + rows > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "eval_merge_labels: int16 labels need row0 + rows <= 32767 (%d + %d)", row0, rows);
+    if (d_label2 && !d_score2) return set_error(LSEG_ERR_INVALID, "eval_merge_labels: the runner-up label needs the runner-up score (its running state)");
+    if ((((uintptr_t)d_scores | (uintptr_t)d_score | (uintptr_t)d_score2 | (uintptr_t)d_sum) & 3) || (((uintptr_t)d_label | (uintptr_t)d_label2) & 1))
+        return set_error(LSEG_ERR_INVALID, "eval_merge_labels: pointers must be aligned to their element");
+    int r = require_device(); if (r) return r;
+    return launch_eval_merge_labels(d_scores, rows, row0, H, W, d_label, d_score, d_label2, d_score2, d_sum, first ? 1 : 0, last ? 1 : 0,
+                                    (hipStream_t)stream);
 }
 int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, void* stream) {
     int r = require_device(); if (r) return r;

@@ -96,8 +96,16 @@ public:
     // low_out (fp32 [B,Kout,img_h/2,img_w/2], lseg_forward_lowres): the logits output_conv would upsample, in the caller's buffer
     // conf (lseg_forward_labels_conf; needs label_out): the runner-up and the log-sum-exp over the labels beside the arg-max, each optional
     struct LabelConf { int16_t* label2; float* score2; float* lse; };
+    // held (lseg_forward_features): the forward stops behind the scale plane and copies what the correlation reads -- g16pad_ and
+    // nscale_ -- into the caller's buffers; no text is read, the gram is pixel_gram's whatever K is set
+    struct HeldOut { void* feat; float* scale; };
     int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
-                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr);
+                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr, const HeldOut* held = nullptr);
+    // label panels over held features (lseg_forward_features / lseg_score_features): the bytes of the two held buffers for B images, and
+    // the low-resolution logits of text rows [row0, row0 + rows) from them -- correlate_planes + upsample2x_planes_scaled, the K > 157
+    // route of lseg_forward_lowres plane for plane
+    void features_bytes(int B, size_t* feat_bytes, size_t* scale_bytes) const;
+    int score_features(const void* feat, const float* scale, int B, int row0, int rows, float* low_out, hipStream_t st);
     int get_text_features(void* out_f16, hipStream_t st);
     int forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st);
     // few-shot episode statistics of the last forward's 2 label planes (episode.hip), inference or train-mode forward alike
@@ -166,6 +174,7 @@ private:
     int text_join(hipStream_t st);
     int check_grouping(int B);
     int check_ragged(int B, bool labels_only);       // the refusals of a forward while ragged groups are set
+    int check_held(const char* what);                // the refusals of lseg_forward_features / lseg_score_features: where corr_low does not hold
     std::vector<int32_t> groups_;
     int* d_goff_ = nullptr;                          // [max_batch + 1] prefix sum of groups_, written by the ragged launch
     int flush_events();

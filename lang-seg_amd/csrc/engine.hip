@@ -708,7 +708,56 @@ int Engine::check_ragged(int B, bool labels_only) {
     return 0;
 }
 
-static bool splitk_enabled() {                           // LSEG_SPLITK=0 (tools) switches both split-K plans off
+// held features exist only where the forward's corr_low holds (the correlation commuted below the x2 upsample reads g16pad_ and nscale_ and
+// nothing else) and for one label set shared by the batch: everything else is refused before a kernel runs, nothing falls back
+int Engine::check_held(const char* what) {
+    const lseg_config& c = cfg;
+    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "%s is an inference feature (train mode is on)", what);
+    if (group_k > 0 || ragged()) return set_error(LSEG_ERR_UNSUPPORTED, "%s: per-image label sets have no held-feature form (one label set shared by the batch)", what);
+    const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
+    // (no bound on out_c: pixel_gram and the generic GEMM take every width the engine accepts -- the 512 of the streamed labels is the
+    // width of THEIR kernel, which nothing here runs)
+    if (!commuted || getenv("LSEG_CORR_FULLRES") || (lw_[0] % 2) != 0 || c.arch_option != 0)
+        return set_error(LSEG_ERR_UNSUPPORTED, "%s needs the commuted correlation: the commuted schedule (no debug taps, no split precision), "
+                                               "arch_option 0 (is %d), an even quarter-resolution width (is %d), no LSEG_CORR_FULLRES",
+                         what, c.arch_option, lw_[0]);
+    return 0;
+}
+
+void Engine::features_bytes(int B, size_t* feat_bytes, size_t* scale_bytes) const {
+    if (feat_bytes) *feat_bytes = (size_t)B * (lh_[0] + 2) * (lw_[0] + 2) * cfg.out_c * sizeof(uint16_t);
+    if (scale_bytes) *scale_bytes = (size_t)B * 4 * lh_[0] * lw_[0] * sizeof(float);
+}
+
+// Low-resolution logits of text rows [row0, row0 + rows) from held features: R = T[row0 ..] . g^T through the generic GEMM, then the scaled
+// x2 upsample with the HELD scale plane -- the two launches lseg_forward_lowres makes for K > 157, on a slice of T.  A plane's dot products
+// do not depend on the slice: every tile shape of the GEMM (64 x 64, 128 x 128, the 160-row label tile) accumulates an output element
+// through the same chain of 16x16x32 MFMAs over ascending k and nothing is split (the contraction is 512 long), so the tile the row count
+// picks moves no bit.
+int Engine::score_features(const void* feat, const float* scale, int B, int row0, int rows, float* low_out, hipStream_t st) {
+    if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
+    if (K_ < 1) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
+    if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
+    if (!feat || !scale || !low_out) return set_error(LSEG_ERR_INVALID, "lseg_score_features: NULL pointer");
+    if (((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(low_out)) & 15) != 0)
+        return set_error(LSEG_ERR_INVALID, "lseg_score_features: the buffers must be 16-byte aligned");
+    if (rows < 1 || row0 < 0 || (long)row0 + rows > K_)
+        return set_error(LSEG_ERR_INVALID, "lseg_score_features: rows [%d, %d + %d) are not inside the %d labels", row0, row0, rows, K_);
+    TRY(check_held("lseg_score_features"));
+    LSEG_HIP_TRY(hipSetDevice(device));
+    if (eval_stale_) TRY(finalize(st));
+    TRY(text_fork(st));                  // the text tower under the rules of the forward (text cache, external features)
+    TRY(text_join(st));
+    const lseg_config& c = cfg;
+    const int hp = lh_[0] + 2, wp = lw_[0] + 2;
+    TRY(correlate_planes(tnorm_ + (size_t)row0 * c.out_c, (const uint16_t*)feat, rows, B * hp * wp, hp * wp, rpl_, 0, st));
+    TRY(launch_upsample2x_planes_scaled(rpl_, scale, low_out, B * rows, rows, lh_[0], lw_[0], st));
+    // the state of a streamed forward: low_ holds no planes, nothing is pending
+    last_B_ = B; low_pending_ = false; labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;
+    return 0;
+}
+
+static bool splitk_enabled() {                         // LSEG_SPLITK=0 (tools) switches both split-K plans off
     static const int on = getenv("LSEG_SPLITK") ? atoi(getenv("LSEG_SPLITK")) : 1;
     return on != 0;
 }
@@ -975,13 +1024,14 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
 }
 
 int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
-                    float* low_out, const LabelConf* conf) {
+                    float* low_out, const LabelConf* conf, const HeldOut* held) {
     const LabelConf cf = conf ? *conf : LabelConf{nullptr, nullptr, nullptr};
     if ((cf.label2 || cf.score2 || cf.lse) && !label_out) return set_error(LSEG_ERR_INVALID, "the confidence outputs need the label output");
     if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
-    if (K_ < 1) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
+    if (K_ < 1 && !held) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
     if (!x_in) return set_error(LSEG_ERR_INVALID, "x is NULL");
+    if (held) TRY(check_held("lseg_forward_features"));      // (groupings and train mode are refused there: nothing below meets them)
     if (score_out && !label_out) return set_error(LSEG_ERR_INVALID, "a score output needs the label output");
     if (label_out && !ragged() && (group_k > 0 ? group_k : K_) > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "int16 labels need K <= 32767 (K=%d)", K_);
     TRY(check_ragged(B, label_out && !logits && !argmax_out && !low_out));
@@ -1001,7 +1051,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     hipEvent_t fwd0 = prof_begin(PF_FWD, st);
     const double ntok2 = (double)ntok_ * ntok_;
 
-    TRY(text_fork(st));                  // ---- text tower (lseg_net.py:181-183) on the side stream
+    if (!held) TRY(text_fork(st));       // ---- text tower (lseg_net.py:181-183) on the side stream; held features read no text
 
     GemmArgs g;
     if (resnet_) {
@@ -1092,8 +1142,10 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
     for (int r = 4; r >= 1; --r) TRY(refine(r, B, st, commuted && r == 1));
 
-    TRY(text_join(st));                  // before the correlation
-    TRY(check_grouping(B));
+    if (!held) {
+        TRY(text_join(st));              // before the correlation
+        TRY(check_grouping(B));
+    }
 
     // ---- head1 + normalise + correlation (lseg_net.py:185-196) ------------------------------------------------
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp = B * hw1;
@@ -1108,7 +1160,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         // the dedicated kernel (corr.hip): T resident in LDS, g streamed once, label planes and cell dot products from the same registers;
         // per-image label sets (zero-shot), other widths and label sets that do not fit the LDS take the generic GEMM + pixel_gram pair
         static const bool corr_generic = getenv("LSEG_CORR_GENERIC") != nullptr;    // A/B switch (tools, tests): the round-4 pair
-        const bool corr_fused = !corr_generic && group_k == 0 && !ragged() && corr_planes_supported(K_, c.out_c);
+        const bool corr_fused = !held && !corr_generic && group_k == 0 && !ragged() && corr_planes_supported(K_, c.out_c);
         // "correlation" family = the dedicated kernel only (label planes + cell dot products; algorithmic BYTES in the flops slot): the generic
         // pair is not bracketed, so no event is taken that would never be paired (the pool is sized per family and forward)
         hipEvent_t pc = corr_fused ? prof_begin(PF_CORR, st) : nullptr;
@@ -1122,6 +1174,17 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         LSEG_HIP_TRY(hipMemcpyAsync(ovf_host_, ovf_dev_, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         LSEG_HIP_TRY(hipEventRecord(ev_ovf_, st));
         ovf_pending_ = true;
+        if (held) {
+            // what the correlation reads, handed to the caller: any label panel can be scored from it later (score_features).  The gram
+            // above is pixel_gram's for every K, so the scale plane is the one lseg_forward_lowres uses on its generic route (K > 157)
+            size_t fb = 0, sb = 0;
+            features_bytes(B, &fb, &sb);
+            LSEG_HIP_TRY(hipMemcpyAsync(held->feat, g16pad_, fb, hipMemcpyDeviceToDevice, st));
+            LSEG_HIP_TRY(hipMemcpyAsync(held->scale, nscale_, sb, hipMemcpyDeviceToDevice, st));
+            labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;       // the state of a streamed forward: no low-resolution logits exist
+            prof_end(PF_FWD, fwd0, 0.0, st);
+            return 0;
+        }
         // masks only, any K: the labels stream past a running (best, arg) pair per output pixel (corr_argmax.hip) -- no (2h, 2w) logits, no
         // full-resolution planes.  The scale plane must be the logits path's bit for bit, so the gram comes from where it comes there: for
         // K <= 157 from corr_planes_kernel (which also writes its quarter-resolution planes into rpl_, 8.9 MB per image at K = 150, that

@@ -357,6 +357,98 @@ __global__ void eval_resize_kernel(const float* __restrict__ src, float* __restr
     }
 }
 
+// ---- label panels: fold `rows` score planes [rows, npix] (labels row0 .. row0 + rows - 1, ascending) into the running per-pixel state
+// (best, label, runner-up, label2, s = sum of exp(value - best)); the stable descending top-2 of lseg_forward_labels_conf -- strict `>`
+// twice, so equal values go to the lower label and a later label equal to the winner is the runner-up -- and its online log-sum-exp whose
+// running maximum IS best: one exp per value, exp(-|v - best|) rescales s when v is the new best and is v's own term otherwise (best =
+// -inf before the first label: exp(-inf) = 0 and s starts at 1).  HBM-bound: every score is read once, the state once per panel.
+// A lane owns one run of four consecutive pixels of the flattened [H, W] map and walks the panel's planes with the state in registers.
+// The run frame is the score plane's (run_frame), so its interior runs are 16 bytes aligned; every other array -- and every plane of the
+// panel, whose alignment moves with npix -- takes the vector access where ITS address allows and element accesses otherwise.
+template <typename V, typename T>
+__device__ __forceinline__ void load_run(const T* p, bool full, const bool (&m)[4], T (&o)[4]) {
+    if (full && (reinterpret_cast<uintptr_t>(p) & (sizeof(V) - 1)) == 0) {
+        const V t = *reinterpret_cast<const V*>(p);
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (m[e]) o[e] = p[e];
+    }
+}
+template <typename V, typename T>
+__device__ __forceinline__ void store_run_any(T* p, bool full, const bool (&m)[4], const T (&o)[4]) {
+    if (full && (reinterpret_cast<uintptr_t>(p) & (sizeof(V) - 1)) == 0) {
+        const V t = {o[0], o[1], o[2], o[3]};
+        *reinterpret_cast<V*>(p) = t;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (m[e]) p[e] = o[e];
+    }
+}
+typedef short i16x4_t __attribute__((ext_vector_type(4)));
+
+// CONF = false keeps (best, label) only; first: the state is not read; last: sum leaves as the log-sum-exp best + log(s)
+template <bool CONF>
+__global__ __launch_bounds__(256) void eval_merge_labels_kernel(const float* __restrict__ scores, int rows, int row0, long long npix,
+                                                                int16_t* __restrict__ label, float* __restrict__ score,
+                                                                int16_t* __restrict__ label2, float* __restrict__ score2,
+                                                                float* __restrict__ sum, int first, int last, int shift, long long nq) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    const long long xb = 4 * q - shift;                   // the run's first pixel; -3 .. -1 for the partial first run
+    bool m[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m[e] = xb + e >= 0 && xb + e < npix;
+    const bool full = all4(m);
+    const float ninf = -__builtin_huge_valf();
+    float best[4] = {ninf, ninf, ninf, ninf}, sec[4] = {ninf, ninf, ninf, ninf}, s[4] = {0.f, 0.f, 0.f, 0.f};
+    int16_t lab[4] = {-1, -1, -1, -1}, lab2[4] = {-1, -1, -1, -1};
+    if (!first) {
+        load_run<f32x4_t>(score + xb, full, m, best);
+        load_run<i16x4_t>(label + xb, full, m, lab);
+        if (CONF) {
+            if (score2) load_run<f32x4_t>(score2 + xb, full, m, sec);
+            if (label2) load_run<i16x4_t>(label2 + xb, full, m, lab2);
+            if (sum) load_run<f32x4_t>(sum + xb, full, m, s);
+        }
+    }
+    const float* p = scores + xb;
+#pragma unroll 4
+    for (int j = 0; j < rows; ++j, p += npix) {
+        float v[4] = {ninf, ninf, ninf, ninf};            // an element outside the map never wins and is never stored
+        load_run<f32x4_t>(p, full, m, v);
+        const int16_t k = (int16_t)(row0 + j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (CONF) {
+                const float ex = __expf(-fabsf(v[e] - best[e]));
+                s[e] = v[e] > best[e] ? s[e] * ex + 1.f : s[e] + ex;
+            }
+            if (v[e] > best[e]) {
+                if (CONF) { sec[e] = best[e]; lab2[e] = lab[e]; }
+                best[e] = v[e]; lab[e] = k;
+            } else if (CONF && v[e] > sec[e]) {
+                sec[e] = v[e]; lab2[e] = k;
+            }
+        }
+    }
+    store_run_any<f32x4_t>(score + xb, full, m, best);
+    store_run_any<i16x4_t>(label + xb, full, m, lab);
+    if (CONF) {
+        if (score2) store_run_any<f32x4_t>(score2 + xb, full, m, sec);
+        if (label2) store_run_any<i16x4_t>(label2 + xb, full, m, lab2);
+        if (sum) {
+            if (last) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[e] = best[e] + logf(s[e]);
+            }
+            store_run_any<f32x4_t>(sum + xb, full, m, s);
+        }
+    }
+}
+
 inline int grid_for(size_t total) {
     size_t g = (total + 255) / 256;
     if (g > 256 * 16) g = 256 * 16;
@@ -420,6 +512,23 @@ int launch_eval_finalize(const float* sum, float* map, int K, int height, int wi
     const int vec = ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(map)) & 15) == 0;
     hipLaunchKernelGGL(eval_finalize_kernel, dim3(grid_for((total + 3) / 4)), dim3(256), 0, st, sum, map, total, height, width, crop, stride,
                        h_grids, w_grids, vec);
+    LSEG_HIP_TRY(hipGetLastError());
+    return 0;
+}
+// one launch per label panel; the frame of the runs is the score plane's, first = 1 writes the state without reading it
+int launch_eval_merge_labels(const float* scores, int rows, int row0, int H, int W, int16_t* label, float* score, int16_t* label2, float* score2,
+                             float* sum, int first, int last, hipStream_t st) {
+    const long long npix = (long long)H * W;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(score) >> 2) & 3);
+    const long long nq = (npix + shift + 3) >> 2;
+    const long long blocks = (nq + 255) / 256;
+    if (blocks > 0x7fffffffLL) return set_error(LSEG_ERR_UNSUPPORTED, "eval_merge_labels: too many pixels");
+    if (label2 || score2 || sum)
+        hipLaunchKernelGGL(eval_merge_labels_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, scores, rows, row0, npix, label, score, label2,
+                           score2, sum, first, last, shift, nq);
+    else
+        hipLaunchKernelGGL(eval_merge_labels_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, scores, rows, row0, npix, label, score, label2,
+                           score2, sum, first, last, shift, nq);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }

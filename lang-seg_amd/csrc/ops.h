@@ -227,6 +227,10 @@ int launch_eval_accumulate_window(const float* outs, float* sum, int K, int heig
 int launch_eval_finalize(const float* sum, float* map, int K, int height, int width, int crop, int stride, int h_grids, int w_grids,
                          hipStream_t st);
 int launch_eval_resize(const float* src, float* dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, hipStream_t st);
+// label panels of the multi-scale evaluator: scores [rows, H, W] (labels row0 ..) folded into the per-pixel (best, label, runner-up, label2,
+// exp-sum) state; label2 / score2 / sum optional
+int launch_eval_merge_labels(const float* scores, int rows, int row0, int H, int W, int16_t* label, float* score, int16_t* label2, float* score2,
+                             float* sum, int first, int last, hipStream_t st);
 
 // ---- resnet.hip: the torchvision ResNet-101 image tower (lseg_config.flags bit 5) ----
 // stem: conv1 7x7/2 pad 3 (3 -> 64) + folded BN + ReLU, fp32 NCHW [B,3,H,W] -> padded NHWC 16-bit [B, Ho+2, Wo+2, 64]; w: fp32 [147][64]

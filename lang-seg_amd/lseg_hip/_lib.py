@@ -63,6 +63,9 @@ SIGNATURES = {
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels_conf": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_forward_lowres": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "lseg_features_bytes": (_i, [_vp, _i, C.POINTER(_sz), C.POINTER(_sz)]),
+    "lseg_forward_features": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "lseg_score_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "lseg_forward_stats": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_episode_stats": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_get_intermediate": (_i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
@@ -134,6 +137,7 @@ SIGNATURES = {
     "lseg_op_eval_accumulate_window_lowres": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_finalize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_eval_merge_labels": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "lseg_op_l2norm_scale_backward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "lseg_op_corr_group_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_corr_group_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

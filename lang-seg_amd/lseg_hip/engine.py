@@ -178,6 +178,11 @@ class HipEngine:
         _lib.check(self.lib.lseg_set_text_groups(self._h, (C.c_int32 * len(sizes))(*sizes), len(sizes)))
         self._groups = sizes
 
+    def clear_grouping(self):
+        """One label set shared by the batch again: drops a per-image grouping of either kind (lseg_set_text_grouping(0) clears both)."""
+        _lib.check(self.lib.lseg_set_text_grouping(self._h, 0))
+        self._group, self._groups = 0, None
+
     def set_text_features(self, feat: torch.Tensor, group_sizes: Optional[Sequence[int]] = None):
         """fp16 [K, out_c] text features computed elsewhere (un-normalised `encode_text` output or already normalised): replaces the
         tokens; the engine's text tower is not run until set_tokens is called again (lseg_set_text_features).  group_sizes: as in
@@ -265,6 +270,37 @@ class HipEngine:
         _lib.check(self.lib.lseg_forward_lowres(self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(low.data_ptr()),
                                                 C.c_void_p(_stream_ptr(self.device))))
         self._raise_callback_error()
+        return low
+
+    def forward_features(self, x: torch.Tensor):
+        """(feat fp16 [B, H/4+2, W/4+2, out_c], scale fp32 [B, H/2, W/2]): what the correlation reads after the image tower
+        (lseg_forward_features) -- held by the caller, any slice of a label set is scored from them later (score_features).  No text is
+        read.  Per-image label sets, train mode and the schedules without the commuted correlation raise LSEG_ERR_UNSUPPORTED."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        fb, sb = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.lseg_features_bytes(self._h, B, C.byref(fb), C.byref(sb)))
+        assert fb.value == B * (H // 4 + 2) * (W // 4 + 2) * self.cfg.out_c * 2 and sb.value == B * (H // 2) * (W // 2) * 4
+        feat = torch.empty((B, H // 4 + 2, W // 4 + 2, self.cfg.out_c), dtype=torch.float16, device=self.device)
+        scale = torch.empty((B, H // 2, W // 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lseg_forward_features(self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(feat.data_ptr()), C.c_void_p(scale.data_ptr()),
+                                                  C.c_void_p(_stream_ptr(self.device))))
+        self._raise_callback_error()
+        return feat, scale
+
+    def score_features(self, feat: torch.Tensor, scale: torch.Tensor, row0: int, rows: int) -> torch.Tensor:
+        """fp32 [B, rows, H/2, W/2]: the low-resolution logits of text rows [row0, row0 + rows) of the current label set for held features
+        (lseg_score_features) -- the planes forward_lowres gives for them (bit for bit where it takes the generic correlation, K > 157)."""
+        B = feat.shape[0]
+        H, W = self.img_h, self.img_w
+        if (feat.dtype != torch.float16 or scale.dtype != torch.float32 or feat.device != self.device or scale.device != self.device
+                or tuple(feat.shape) != (B, H // 4 + 2, W // 4 + 2, self.cfg.out_c) or tuple(scale.shape) != (B, H // 2, W // 2)
+                or not feat.is_contiguous() or not scale.is_contiguous()):
+            raise ValueError(f"held features of another engine plan: feat {tuple(feat.shape)} {feat.dtype}, scale {tuple(scale.shape)} {scale.dtype} "
+                             f"for an engine of {H}x{W} on {self.device}")
+        low = torch.empty((B, max(int(rows), 0), H // 2, W // 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lseg_score_features(self._h, C.c_void_p(feat.data_ptr()), C.c_void_p(scale.data_ptr()), B, int(row0), int(rows),
+                                                C.c_void_p(low.data_ptr()), C.c_void_p(_stream_ptr(self.device))))
         return low
 
     def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):

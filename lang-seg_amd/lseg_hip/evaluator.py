@@ -100,6 +100,14 @@ def plan_schedule(geo: Sequence[ScaleGeometry], flip: bool, max_stack: int, max_
     return steps, largest
 
 
+def plan_panels(K: int, panel: int) -> List[Tuple[int, int]]:
+    """The label panels [(row0, rows), ...] of a label set of K rows, at most `panel` rows each: ascending, disjoint, covering."""
+    K, panel = int(K), int(panel)
+    if K < 1 or panel < 1:
+        raise ValueError(f"plan_panels: K={K} and panel={panel} must both be at least 1")
+    return [(row0, min(panel, K - row0)) for row0 in range(0, K, panel)]
+
+
 def _pad_image(img, mean, std, crop_size):          # encoding_models.py:144-155
     b, c, h, w = img.shape
     padh = crop_size - h if h < crop_size else 0
@@ -134,6 +142,12 @@ class ModuleSurface(torch.nn.Module):
 
     def evaluate_random_lowres(self, x, labelset):
         return self.net.forward_lowres(x, labelset)
+
+    def hold_features(self, x):
+        return self.net.hold_features(x)
+
+    def score_held(self, held, row0, rows, labelset=""):
+        return self.net.score_held(held, row0, rows, labelset)
 
 
 class BatchedMultiEval(torch.nn.Module):
@@ -294,6 +308,129 @@ class BatchedMultiEval(torch.nn.Module):
             finally:
                 net.cache_text = was
         return self._forward_torch(image, label_set)
+
+    def parallel_forward_labels(self, inputs: Sequence[torch.Tensor], label_set=None, confidence=False, panel=64) -> List[tuple]:
+        """list of [3,h,w] images in, list of forward_labels results out."""
+        return [self.forward_labels(img.unsqueeze(0).cuda(), label_set, confidence, panel) for img in inputs]
+
+    @torch.no_grad()
+    def forward_labels(self, image: torch.Tensor, label_set=None, confidence=False, panel=64):
+        """torch.max(self.forward(image, label_set), 1) for a label set of ANY size without the [K,h,w] score tensor: (label int16 [h,w],
+        score fp32 [h,w]); confidence=True adds (label2 int16, score2 fp32, lse fp32) -- entries 0 / 1 of the stable descending sort of the
+        scores over the labels and their log-sum-exp.  The multi-scale score is linear in the per-crop logits and those are linear in the
+        text rows, so the image tower runs ONCE per crop (module.hold_features keeps what the correlation reads: 15.2 MB per 480^2 crop)
+        and the label set is walked in panels of `panel` rows: per panel the held crops are scored (module.score_held), fused by the
+        lowres accumulate / finalize / resize kernels with K = rows, and folded into the running per-pixel state by
+        lseg_op_eval_merge_labels.  Peak memory follows the panel, not K.  Every evaluator kernel treats planes independently, so a
+        plane's fused scores do not depend on the panel that carried it: label / score / label2 / score2 are the same bits for every
+        panel size (DESIGN par. 3.8).  Device images only, the lowres arithmetic whatever self.lowres says; the module must offer
+        hold_features and score_held: there is no fallback."""
+        missing = [m for m in ("hold_features", "score_held") if not callable(getattr(self.module, m, None))]
+        if missing:
+            raise AttributeError(f"BatchedMultiEval.forward_labels needs module.{' / module.'.join(missing)} "
+                                 f"({type(self.module).__name__} has no such method); there is no fallback")
+        if not image.is_cuda:
+            raise ValueError("BatchedMultiEval.forward_labels runs on device images only")
+        if self.crop_size % 2 or self.crop_size < 4:
+            raise ValueError(f"BatchedMultiEval.forward_labels: crop_size={self.crop_size} must be even and >= 4")
+        net = getattr(self.module, "net", None)
+        if net is None or not hasattr(net, "cache_text"):
+            return self._forward_labels_device(image, label_set, bool(confidence), int(panel))
+        was = net.cache_text
+        net.cache_text = True                # the label set is encoded once for the whole call, as in forward
+        try:
+            return self._forward_labels_device(image, label_set, bool(confidence), int(panel))
+        finally:
+            net.cache_text = was
+
+    def _forward_labels_device(self, image, label_set, confidence, panel):
+        from . import _lib
+        lib = _lib.load()
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        st = C.c_void_p(torch.cuda.current_stream(image.device).cuda_stream)
+        batch, ch, h, w = image.shape
+        assert batch == 1 and image.dtype == torch.float32
+        nclass = self.nclass if label_set is None else len(label_set)
+        panels = plan_panels(nclass, panel)
+        crop = self.crop_size
+        if self.module._up_kwargs != {"mode": "bilinear", "align_corners": True}:
+            raise ValueError("the device evaluator implements the reference's bilinear / align_corners=True resize")
+        pad = (C.c_float * 3)(*[float(v) for v in (-np.array(self.module.mean) / np.array(self.module.std))])
+        image = image.contiguous()
+        flip, twins = int(self.flip), 2 if self.flip else 1
+        side = crop // 2
+        geo = [scale_geometry(h, w, scale, self.base_size, crop) for scale in self.scales]
+        max_stack = getattr(self, "max_stack", None)
+        if max_stack is None:
+            max_stack = self._max_stack if self._max_stack is not None else 192
+        steps, largest = plan_schedule(geo, self.flip, int(max_stack), self.max_batch)
+        net = getattr(self.module, "net", None)
+        if callable(getattr(net, "reserve_batch", None)):
+            net.reserve_batch(min(self.max_batch, largest), crop, crop, None if label_set is None else nclass, image.device)
+        labelset = "" if label_set is None else label_set
+
+        def hold(xs):                        # the towers, once: max_batch crops per forward, what the correlation reads is kept
+            return [self.module.hold_features(xs[i:i + self.max_batch].contiguous()) for i in range(0, xs.shape[0], self.max_batch)]
+
+        held = []                            # per step: the held chunks of its stack, or one such list per window
+        for step in steps:
+            stacks = []
+            for i in step.scales:
+                g = geo[i]
+                cur = image.new_empty((ch, g.height, g.width))
+                _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, g.height, g.width, 0, st))
+                crops = image.new_empty((twins * g.n_box, ch, crop, crop))
+                _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip, pad, st))
+                stacks.append(crops)
+            if step.windows is None:
+                held.append(hold(torch.cat(stacks, dim=0) if len(stacks) > 1 else stacks[0]))
+            else:
+                crops, n = stacks[0], geo[step.scales[0]].n_box
+                held.append([hold(torch.cat([crops[first:first + nb], crops[n + first:n + first + nb]], dim=0) if self.flip
+                                  else crops[first:first + nb]) for first, nb in step.windows])
+            del stacks
+
+        def logits(chunks, row0, rows):      # the panel's planes of a held forward group, [n, rows, crop/2, crop/2]
+            outs = [self.module.score_held(hc, row0, rows, labelset) for hc in chunks]
+            outs = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+            assert outs.shape[1:] == (rows, side, side) and outs.dtype == torch.float32 and outs.is_contiguous()
+            return outs
+
+        label = torch.empty((h, w), dtype=torch.int16, device=image.device)
+        score = image.new_empty((h, w))
+        label2 = torch.empty_like(label) if confidence else None
+        score2, lse = (torch.empty_like(score), torch.empty_like(score)) if confidence else (None, None)
+        for pi, (row0, rows) in enumerate(panels):
+            scores = image.new_zeros((rows, h, w))
+            for step, hs in zip(steps, held):
+                if step.windows is None:
+                    outs = logits(hs, row0, rows)
+                    o0 = 0
+                    for i in step.scales:
+                        g = geo[i]
+                        nc = twins * g.n_box
+                        smap = image.new_empty((rows, g.height, g.width))
+                        _lib.check(lib.lseg_op_eval_accumulate_lowres(P(outs[o0:o0 + nc]), P(smap), rows, g.height, g.width, g.ph, g.pw, crop, g.stride,
+                                                                      g.h_grids, g.w_grids, flip, st))
+                        _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), rows, g.height, g.width, h, w, 1, st))
+                        o0 += nc
+                    del outs, smap
+                else:
+                    g = geo[step.scales[0]]
+                    smap = image.new_zeros((rows, g.height, g.width))
+                    for (first, nb), hw in zip(step.windows, hs):
+                        outs = logits(hw, row0, rows)
+                        _lib.check(lib.lseg_op_eval_accumulate_window_lowres(P(outs), P(smap), rows, g.height, g.width, g.ph, g.pw, crop, g.stride,
+                                                                             g.h_grids, g.w_grids, flip, first, nb, st))
+                        del outs
+                    _lib.check(lib.lseg_op_eval_finalize(P(smap), P(smap), rows, g.height, g.width, g.ph, g.pw, crop, g.stride, g.h_grids,
+                                                         g.w_grids, st))
+                    _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), rows, g.height, g.width, h, w, 1, st))
+                    del smap
+            _lib.check(lib.lseg_op_eval_merge_labels(P(scores), rows, row0, h, w, P(label), P(score), P(label2), P(score2), P(lse),
+                                                     int(pi == 0), int(pi == len(panels) - 1), st))
+            del scores
+        return (label, score, label2, score2, lse) if confidence else (label, score)
 
     @torch.no_grad()
     def _forward_torch(self, image: torch.Tensor, label_set=None) -> torch.Tensor:

@@ -117,6 +117,18 @@ class _EngineLossFn(torch.autograd.Function):
         return (None, None, None, None, None, None) + grads
 
 
+class HeldFeatures:
+    """What LSeg.hold_features keeps of a batch after the image tower: feat fp16 [B, H/4+2, W/4+2, out_c] and scale fp32 [B, H/2, W/2]
+    (what the correlation reads), the batch size, the image size (H, W) and the stamp of the weights that produced them."""
+    __slots__ = ("feat", "scale", "B", "size", "stamp")
+
+    def __init__(self, feat, scale, B, size, stamp):
+        self.feat, self.scale, self.B, self.size, self.stamp = feat, scale, int(B), (int(size[0]), int(size[1])), stamp
+
+    def nbytes(self):
+        return self.feat.numel() * 2 + self.scale.numel() * 4
+
+
 def _new_shared(image_dtype):
     return _SharedState(image_dtype=image_dtype, lock=threading.RLock())
 
@@ -514,6 +526,48 @@ class LSeg(BaseModel):
         if self._range_guard(eng, x.device):
             return self.forward_lowres(x, labelset)                     # fell back to bf16: run again on a bf16 engine
         return out
+
+    def hold_features(self, x):
+        """Run the image tower on x [B,3,H,W] and keep what the correlation reads (lseg_forward_features): a HeldFeatures whose label
+        planes score_held forms later, for any slice of any label set, without another tower pass -- BatchedMultiEval.forward_labels
+        walks a label set of any size in panels over them.  Inference only; no label set is read."""
+        if not x.is_cuda:
+            raise RuntimeError("LSegNet.hold_features needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("LSegNet.hold_features is an inference path: call it under net.eval() or torch.no_grad()")
+        B, _, H, W = x.shape
+        eng = self._engine(B, H, W, 1, x.device)
+        if eng.training:
+            eng.set_train(False)
+        if eng._group or eng._groups is not None:                      # a per-image grouping left by an earlier call: held features have none
+            eng.clear_grouping()
+            eng._tok = None
+        self._last_engine = eng
+        feat, scale = eng.forward_features(x.float())
+        if self._range_guard(eng, x.device):
+            return self.hold_features(x)                                # fell back to bf16: run again on a bf16 engine
+        return HeldFeatures(feat, scale, B, (H, W), eng._stamp)
+
+    def score_held(self, held, row0, rows, labelset=""):
+        """fp32 [B, rows, H/2, W/2]: the planes forward_lowres(x, labelset) would give for labels [row0, row0 + rows) of the label set,
+        from the features hold_features(x) kept (lseg_score_features).  Raises when the weights changed since hold_features."""
+        if labelset == "":
+            text = self.text
+        else:                                                           # one call per panel and forward group: tokenise a label set once
+            key = labelset if isinstance(labelset, str) else tuple(labelset)
+            if getattr(self, "_held_text", (None, None))[0] != key:
+                self._held_text = (key, tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab))
+            text = self._held_text[1]
+        H, W = held.size
+        eng = self._engine(held.B, H, W, text.shape[0], held.feat.device)
+        if held.stamp != eng._stamp:
+            raise RuntimeError("LSegNet.score_held: the weights changed since hold_features ran (load_state_dict, an optimizer step, a "
+                               "dtype or device move): the held features belong to the old weights -- hold them again")
+        if eng.training:
+            eng.set_train(False)
+        self._set_tokens(eng, text, labelset)
+        self._last_engine = eng
+        return eng.score_features(held.feat, held.scale, int(row0), int(rows))
 
     def reserve_batch(self, B, H, W, n_labels=None, device=None):
         """Make the inference engine of (H, W) on `device` large enough for batches of B images and n_labels labels (None: this network's
