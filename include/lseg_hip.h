@@ -323,6 +323,39 @@ int lseg_op_gemm(const void* d_A, const void* d_W, const float* d_bias, const fl
  * max_grid > 0 caps the persistent grid (tools/epilogue_table.py).  d_bias fp32 [N] is required. */
 int lseg_op_gemm_vit(const void* d_A, const void* d_W, const float* d_bias, void* d_Cq, void* d_Ck, void* d_Cv, int M, int N, int K,
                      int ab_dtype, int kind, int ntok, int npad, int max_grid, void* stream);
+/* One GEMM of the family the engine launches, described the way its schedules describe it (csrc/engine.h: lin_args, add_residual, qkv_args,
+ * pixshuf_args, to_periodic_rows), with the launcher's tools-only knobs exposed: the operator tests reach every epilogue, tile and schedule
+ * at small shapes through it (tests/test_gpu_gemm_family.py).  A [M, K] and W [N, K] are row-major 16-bit operands of ab_dtype, bias fp32 [N]
+ * ([ch] for form 2) or NULL (form 0 only).
+ *   form 0  linear: C [M, N] = out_dtype(act(A W^T + bias) [+ residual [M, N] of res_dtype]); act 0 none, 1 GELU, 3 ReLU.  nsplit > 1: split-K,
+ *           slab s = C + s * c_split_stride (fp32 elements) holds the partial product over K-steps [s * split_steps, (s + 1) * split_steps) of
+ *           64; needs bias == residual == NULL and ranges that tile K / 64 exactly.
+ *   form 1  qkv: N = 3 * heads * 64, K = heads * 64, M = B * ntok; C = q and Ck = k as [B * heads, npad, 64], Cv = v^T [B * heads, 64, npad],
+ *           pad tokens untouched; qscale != 0 multiplies q before its single rounding.
+ *   form 2  ConvTranspose2d(kernel = stride = s) as a GEMM: rows m = (b, y, x) on the (ho, wo) grid, columns n = (i * s + j) * ch + co; C is the
+ *           padded NHWC map [B, ho * s + 2, wo * s + 2, ch], whose one-pixel border is untouched; bias fp32 [ch].
+ *   form 3  periodic rows (the patch embedding): rows m = (b, r), r < p_div, land in row b * p_mul + r + p_off of C [*, N] and add row
+ *           r + p_off of residual [*, ldr] (res_dtype).
+ * tag 0 | 1: the two symbols of the GELU epilogue.  tile 0: the launcher's cost model; 1 = 64x64, 2 = 128x128, 6 = 256x256 (taken when the
+ * epilogue has that instantiation and N % 256 == 0, else 128x128).  max_grid: 0 or a multiple of 8, caps the persistent grid.
+ * LSEG_ERR_INVALID / LSEG_ERR_UNSUPPORTED before anything is launched: a NULL required pointer, a shape that does not fit the form, whatever
+ * launch_gemm refuses (K % 64, split-K ranges that do not tile K, qscale without the specialised qkv epilogue, ...). */
+typedef struct lseg_gemm_case {
+    int form;
+    const void* A; const void* W; const float* bias; const void* residual;
+    void* C; void* Ck; void* Cv;
+    int M, N, K, ab_dtype, out_dtype, res_dtype, act;
+    int tag, tile, max_grid;
+    int nsplit, split_steps; size_t c_split_stride;
+    int ntok, npad, heads; float qscale;          /* form 1 */
+    int ho, wo, s, ch;                            /* form 2 */
+    int p_div, p_mul, p_off, ldr;                 /* form 3 */
+} lseg_gemm_case;
+int lseg_op_gemm_ex(const lseg_gemm_case* c, void* stream);
+/* What that launch decides on a device of `cus` compute units, host only (no device needed, the pointers are only looked at for their
+ * alignment): out4 = {epilogue id (0 generic, 1 LIN16, 2 LIN16_GELU, 3 RES32, 4 QKV16, 6 LIN16_F16, 7 PIX16, 8 PART32, 11 LIN32),
+ * tile (1 | 2 | 6), workgroups, most work items ((tile, K-range) pairs) one workgroup walks}.  Refuses what lseg_op_gemm_ex refuses. */
+int lseg_op_gemm_ex_plan(const lseg_gemm_case* c, int cus, int* out4);
 /* The residual form alone -- d_C (fp32 [rows_alloc, N], rows_alloc >= M) += A W^T + bias, in place: attn.proj / mlp.fc2 of a timm Block
  * (lseg_vit.py:196-197) -- with the caller stating how many rows of d_A and d_C are ALLOCATED.  When they reach the next multiple of 256
  * the launch takes the hand-scheduled 256 x 128 kernel (csrc/gemm_asm.hip: whole tiles, no masks; rows >= M of d_C are overwritten with

@@ -287,6 +287,75 @@ int lseg_op_gemm_res32(const void* A, const void* W, const float* bias, float* C
     return launch_gemm(g, ab, (hipStream_t)stream);
 }
 
+// lseg_gemm_case -> the GemmArgs the schedules would build for it (engine.h builders); every refusal of a malformed case
+static int gemm_case_args(const lseg_gemm_case* c, GemmArgs& g, int* ab) {
+    if (!c) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: NULL case");
+    int r, od, rd = DT_F32;
+    if ((r = op_dt(c->ab_dtype, ab)) || (r = op_dt(c->out_dtype, &od))) return r;
+    if (*ab == DT_F32) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: operands must be bf16 or fp16");
+    if (c->residual && (r = op_dt(c->res_dtype, &rd))) return r;
+    if (!c->A || !c->W || !c->C) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: NULL operand or output");
+    if (c->M < 1 || c->N < 1 || c->K < 1) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: empty problem %dx%dx%d", c->M, c->N, c->K);
+    if (c->form < 0 || c->form > 3) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: form %d (0..3)", c->form);
+    if (c->tag < 0 || c->tag > 1) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: tag %d (0 | 1)", c->tag);
+    if (c->tile != 0 && c->tile != 1 && c->tile != 2 && c->tile != 6) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: tile %d (0, 1, 2, 6)", c->tile);
+    if (c->max_grid < 0 || (c->max_grid % 8)) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: max_grid %d (0 or a multiple of 8)", c->max_grid);
+    if (c->act != ACT_NONE && c->act != ACT_GELU && c->act != ACT_RELU) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: act %d (0, 1, 3)", c->act);
+    if (c->form != 0 && (c->act != ACT_NONE || c->nsplit > 1 || !c->bias))
+        return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: forms 1..3 take a bias, no activation and no split-K");
+    if (c->form != 0 && c->form != 3 && c->residual) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: forms 1 and 2 take no residual");
+    if (c->nsplit < 0 || c->split_steps < 0) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: negative split-K range");
+    Lin w;
+    w.w = (uint16_t*)c->W; w.b = (float*)c->bias; w.n = c->N; w.k = c->K;
+    switch (c->form) {
+        case 0:
+            g = lin_args(c->A, w, c->M, c->C, od);
+            g.act = c->act;
+            if (c->residual) add_residual(g, c->residual, rd);
+            g.nsplit = c->nsplit; g.split_steps = c->split_steps; g.c_split_stride = c->c_split_stride;
+            break;
+        case 1:
+            if (c->heads < 1 || c->K != c->heads * 64 || c->N != 3 * c->K || c->ntok < 1 || c->npad < c->ntok || c->M % c->ntok || !c->Ck || !c->Cv)
+                return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: qkv needs K = heads * 64, N = 3 K, M = B * ntok, npad >= ntok, Ck and Cv");
+            g = qkv_args(c->A, w, c->M, c->C, c->Ck, c->Cv, c->ntok, c->npad, c->heads, od);
+            g.qkv_qscale = c->qscale;
+            break;
+        case 2:
+            if (c->s < 1 || c->ch < 1 || c->ho < 1 || c->wo < 1 || c->N != c->s * c->s * c->ch || c->M % (c->ho * c->wo))
+                return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: pixel shuffle needs N = s * s * ch and M = B * ho * wo");
+            g = pixshuf_args(c->A, w, c->M, c->C, c->ch, c->s, c->ho, c->wo, od);
+            break;
+        default:
+            if (!c->residual || c->p_div < 1 || c->p_off < 0 || c->p_mul < c->p_div + c->p_off || c->M % c->p_div || c->ldr < c->N)
+                return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex: periodic rows need a table, M = B * p_div, p_mul >= p_div + p_off >= p_div, ldr >= N");
+            g = lin_args(c->A, w, c->M, c->C, od);
+            to_periodic_rows(g, c->residual, rd, c->ldr, c->p_div, c->p_mul, c->p_off);
+            break;
+    }
+    g.tag = c->tag; g.tile_hint = c->tile; g.max_grid = c->max_grid;
+    return 0;
+}
+
+int lseg_op_gemm_ex(const lseg_gemm_case* c, void* stream) {
+    GemmArgs g;
+    int ab, r = gemm_case_args(c, g, &ab);
+    if (r) return r;
+    if ((r = gemm_check(g, ab))) return r;                 // every refusal of the launcher, before a device is asked for
+    if ((r = require_device())) return r;
+    return launch_gemm(g, ab, (hipStream_t)stream);
+}
+
+int lseg_op_gemm_ex_plan(const lseg_gemm_case* c, int cus, int* out4) {
+    if (!out4) return set_error(LSEG_ERR_INVALID, "lseg_op_gemm_ex_plan: NULL pointer");
+    GemmArgs g;
+    int ab, r = gemm_case_args(c, g, &ab);
+    if (r) return r;
+    GemmPlan p;
+    if ((r = gemm_plan(g, ab, cus, p))) return r;
+    out4[0] = p.epi; out4[1] = p.tile; out4[2] = p.grid; out4[3] = p.items;
+    return 0;
+}
+
 int lseg_op_colsum(const void* in, int dtype, float* out, int R, int C, int ld, int accumulate, float* det_ws, size_t det_cap, void* stream) {
     int r = require_device(); if (r) return r;
     int dt;

@@ -51,6 +51,12 @@ inline GemmArgs pixshuf_args(const void* A, const Lin& w, int M, void* C, int ch
     g.map_mode = MAP_PIXSHUF; g.ho = ho; g.wo = wo; g.ps_s = s; g.ps_C = ch;
     return g;
 }
+// rows m = (image, r) with r < p_div land in row image * p_mul + r + p_off of C, plus row r + p_off of a [*, ldr] table shared by the images:
+// the patch embedding writes token rows 1.. of every image and adds the position embedding (p_div = patches, p_mul = tokens, p_off = 1)
+inline void to_periodic_rows(GemmArgs& g, const void* table, int table_dtype, int ldr, int p_div, int p_mul, int p_off) {
+    g.res_mode = RES_PERIODIC; g.res = table; g.res_dtype = table_dtype; g.ldr = ldr;
+    g.map_mode = MAP_PERIODIC; g.p_div = p_div; g.p_mul = p_mul; g.p_off = p_off;
+}
 inline float logit_scale() { return expf(logf(1.0f / 0.07f)); }            // lseg_net.py:141
 
 struct VitBlock { float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; Lin qkv, proj, fc1, fc2; };

@@ -849,8 +849,7 @@ int Engine::patch_embed(const float* x_in, float* x, int B, hipStream_t st) {
     if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
     else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
     GemmArgs g = lin_args(patchA_, patch_, B * np_, x, DT_F32);
-    g.res_mode = RES_PERIODIC; g.res = pos_; g.res_dtype = DT_F32; g.ldr = c.dim;
-    g.map_mode = MAP_PERIODIC; g.p_div = np_; g.p_mul = ntok_; g.p_off = 1;
+    to_periodic_rows(g, pos_, DT_F32, c.dim, np_, ntok_, 1);
     TRY(igemm(g, st));
     return launch_cls_rows(cls_, pos_, x, B, ntok_, c.dim, st);
 }

@@ -86,7 +86,8 @@ struct GemmArgs {
     int rows_alloc;             // rows of A and of C / res that are ALLOCATED (>= M; 0 = exactly M).  A caller whose buffers reach the next
                                 // multiple of 256 rows lets the residual GEMMs run on the hand-scheduled kernel (gemm_asm.hip), which computes
                                 // whole 256-row tiles and never masks: rows >= M are garbage in, garbage out, nobody reads them
-    int tile_hint;              // 0: the launcher's cost model picks the tile; 2 = 128x128, 6 = 256x256 (callers that plan tile and split-K together)
+    int tile_hint;              // 0: the launcher's cost model picks the tile; 1 = 64x64, 2 = 128x128, 6 = 256x256 (callers that plan tile and
+                                // split-K together; the operator tests, which need each tile at small shapes)
     // ---- ResNet bottlenecks (resnet.hip, Engine::rn_conv).  Both default to the behaviour above when zero.
     int ksize;                  // implicit conv kernel: 1 = 1x1 conv, pad 0 (K = cin; reads the centre of the padded input); 0 / 3 = 3x3, pad 1
     int relu_after_res;         // with act = ACT_RELU and a residual: C = T(relu(acc + bias + res [+ res2])) -- the bottleneck's
@@ -97,6 +98,14 @@ void gemm_args_init(GemmArgs& g);
 int device_cu_count(int dev);
 // ab_dtype: DT_BF16 | DT_F16.  Returns 0 or a negative lseg_status.
 int launch_gemm(const GemmArgs& g, int ab_dtype, hipStream_t stream);
+// What launch_gemm decides for g on a device of `cus` compute units, without launching (and without a device): epi = the kernel's
+// epilogue id (gemm.hip: enum Epi, 0 = generic), tile = 1 (64x64) | 2 (128x128) | 6 (256x256) | 5 (160x128 label planes) | 4 (64x512 fused
+// head), grid = workgroups of the persistent launch, items = the most work items ((tile, K-range) pairs) any workgroup walks.
+// Refuses what launch_gemm refuses, with the same status.
+struct GemmPlan { int epi, tile, grid, items, dev; };
+int gemm_plan(const GemmArgs& g, int ab_dtype, int cus, GemmPlan& p);
+// Every refusal of launch_gemm for g, with its status, and nothing else: no device is asked for, nothing is launched.
+int gemm_check(const GemmArgs& g, int ab_dtype);
 // true when launch_gemm would run this problem on the specialised padded-NHWC epilogue (the one that honours C_relu)
 bool gemm_epilogue_is_pad16(const GemmArgs& g, int ab_dtype);
 // true when launch_gemm would honour g.qkv_qscale (it refuses a non-zero scale otherwise)

@@ -1386,68 +1386,56 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::MINW) void lseg_gemm_kernel(cons
     wait_vmcnt<0>();     // drain the never-consumed tail loads before the LDS is released
 }
 
-template <typename T, typename CFG, bool CONV, bool RELU_IN, int EPI, int TAG>
-int launch_one(const GemmArgs& g, hipStream_t stream) {
-    const int tiles = ((g.M + CFG::BM - 1) / CFG::BM) * ((g.N + CFG::BN - 1) / CFG::BN) * (g.nsplit > 1 ? g.nsplit : 1);
-    const size_t lds = CFG::LDS + (CFG::BN == 512 ? 1024 : 0);
-    // persistent grid: a multiple of 8 (one slice per XCD), at most `slots` resident workgroups
+// Tile ids of the plan: 1 = 64x64, 2 = 128x128, 6 = 256x256 (the values of tile_hint / LSEG_GEMM_TILE), 5 = 160x128 (label planes),
+// 4 = 64x512 (fused head).  per_cu: resident workgroups per compute unit, by LDS and by waves.
+template <typename CFG>
+constexpr int cfg_per_cu() {
     constexpr int by_lds = 163840 / CFG::LDS, by_waves = 8 / (CFG::NW / 4);
-    constexpr int per_cu = by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : by_waves;
-    int dev = 0;
-    LSEG_HIP_TRY(hipGetDevice(&dev));
-    const int slots = device_cu_count(dev) * per_cu;
-    int grid = ((tiles + 7) / 8) * 8;
-    if (grid > slots) grid = slots;
-    if (g.max_grid >= 8 && grid > g.max_grid) grid = g.max_grid & ~7;      // tools: part of the chip (tools/epilogue_table.py)
+    return by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : by_waves;
+}
+struct TileGeom { int bm, bn, per_cu; };
+TileGeom tile_geom(int tile) {
+    switch (tile) {
+        case 1: return {CfgSmall::BM, CfgSmall::BN, cfg_per_cu<CfgSmall>()};
+        case 6: return {CfgHuge::BM, CfgHuge::BN, cfg_per_cu<CfgHuge>()};
+        case 5: return {CfgLab::BM, CfgLab::BN, cfg_per_cu<CfgLab>()};
+        case 4: return {CfgRow::BM, CfgRow::BN, cfg_per_cu<CfgRow>()};
+        default: return {CfgMid::BM, CfgMid::BN, cfg_per_cu<CfgMid>()};
+    }
+}
+
+template <typename T, typename CFG, bool CONV, bool RELU_IN, int EPI, int TAG>
+int launch_one(const GemmArgs& g, const GemmPlan& p, hipStream_t stream) {
+    const size_t lds = CFG::LDS + (CFG::BN == 512 ? 1024 : 0);
     auto kern = lseg_gemm_kernel<T, CFG, CONV, RELU_IN, EPI, TAG>;
     // the dynamic-LDS opt-in is a per-DEVICE function attribute: one bit per device (a process may drive several GPUs, one
     // engine and one host thread each: additional_utils/models.py:229-238), set with an atomic so concurrent threads are safe
     static std::atomic<unsigned long long> attr_done{0};
-    const unsigned long long bit = 1ull << (dev & 63);
+    const unsigned long long bit = 1ull << (p.dev & 63);
     if (!(attr_done.load(std::memory_order_acquire) & bit)) {
         LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done.fetch_or(bit, std::memory_order_release);
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(CFG::THREADS), lds, stream, g);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(CFG::THREADS), lds, stream, g);
     LSEG_HIP_TRY(hipGetLastError());
     return 0;
 }
 
 template <typename T, bool CONV, bool RELU_IN, int EPI, int TAG>
-int pick_tile(const GemmArgs& g, hipStream_t stream) {
-    const long t_mid = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * (g.nsplit > 1 ? g.nsplit : 1);
-    // tools/tests: 1 = 64x64, 2 = 128x128, 6 = 256x256.  Read ONCE per process (function-local static: thread-safe initialisation, no getenv
-    // on the launch path -- several hundred launches per forward, possibly from several host threads); the sweeping tool and the forced-tile
-    // tests start one interpreter per tile (tools/tile_sweep.py, tests/test_gpu_tile_configs.py)
-    static const int force = [] { const char* e = getenv("LSEG_GEMM_TILE"); return e ? atoi(e) : 0; }();
-    int pick = t_mid >= 192 ? 2 : 1;
-    if (EPI == EPI_GENERIC && !CONV && g.map_mode == MAP_LABELPLANES && g.M > 128 && g.M <= 160 && !force)
-        return launch_one<T, CfgLab, false, false, EPI_GENERIC, TAG>(g, stream);
-    if (EPI != EPI_GENERIC && pick == 2) {
-        // 256x256 tiles (one 8-wave workgroup per CU) move half the operand bytes per MFMA through the
-        // CU's L1/LDS-DMA path and run ~12% faster per flop than two 128x128 workgroups -- when the
-        // tile count quantises well over the 256 CUs.  Persistent schedules: ceil(tiles / slots) rounds.
-        const long t_huge = (long)((g.M + 255) / 256) * ((g.N + 255) / 256) * (g.nsplit > 1 ? g.nsplit : 1);
-        const double time_huge = (double)((t_huge + 255) / 256) * 4.0 / 1.12;
-        const double time_mid = (double)((t_mid + 511) / 512) * 2.0;
-        if (time_huge < time_mid) pick = 6;
+int pick_tile(const GemmArgs& g, const GemmPlan& p, hipStream_t stream) {
+    if constexpr (EPI == EPI_GENERIC && !CONV) {
+        if (p.tile == 5) return launch_one<T, CfgLab, false, false, EPI_GENERIC, TAG>(g, p, stream);
     }
-    if (g.tile_hint == 2 || g.tile_hint == 6) pick = g.tile_hint;
-    if (force) pick = force;
-    if (pick == 6 && (g.N % 256) != 0) pick = 2;      // the specialised epilogues write whole tile rows: N must be a multiple of BN
     if constexpr (EPI != EPI_GENERIC) {
-        if (pick == 6) return launch_one<T, CfgHuge, CONV, RELU_IN, EPI, TAG>(g, stream);
+        if (p.tile == 6) return launch_one<T, CfgHuge, CONV, RELU_IN, EPI, TAG>(g, p, stream);
     }
-    if (pick == 6) pick = 2;
-    if (pick == 2) return launch_one<T, CfgMid, CONV, RELU_IN, EPI, TAG>(g, stream);
-    return launch_one<T, CfgSmall, CONV, RELU_IN, EPI, TAG>(g, stream);
+    if (p.tile == 2) return launch_one<T, CfgMid, CONV, RELU_IN, EPI, TAG>(g, p, stream);
+    return launch_one<T, CfgSmall, CONV, RELU_IN, EPI, TAG>(g, p, stream);
 }
 
 // Which specialised epilogue (if any) reproduces this launch exactly.
-template <typename T>
-int select_epi(const GemmArgs& g) {
-    constexpr int dt = std::is_same<T, BF16>::value ? DT_BF16 : DT_F16;
+int select_epi(const GemmArgs& g, int dt) {
     static const bool off = getenv("LSEG_GEMM_GENERIC_EPI") != nullptr;       // A/B switch (tools)
     if (!off && (g.nsplit > 1 || g.kmajor) && !g.split && !(g.dbg & 3) && !g.bias && !g.round_mid && (g.N % 128) == 0 && g.map_mode == MAP_LINEAR &&
         g.res_mode == RES_NONE && g.act == ACT_NONE && g.out_dtype == DT_F32 && (g.ldc % 4) == 0 && (g.c_split_stride % 4) == 0 &&
@@ -1489,73 +1477,126 @@ int select_epi(const GemmArgs& g) {
     return EPI_GENERIC;
 }
 
-template <typename T>
-int dispatch(const GemmArgs& g, hipStream_t stream) {
+// The launcher's whole choice for a problem that passed gemm_check: which epilogue, which tile, how large a persistent grid.  `cus` is a
+// parameter so that the choice can be asked for without a device (lseg_op_gemm_ex_plan).  Returns 0 or a negative lseg_status.
+int plan_gemm(const GemmArgs& g, int dt, int cus, GemmPlan& p) {
+    // tools/tests: 1 = 64x64, 2 = 128x128, 6 = 256x256.  Read ONCE per process (function-local static: thread-safe initialisation, no getenv
+    // on the launch path -- several hundred launches per forward, possibly from several host threads); the sweeping tool and the forced-tile
+    // tests start one interpreter per tile (tools/tile_sweep.py, tests/test_gpu_tile_configs.py)
+    static const int force = [] { const char* e = getenv("LSEG_GEMM_TILE"); return e ? atoi(e) : 0; }();
+    const long nsplit = g.nsplit > 1 ? g.nsplit : 1;
     if (g.kmajor) {
-        if (select_epi<T>(g) != EPI_PART32 || g.conv || (g.relu_in && !g.kconv_cin) || (g.kconv_cin && ((g.kconv_cin % 128) || g.ldw != g.kconv_cin)) || g.k_valid < 1 || g.k_valid > g.K || g.K - g.k_valid >= 64 ||
+        if (select_epi(g, dt) != EPI_PART32 || g.conv || (g.relu_in && !g.kconv_cin) || (g.kconv_cin && ((g.kconv_cin % 128) || g.ldw != g.kconv_cin)) || g.k_valid < 1 || g.k_valid > g.K || g.K - g.k_valid >= 64 ||
             (double)g.k_valid * g.lda * 2 >= 2.0e9 || (double)g.k_valid * g.ldw * 2 >= 2.0e9)
             return set_error(LSEG_ERR_UNSUPPORTED, "K-major GEMM: needs fp32 slab output (MAP_LINEAR, no bias / residual), N %% 128 == 0, operands < 2 GB");
-        if (g.relu_in) return launch_one<T, CfgMid, false, true, EPI_PART32, 2>(g, stream);
-        return launch_one<T, CfgMid, false, false, EPI_PART32, 2>(g, stream);
-    }
-    if (g.map_mode == MAP_ROWNORM) {
+        p.epi = EPI_PART32; p.tile = 2;
+    } else if (g.map_mode == MAP_ROWNORM) {
         if (g.split) return set_error(LSEG_ERR_UNSUPPORTED, "the fused head has no split-precision form (use the two-kernel path)");
         if (g.conv || g.relu_in || g.N != 512 || !g.bias)
             return set_error(LSEG_ERR_UNSUPPORTED, "fused head needs a plain GEMM with N == 512 and a bias");
-        return launch_one<T, CfgRow, false, false, EPI_GENERIC, 0>(g, stream);
-    }
-    const int epi = select_epi<T>(g);
-    if (g.conv) {
-        if (epi == EPI_PART32) return pick_tile<T, true, false, EPI_PART32, 0>(g, stream);
-        if (epi == EPI_PAD16) {
-            if (g.relu_in) return pick_tile<T, true, true, EPI_PAD16, 0>(g, stream);
-            return pick_tile<T, true, false, EPI_PAD16, 0>(g, stream);
+        p.epi = EPI_GENERIC; p.tile = 4;
+    } else {
+        int epi = select_epi(g, dt);
+        if (g.conv && epi != EPI_PART32 && epi != EPI_PAD16) epi = EPI_GENERIC;
+        if (!g.conv && g.relu_in) return set_error(LSEG_ERR_UNSUPPORTED, "gemm: relu_in is only implemented for the conv path");
+        if (!g.conv && g.split && dt != DT_F16) return set_error(LSEG_ERR_UNSUPPORTED, "split precision runs on fp16 (hi, lo) pairs");
+        const long t_mid = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * nsplit;
+        int pick = t_mid >= 192 ? 2 : 1;
+        if (epi == EPI_GENERIC && !g.conv && g.map_mode == MAP_LABELPLANES && g.M > 128 && g.M <= 160 && !force) {
+            pick = 5;
+        } else {
+            if (epi != EPI_GENERIC && pick == 2) {
+                // 256x256 tiles (one 8-wave workgroup per CU) move half the operand bytes per MFMA through the
+                // CU's L1/LDS-DMA path and run ~12% faster per flop than two 128x128 workgroups -- when the
+                // tile count quantises well over the 256 CUs.  Persistent schedules: ceil(tiles / slots) rounds.
+                const long t_huge = (long)((g.M + 255) / 256) * ((g.N + 255) / 256) * nsplit;
+                const double time_huge = (double)((t_huge + 255) / 256) * 4.0 / 1.12;
+                const double time_mid = (double)((t_mid + 511) / 512) * 2.0;
+                if (time_huge < time_mid) pick = 6;
+            }
+            if (g.tile_hint == 1 || g.tile_hint == 2 || g.tile_hint == 6) pick = g.tile_hint;
+            if (force) pick = force;
+            if (pick == 6 && (g.N % 256) != 0) pick = 2;      // the specialised epilogues write whole tile rows: N must be a multiple of BN
+            if (pick == 6 && epi == EPI_GENERIC) pick = 2;    // the generic epilogue has no 256x256 instantiation
+            if (pick != 6 && pick != 2) pick = 1;
         }
-        if (g.relu_in) return pick_tile<T, true, true, EPI_GENERIC, 0>(g, stream);
-        return pick_tile<T, true, false, EPI_GENERIC, 0>(g, stream);
+        p.epi = epi; p.tile = pick;
     }
-    if (g.relu_in && !g.kmajor) return set_error(LSEG_ERR_UNSUPPORTED, "gemm: relu_in is only implemented for the conv path");
-    if (g.split && !std::is_same<T, F16>::value) return set_error(LSEG_ERR_UNSUPPORTED, "split precision runs on fp16 (hi, lo) pairs");
-    switch (epi) {
-        case EPI_PAD16: return pick_tile<T, false, false, EPI_PAD16, 0>(g, stream);
-        case EPI_LIN16: return pick_tile<T, false, false, EPI_LIN16, 0>(g, stream);
+    // persistent grid: a multiple of 8 (one slice per XCD), at most `slots` resident workgroups
+    const TileGeom tg = tile_geom(p.tile);
+    const long tiles = (long)((g.M + tg.bm - 1) / tg.bm) * ((g.N + tg.bn - 1) / tg.bn) * nsplit;
+    const long slots = (long)cus * tg.per_cu;
+    long grid = ((tiles + 7) / 8) * 8;
+    if (grid > slots) grid = slots;
+    if (g.max_grid >= 8 && grid > g.max_grid) grid = g.max_grid & ~7;      // tools: part of the chip (tools/epilogue_table.py)
+    p.grid = (int)grid;
+    const long wpx = grid >> 3, per_xcd = (tiles + 7) / 8;                 // the kernel's schedule: XCD x walks its slice with stride grid / 8
+    p.items = wpx > 0 ? (int)((per_xcd + wpx - 1) / wpx) : 0;
+    return 0;
+}
+
+template <typename T>
+int dispatch(const GemmArgs& g, hipStream_t stream) {
+    constexpr int dt = std::is_same<T, BF16>::value ? DT_BF16 : DT_F16;
+    GemmPlan p{};
+    LSEG_HIP_TRY(hipGetDevice(&p.dev));
+    const int r = plan_gemm(g, dt, device_cu_count(p.dev), p);
+    if (r) return r;
+    if (g.kmajor) {
+        if (g.relu_in) return launch_one<T, CfgMid, false, true, EPI_PART32, 2>(g, p, stream);
+        return launch_one<T, CfgMid, false, false, EPI_PART32, 2>(g, p, stream);
+    }
+    if (g.map_mode == MAP_ROWNORM) return launch_one<T, CfgRow, false, false, EPI_GENERIC, 0>(g, p, stream);
+    if (g.conv) {
+        if (p.epi == EPI_PART32) return pick_tile<T, true, false, EPI_PART32, 0>(g, p, stream);
+        if (p.epi == EPI_PAD16) {
+            if (g.relu_in) return pick_tile<T, true, true, EPI_PAD16, 0>(g, p, stream);
+            return pick_tile<T, true, false, EPI_PAD16, 0>(g, p, stream);
+        }
+        if (g.relu_in) return pick_tile<T, true, true, EPI_GENERIC, 0>(g, p, stream);
+        return pick_tile<T, true, false, EPI_GENERIC, 0>(g, p, stream);
+    }
+    switch (p.epi) {
+        case EPI_PAD16: return pick_tile<T, false, false, EPI_PAD16, 0>(g, p, stream);
+        case EPI_LIN16: return pick_tile<T, false, false, EPI_LIN16, 0>(g, p, stream);
         case EPI_LIN16_GELU:
-            if (g.tag == 1) return pick_tile<T, false, false, EPI_LIN16_GELU, 1>(g, stream);
-            return pick_tile<T, false, false, EPI_LIN16_GELU, 0>(g, stream);
-        case EPI_RES32: return pick_tile<T, false, false, EPI_RES32, 0>(g, stream);
-        case EPI_LIN16_F16: return pick_tile<T, false, false, EPI_LIN16_F16, 0>(g, stream);
-        case EPI_LIN32: return pick_tile<T, false, false, EPI_LIN32, 0>(g, stream);
-        case EPI_LIN16_GELU2: return pick_tile<T, false, false, EPI_LIN16_GELU2, 0>(g, stream);
-        case EPI_LIN16_DGELU: return pick_tile<T, false, false, EPI_LIN16_DGELU, 0>(g, stream);
-        case EPI_PIX16: return pick_tile<T, false, false, EPI_PIX16, 0>(g, stream);
-        case EPI_QKV16: return pick_tile<T, false, false, EPI_QKV16, 0>(g, stream);
-        case EPI_PART32: return pick_tile<T, false, false, EPI_PART32, 0>(g, stream);
-        default: return pick_tile<T, false, false, EPI_GENERIC, 0>(g, stream);
+            if (g.tag == 1) return pick_tile<T, false, false, EPI_LIN16_GELU, 1>(g, p, stream);
+            return pick_tile<T, false, false, EPI_LIN16_GELU, 0>(g, p, stream);
+        case EPI_RES32: return pick_tile<T, false, false, EPI_RES32, 0>(g, p, stream);
+        case EPI_LIN16_F16: return pick_tile<T, false, false, EPI_LIN16_F16, 0>(g, p, stream);
+        case EPI_LIN32: return pick_tile<T, false, false, EPI_LIN32, 0>(g, p, stream);
+        case EPI_LIN16_GELU2: return pick_tile<T, false, false, EPI_LIN16_GELU2, 0>(g, p, stream);
+        case EPI_LIN16_DGELU: return pick_tile<T, false, false, EPI_LIN16_DGELU, 0>(g, p, stream);
+        case EPI_PIX16: return pick_tile<T, false, false, EPI_PIX16, 0>(g, p, stream);
+        case EPI_QKV16: return pick_tile<T, false, false, EPI_QKV16, 0>(g, p, stream);
+        case EPI_PART32: return pick_tile<T, false, false, EPI_PART32, 0>(g, p, stream);
+        default: return pick_tile<T, false, false, EPI_GENERIC, 0>(g, p, stream);
     }
 }
 
 }  // namespace
 
 bool gemm_epilogue_is_pad16(const GemmArgs& g, int ab_dtype) {
-    if (ab_dtype == DT_BF16) return select_epi<BF16>(g) == EPI_PAD16;
-    if (ab_dtype == DT_F16) return select_epi<F16>(g) == EPI_PAD16;
+    if (ab_dtype == DT_BF16) return select_epi(g, DT_BF16) == EPI_PAD16;
+    if (ab_dtype == DT_F16) return select_epi(g, DT_F16) == EPI_PAD16;
     return false;
 }
 
 bool gemm_qkv_scales_q(const GemmArgs& g, int ab_dtype) {
-    const int e = ab_dtype == DT_BF16 ? select_epi<BF16>(g) : ab_dtype == DT_F16 ? select_epi<F16>(g) : EPI_GENERIC;
+    const int e = ab_dtype == DT_BF16 ? select_epi(g, DT_BF16) : ab_dtype == DT_F16 ? select_epi(g, DT_F16) : EPI_GENERIC;
     return !g.conv && !g.kmajor && g.map_mode == MAP_QKV && e == EPI_QKV16;
 }
 
 bool gemm_fuses_gelu(const GemmArgs& g, int ab_dtype) {
     static const bool off = getenv("LSEG_NO_GELU_FUSE") != nullptr;       // tools: A/B switch back to the separate GELU passes
     if (off) return false;
-    const int e = ab_dtype == DT_BF16 ? select_epi<BF16>(g) : ab_dtype == DT_F16 ? select_epi<F16>(g) : EPI_GENERIC;
+    const int e = ab_dtype == DT_BF16 ? select_epi(g, DT_BF16) : ab_dtype == DT_F16 ? select_epi(g, DT_F16) : EPI_GENERIC;
     return !g.conv && !g.kmajor && g.map_mode != MAP_ROWNORM && (e == EPI_LIN16_GELU2 || e == EPI_LIN16_DGELU);
 }
 
-int launch_gemm(const GemmArgs& g_in, int ab_dtype, hipStream_t stream) {
-    GemmArgs g = g_in;
+// What every launch applies to its argument block (the tools' environment switches) and every refusal that precedes the choice of a kernel:
+// shared by launch_gemm and gemm_plan, so that a plan is given for exactly the problems a launch accepts.
+static int gemm_prepare(GemmArgs& g, int ab_dtype) {
     static const int dbg = getenv("LSEG_GEMM_DBG") ? atoi(getenv("LSEG_GEMM_DBG")) : 0;
     g.dbg = dbg;
     static const int group_env = getenv("LSEG_GEMM_GROUP_M") ? atoi(getenv("LSEG_GEMM_GROUP_M")) : 0;     // tools: A/B of the rasterisation group
@@ -1586,11 +1627,35 @@ int launch_gemm(const GemmArgs& g_in, int ab_dtype, hipStream_t stream) {
         if (a_bytes >= 4.0e9 || (double)g.N * g.ldw * 2 >= 4.0e9)
             return set_error(LSEG_ERR_UNSUPPORTED, "gemm: operand larger than 4 GB (32-bit lane offsets)");
     }
+    if (ab_dtype != DT_BF16 && ab_dtype != DT_F16) return set_error(LSEG_ERR_INVALID, "gemm: operand dtype %d", ab_dtype);
+    return 0;
+}
+
+int gemm_check(const GemmArgs& g_in, int ab_dtype) {
+    GemmArgs g = g_in;
+    const int r = gemm_prepare(g, ab_dtype);
+    if (r) return r;
+    GemmPlan p{};
+    return plan_gemm(g, ab_dtype, 1, p);        // the refusals that depend on the kernel chosen; none of them depends on the CU count
+}
+
+int gemm_plan(const GemmArgs& g_in, int ab_dtype, int cus, GemmPlan& p) {
+    GemmArgs g = g_in;
+    const int r = gemm_prepare(g, ab_dtype);
+    if (r) return r;
+    if (cus < 1) return set_error(LSEG_ERR_INVALID, "gemm_plan: cus=%d", cus);
+    p = GemmPlan{};
+    return plan_gemm(g, ab_dtype, cus, p);
+}
+
+int launch_gemm(const GemmArgs& g_in, int ab_dtype, hipStream_t stream) {
+    GemmArgs g = g_in;
+    const int r = gemm_prepare(g, ab_dtype);
+    if (r) return r;
     // the residual Linears of the ViT block: the hand-scheduled kernel (gemm_asm.hip) when asked for (LSEG_GEMM_ASM=1) and the buffers are tile-padded
     if (gemm_res32_asm_enabled() && gemm_res32_asm_eligible(g, ab_dtype)) return launch_gemm_res32_asm(g, ab_dtype, stream);
     if (ab_dtype == DT_BF16) return dispatch<BF16>(g, stream);
-    if (ab_dtype == DT_F16) return dispatch<F16>(g, stream);
-    return set_error(LSEG_ERR_INVALID, "gemm: operand dtype %d", ab_dtype);
+    return dispatch<F16>(g, stream);
 }
 
 }  // namespace lseg

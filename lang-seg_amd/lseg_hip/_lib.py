@@ -35,6 +35,21 @@ class LSegConfigC(C.Structure):
     ]
 
 
+class LSegGemmCase(C.Structure):
+    """lseg_gemm_case of include/lseg_hip.h (lseg_op_gemm_ex, lseg_op_gemm_ex_plan)."""
+    _fields_ = [
+        ("form", C.c_int),
+        ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p),
+        ("C", C.c_void_p), ("Ck", C.c_void_p), ("Cv", C.c_void_p),
+        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("ab_dtype", C.c_int), ("out_dtype", C.c_int), ("res_dtype", C.c_int), ("act", C.c_int),
+        ("tag", C.c_int), ("tile", C.c_int), ("max_grid", C.c_int),
+        ("nsplit", C.c_int), ("split_steps", C.c_int), ("c_split_stride", C.c_size_t),
+        ("ntok", C.c_int), ("npad", C.c_int), ("heads", C.c_int), ("qscale", C.c_float),
+        ("ho", C.c_int), ("wo", C.c_int), ("s", C.c_int), ("ch", C.c_int),
+        ("p_div", C.c_int), ("p_mul", C.c_int), ("p_off", C.c_int), ("ldr", C.c_int),
+    ]
+
+
 class LSegError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -98,6 +113,8 @@ SIGNATURES = {
     "lseg_op_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_vit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_res32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_gemm_ex": (_i, [C.POINTER(LSegGemmCase), _vp]),
+    "lseg_op_gemm_ex_plan": (_i, [C.POINTER(LSegGemmCase), _i, C.POINTER(_i * 4)]),
     "lseg_op_colsum": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_bn_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_bn_bwd_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, C.c_size_t, _vp]),
