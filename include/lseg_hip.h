@@ -389,6 +389,32 @@ int lseg_op_attention(const void* d_q, const void* d_k, const void* d_vt, void* 
  * 2^(q'.k).  Same layouts as lseg_op_attention. */
 int lseg_op_attention_prescaled(const void* d_q, const void* d_k, const void* d_vt, void* d_out, float* d_lse2,
                                 int B, int H, int Ntok, int Npad, int dtype, void* stream);
+/* Both of the above through one entry, the engine's launcher as it is: prescaled = 0 (scale applied to the scores, optional causal mask)
+ * or 1 (q carries scale * log2(e), `scale` ignored, no causal form: LSEG_ERR_UNSUPPORTED).  d_lse2 (optional, fp32 [B*H, Npad]) receives
+ * log2 sum_k 2^(s_k scale log2(e)) over the unmasked keys of each query row -- what the training step saves for the backward.
+ * Refused: Npad % 128 != 0 or Npad < Ntok, dtype LSEG_F32, NULL q / k / vt / out, B, H or Ntok < 1.
+ *
+ * PADDING CONTRACT of the forward (rows Ntok .. Npad-1 of q and k, columns Ntok .. Npad-1 of every vt row), read from csrc/attention.hip:
+ *   q    padded rows: any finite value.  They are loaded by the lanes of a partly filled wave; nothing computed from them is stored.
+ *        (Pre-scaled form: a padded row can fire its wave's refresh of the reference maximum, which moves the roundings of the wave's
+ *        real rows within their error bound; the plain form's outputs do not depend on the padding bit for bit.)
+ *   k    padded rows: any finite value.  Their scores are replaced by -inf before the row maximum is taken.
+ *   vt   padded columns: any finite value.  They meet a probability of exactly 0 in the P V product (0 x finite = 0; an inf or NaN there
+ *        would poison the row).
+ *   out  [B, Ntok, H*64] has no padding: every element is written.
+ *   lse2 rows < Ntok of every head are written; rows Ntok .. Npad-1 are LEFT UNWRITTEN (they keep what the caller put there). */
+int lseg_op_attention_ex(const void* d_q, const void* d_k, const void* d_vt, void* d_out, float* d_lse2, int B, int H, int Ntok, int Npad,
+                         int dtype, int causal, float scale, int prescaled, void* stream);
+/* What that launch decides on a device of `cus` compute units, host only (no device needed): out6 = {waves per workgroup (2 | 4; a
+ * workgroup owns 32 x waves query rows of one head), query blocks per head, workgroups, 64-key tiles the last query block walks,
+ * 1 when the head -> XCD map applies (B * H % 8 == 0) else 0, dynamic LDS bytes (two stages of a K and a V^T tile)}.
+ * Refused: B, H, Ntok or cus < 1, prescaled with causal (LSEG_ERR_UNSUPPORTED), NULL out6. */
+int lseg_op_attention_plan(int B, int H, int Ntok, int causal, int prescaled, int cus, int* out6);
+/* The split-precision ("strict") forward: every operand is a pair of fp16 planes, x = hi + lo, the lo plane `*_plane` ELEMENTS behind the
+ * hi plane (q and k share qk_plane); softmax(Q K^T scale) V in fp32, no mask; out [B, Ntok, H*64] written as hi and lo planes.
+ * Padded rows / columns of q, k, vt are never read (any value, finite or not).  Refused: NULL q / k / vt / out, B, H or Ntok < 1. */
+int lseg_op_attention_strict(const void* d_q, const void* d_k, const void* d_vt, void* d_out, size_t qk_plane, size_t vt_plane,
+                             size_t out_plane, int B, int H, int Ntok, int Npad, float scale, void* stream);
 /* 3x3 conv, NHWC, zero-padded borders: in [B,H+2,W+2,Cin] (bf16, border = 0) ->
  * out [B,Ho+2,Wo+2,Cout] interior written; w_packed [Cout, 9*Cin] bf16 (tap-major).
  * stride 1|2, relu_in / relu_out flags, bias fp32 [Cout] or NULL, residual (same
@@ -655,7 +681,23 @@ int lseg_op_softmax_ce_backward(const float* d_scores, const int64_t* d_target, 
  * d_q,d_k [BH,Npad,64], d_vt [BH,64,Npad], d_o / d_do [B,Ntok,H*64] (forward layouts, bf16/fp16); d_lse2 [BH,Npad] fp32 = log2 of
  * each query row's sum_k exp2(s_k * scale * log2e) (the forward's running statistics) -- a dQ kernel and a
  * dK/dV kernel in the forward kernel's MFMA / direct-to-LDS structure, writing d(qkv Linear output) [B*Ntok, 3*H*64] (bf16/fp16)
- * directly.  d_ws: lseg_op_attention_backward_ws_bytes(B, H, Npad) bytes of device scratch, or NULL (then allocated per call). */
+ * directly.  d_ws: lseg_op_attention_backward_ws_bytes(B, H, Npad) bytes of device scratch, or NULL (then allocated per call).
+ * What is computed, from the operands as given: P = exp2(Q K^T scale log2(e) - lse2), D = rowsum(dO o O), dS = P o (dO V^T - D) scale,
+ * dQ = dS K, dK = dS^T Q, dV = P^T dO (P and dS rounded once to the operand type).
+ * Refused: Npad % 128 != 0 or Npad < Ntok, dtype LSEG_F32, a NULL operand, B, H or Ntok < 1, q / k / vt / o / do / ws not 16-byte aligned.
+ *
+ * PADDING CONTRACT of the backward (rows Ntok .. Npad-1 of q, k, lse2; columns Ntok .. Npad-1 of every vt row), read from
+ * csrc/attention_bwd2.hip.  d_o and d_do [B, Ntok, H*64] have no padding; the prep kernel supplies dO = 0 and D = 0 for padded queries.
+ *   k    padded rows: any finite value.  dQ: their probabilities are replaced by 0 and 0 x k stays 0.  dK / dV: their lanes store nothing.
+ *   vt   padded columns: any finite value (dQ multiplies dO . v_pad by the probability 0).
+ *   q    padded rows: finite AND bounded together with lse2 (next line).  The dK / dV kernel does NOT mask padded queries: they add
+ *        P x 0 and 0 x q, which is 0 only while P is finite after its rounding to the operand type and q is finite.
+ *   lse2 padded rows: finite, and for every padded row r and every key j < Ntok
+ *            q_r . k_j scale log2(e) - lse2[r] <= 15 (fp16) | 127 (bf16),
+ *        so that exp2 of it stays finite in the operand type (0 x inf is NaN in the matrix pipe).  lseg_op_attention_ex leaves these
+ *        rows unwritten: the caller initialises them once.  All-zero q and lse2 padding -- zero-allocated buffers, as the engine's are --
+ *        satisfies this (P = 1).
+ *   dqkv [B*Ntok, 3*H*64] has no padding: every element is written.  d_ws is overwritten entirely. */
 size_t lseg_op_attention_backward_ws_bytes(int B, int H, int Npad);
 int lseg_op_attention_backward_qkv(const void* d_q, const void* d_k, const void* d_vt, const void* d_o, const void* d_do,
                                    const float* d_lse2, void* d_dqkv, void* d_ws, int B, int H, int Ntok, int Npad, int dtype,

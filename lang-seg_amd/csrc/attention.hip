@@ -329,6 +329,22 @@ int launch_attention_lse(const void* q, const void* k, const void* vt, void* out
     return launch_attention_ex(q, k, vt, out, lse2, B, H, ntok, npad, dtype, causal, scale, 0, stream);
 }
 
+// What launch_attention_ex launches for a shape on a device of `cus` compute units: the one place the choice is made (the launcher and the
+// host-only lseg_op_attention_plan both ask here).  2-wave workgroups when the 4-wave grid would not fill the chip (never for causal masks);
+// the kernels are launched with NS = 2 stages of K + V^T (2 x 16 KB of dynamic LDS) whatever the template could do.
+int plan_attention(int B, int H, int ntok, int causal, int prescaled, int cus, AttnPlan& p) {
+    if (B < 1 || H < 1 || ntok < 1 || cus < 1) return set_error(LSEG_ERR_INVALID, "attention: B=%d H=%d ntok=%d cus=%d must be >= 1", B, H, ntok, cus);
+    if (prescaled && causal) return set_error(LSEG_ERR_UNSUPPORTED, "attention: the pre-scaled form has no causal variant");
+    const bool narrow = (long)((ntok + 127) / 128) * B * H < 2L * cus && !causal;      // 2-wave workgroups when the grid would not fill the chip
+    p.nw = narrow ? 2 : 4;
+    p.nqb = (ntok + 32 * p.nw - 1) / (32 * p.nw);
+    p.grid = p.nqb * B * H;
+    p.last_tiles = (ntok + 63) >> 6;             // the last query block's kv_end is ntok with and without the causal mask
+    p.xcd_map = ((B * H) & 7) == 0;
+    p.lds = 2 * 2 * 8192;
+    return 0;
+}
+
 // prescaled != 0: q was written as T(q * scale * log2(e)) (one rounding, in the QKV GEMM's epilogue: GemmArgs::qkv_qscale) -- the
 // inference engine's path; the matrix pipe then delivers the exp2 argument directly (kernel PRE = true).  Not for causal masks.
 int launch_attention_ex(const void* q, const void* k, const void* vt, void* out, float* lse2, int B, int H, int ntok,
@@ -344,10 +360,12 @@ int launch_attention_ex(const void* q, const void* k, const void* vt, void* out,
     if (dtype != DT_BF16 && dtype != DT_F16) return set_error(LSEG_ERR_INVALID, "attention: dtype %d", dtype);
     int dev = 0;
     LSEG_HIP_TRY(hipGetDevice(&dev));
-    const bool narrow = (long)((ntok + 127) / 128) * B * H < 2L * device_cu_count(dev) && !causal;      // 2-wave workgroups when the grid would not fill the chip
-    const int nw = narrow ? 2 : 4;
-    const size_t lds = (size_t)2 * 2 * 8192;
-    dim3 grid(((ntok + 32 * nw - 1) / (32 * nw)) * B * H);
+    AttnPlan p;
+    const int r = plan_attention(B, H, ntok, causal, prescaled, device_cu_count(dev), p);
+    if (r) return r;
+    const int nw = p.nw;
+    const size_t lds = (size_t)p.lds;
+    dim3 grid(p.grid);
 #define ATT(TT, NWV, PV) hipLaunchKernelGGL((lseg_attention_kernel<TT, NWV, 2, PV>), grid, dim3(64 * NWV), lds, stream, a)
 #define ATT_T(NWV, PV) do { if (dtype == DT_BF16) ATT(BF16, NWV, PV); else ATT(F16, NWV, PV); } while (0)
     if (nw == 2) { if (prescaled) ATT_T(2, true); else ATT_T(2, false); }

@@ -405,6 +405,33 @@ int lseg_op_attention_prescaled(const void* q, const void* k, const void* vt, vo
     return launch_attention_ex(q, k, vt, out, lse2, B, H, Ntok, Npad, dt, 0, 1.0f, 1, (hipStream_t)stream);
 }
 
+int lseg_op_attention_ex(const void* q, const void* k, const void* vt, void* out, float* lse2, int B, int H, int Ntok, int Npad, int dtype,
+                         int causal, float scale, int prescaled, void* stream) {
+    int r = require_device(); if (r) return r;
+    int dt;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (!q || !k || !vt || !out) return set_error(LSEG_ERR_INVALID, "attention_ex: NULL pointer");
+    if (B < 1 || H < 1 || Ntok < 1) return set_error(LSEG_ERR_INVALID, "attention_ex: bad shape");
+    return launch_attention_ex(q, k, vt, out, lse2, B, H, Ntok, Npad, dt, causal, scale, prescaled, (hipStream_t)stream);
+}
+
+int lseg_op_attention_plan(int B, int H, int Ntok, int causal, int prescaled, int cus, int* out6) {
+    if (!out6) return set_error(LSEG_ERR_INVALID, "attention_plan: NULL pointer");
+    AttnPlan p;
+    const int r = plan_attention(B, H, Ntok, causal, prescaled, cus, p);
+    if (r) return r;
+    out6[0] = p.nw; out6[1] = p.nqb; out6[2] = p.grid; out6[3] = p.last_tiles; out6[4] = p.xcd_map; out6[5] = p.lds;
+    return 0;
+}
+
+int lseg_op_attention_strict(const void* q, const void* k, const void* vt, void* out, size_t qk_plane, size_t vt_plane, size_t out_plane,
+                             int B, int H, int Ntok, int Npad, float scale, void* stream) {
+    int r = require_device(); if (r) return r;
+    if (!q || !k || !vt || !out) return set_error(LSEG_ERR_INVALID, "attention_strict: NULL pointer");
+    if (B < 1 || H < 1 || Ntok < 1) return set_error(LSEG_ERR_INVALID, "attention_strict: bad shape");
+    return launch_attention_strict(q, k, vt, out, qk_plane, vt_plane, out_plane, B, H, Ntok, Npad, scale, (hipStream_t)stream);
+}
+
 int lseg_op_conv3x3(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B,
                     int H, int W, int Cin, int Cout, int stride, int relu_in, int relu_out, void* stream) {
     int r = require_device(); if (r) return r;

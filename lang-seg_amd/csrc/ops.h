@@ -164,6 +164,11 @@ int launch_attention_lse(const void* q, const void* k, const void* vt, void* out
                          int causal, float scale, hipStream_t stream);
 int launch_attention_ex(const void* q, const void* k, const void* vt, void* out, float* lse2, int B, int H, int ntok, int npad, int dtype,
                         int causal, float scale, int prescaled, hipStream_t stream);
+// What launch_attention_ex launches on a device of `cus` compute units (host only): nw = waves per workgroup (2 | 4), nqb = query blocks of
+// 32 nw rows per head, grid = workgroups, last_tiles = 64-key tiles the last query block walks, xcd_map = the head -> XCD map applies
+// (B * H % 8 == 0), lds = dynamic LDS bytes.  Refuses B, H, ntok, cus < 1 and prescaled with causal.
+struct AttnPlan { int nw, nqb, grid, last_tiles, xcd_map, lds; };
+int plan_attention(int B, int H, int ntok, int causal, int prescaled, int cus, AttnPlan& p);
 int launch_bn_stats(const void* x, float* stats, int B, int H, int W, int C, int dtype, hipStream_t st, int pre_zeroed = 0,
                     float* det_ws = nullptr, size_t det_cap = 0);
 int launch_bn_apply(const void* x, void* y, const float* stats, const float* gamma, const float* beta, const void* res1, const void* res2,

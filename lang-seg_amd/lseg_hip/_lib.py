@@ -121,6 +121,9 @@ SIGNATURES = {
     "lseg_op_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "lseg_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_attention_prescaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_attention_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "lseg_op_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i * 6)]),
+    "lseg_op_attention_strict": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _i, _i, _f, _vp]),
     "lseg_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_upsample2x_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_rn_stem": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
