@@ -523,6 +523,57 @@ int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const 
                           int ignore_index, const int64_t* d_class_id, int nclass, int64_t* d_inter_buf, int64_t* d_union_buf,
                           int64_t* d_areas, double* d_nll, int64_t* d_flags, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Segmentation statistics of a LABEL MAP against a target mask (csrc/label_stats.hip): lseg_op_seg_stats' counters for the routes that
+ * never form the [B,K,H,W] scores (lseg_forward_labels, the ragged lists of lseg_set_text_groups, BatchedMultiEval.forward_labels).
+ * replaces: batch_pix_accuracy + batch_intersection_union ([3P] encoding/utils/metrics.py) on torch.max(scores, 1)[1].
+ * d_label int16 [B,H,W]; d_target int64 [B,H,W]; any alignment of their elements (a lane reads four pixels: one 8-byte label load and
+ *   two 16-byte target loads where the addresses allow, element loads at the ends of an image).
+ * Shared label set (d_offsets NULL): d_counts int64 [2+3K] = {correct, labeled, area_inter[K], area_pred[K], area_lab[K]}, the layout of
+ *   lseg_op_seg_stats.  Per pixel (label l, target t): t == -1 or t == ignore_index is unlabeled and counts nowhere; any other t < 0
+ *   counts nowhere and is flagged; otherwise labeled++ and area_pred[l]++, and for t < K area_lab[t]++ and, when l == t, correct++ and
+ *   area_inter[l]++; t >= K is flagged and is in no area_lab and no intersection (the predicted area still counts, as in
+ *   lseg_op_episode_stats).  With ignore_index = -1, or a target that holds no ignore_index, this is lseg_op_seg_stats' rule: the counts
+ *   equal its counts for any scores whose first-maximum arg-max is d_label, exactly.
+ * Ragged lists (d_offsets int32 [B+1] on the DEVICE, the prefix sum of the per-image counts as lseg_op_corr_argmax_ragged leaves it; K =
+ *   the largest count, an upper bound for every image): labels and targets of image b index its own list [0, k_b).  Without d_class_map
+ *   the areas are indexed offsets[b] + l and have length offsets[B], which takes K's place in the d_counts layout.  With d_class_map
+ *   int32 [offsets[B]] prediction and target both go through class_map[offsets[b] + l] in [0, nclass): three areas of length nclass,
+ *   a pixel is correct when the two class ids agree, duplicate ids add up, and an id outside [0, nclass) is skipped, never written out
+ *   of bounds (the caller validates the ids on the host, as for lseg_op_episode_stats).
+ * d_flags int64 [2] = {pixels whose target is neither unlabeled nor inside its label range, pixels whose label is outside its range (these
+ *   count nowhere)}.  accumulate = 0 overwrites d_counts and d_flags, 1 adds to both: a meter can live on the device across batches.
+ * Areas: while 3 x bins x 4 bytes fit 48 KiB (bins <= 4096; bins = K, or nclass with a map) every workgroup keeps its three histograms in
+ *   LDS and flushes the non-zero bins with 64-bit atomics; above that every update is a 64-bit global atomic.  Integer sums: exact in any
+ *   order.  lseg_op_label_stats_plan (host only, no device) returns out2 = {route: 0 LDS / 1 global, bins per workgroup (0 on route 1)}.
+ * Before anything is launched or the device is touched: LSEG_ERR_INVALID for a NULL required pointer, B, H, W or K < 1, a map without
+ *   offsets or with nclass < 1, pointers not aligned to their element; LSEG_ERR_UNSUPPORTED for K > 32767 or H W > 2^31 - 1. */
+int lseg_op_label_stats_plan(int K_or_bins, int* out2);
+int lseg_op_label_stats(const int16_t* d_label, const int64_t* d_target, int B, int H, int W, int K, int ignore_index,
+                        const int32_t* d_offsets, const int32_t* d_class_map, int nclass, int64_t* d_counts, int64_t* d_flags,
+                        int accumulate, void* stream);
+/* lseg_op_seg_stats_lowres for a label set walked in PANELS (csrc/label_stats.hip): metrics and the cross-entropy value with peak memory
+ * set by the panel, not by K -- the scoring side of the held-features route (lseg_forward_features / lseg_score_features).
+ *   lseg_op_stats_fold_lowres  d_low fp32 [B,rows,h,w]: the low-resolution logits of labels row0 .. row0+rows-1, read through output_conv's
+ *       x2 bilinear (align_corners=True) on the fly -- every value is bit-identical to lseg_op_upsample2x_planes of the same planes.  Per
+ *       pixel of the [B,2h,2w] grid (d_target int64, d_label int16, d_best / d_sum / d_tlogit fp32): `if v > best: (best, label) = (v, k)`
+ *       (panels in ascending label order: the first maximum wins), the online sum of exp(v - best) by lseg_op_eval_merge_labels' rule (a new
+ *       best rescales, sum = sum * exp(old_best - new_best) + 1; any other value adds exp(v - best)), and d_tlogit = v where k == target
+ *       (NaN until a panel holds the target).  first = 1 writes the state without reading it.  h, w >= 2; d_label 4-byte, the fp32 planes
+ *       and d_target 8-byte aligned (a lane owns a pixel pair).  row0 + rows > 32767: LSEG_ERR_UNSUPPORTED.
+ *   lseg_op_stats_finish       d_counts int64 [2+3K] exactly as lseg_op_label_stats (shared label set, accumulate = 0) gives from d_label --
+ *       one kernel body -- and d_nll double [2] = {sum over valid pixels (target in [0, K), != ignore_index) of best + log(sum) - tlogit,
+ *       number of those pixels}: per-workgroup partials in d_ws folded in ascending order, so two calls on the same input give the same
+ *       bits.  d_flags int64 [3] = lseg_op_label_stats' two words and the number of valid pixels whose target no panel covered (a caller
+ *       error: left out of the sum and the count).  d_ws: lseg_op_stats_finish_ws_bytes(B, H, W) bytes of device scratch, 8-byte aligned.
+ * The state of K labels is the same bits for every partition into panels (label, best, tlogit exactly; sum is one chain of fp32 operations
+ * in label order whatever the panels).  LSEG_ERR_INVALID before anything is launched for NULL pointers and shapes < 1. */
+int lseg_op_stats_fold_lowres(const float* d_low, int B, int rows, int row0, int h, int w, const int64_t* d_target,
+                              int16_t* d_label, float* d_best, float* d_sum, float* d_tlogit, int first, void* stream);
+size_t lseg_op_stats_finish_ws_bytes(int B, int H, int W);
+int lseg_op_stats_finish(const int16_t* d_label, const float* d_best, const float* d_sum, const float* d_tlogit, const int64_t* d_target,
+                         int B, int H, int W, int K, int ignore_index, int64_t* d_counts, double* d_nll, int64_t* d_flags, void* d_ws,
+                         size_t ws_bytes, void* stream);
+
 /* The pixel x text correlation on the engine's commuted schedule (DESIGN.md par. 3.4), one dedicated kernel (csrc/corr.hip).
  * replaces: `logits_per_image = self.logit_scale * image_features.half() @ text_features.t()` (modules/models/lseg_net.py:194) together
  *   with the norm of lseg_net.py:190 -- as label planes R[b, k, p] = t_k . g_p on the quarter-resolution map g (the combined

@@ -575,6 +575,25 @@ int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const 
                                 d_nll, d_flags, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+// label_stats.hip: every check of these launchers comes before the device is touched (a refusal needs no device)
+int lseg_op_label_stats_plan(int K_or_bins, int* out2) { return label_stats_plan(K_or_bins, out2); }
+int lseg_op_label_stats(const int16_t* d_label, const int64_t* d_target, int B, int H, int W, int K, int ignore_index, const int32_t* d_offsets,
+                        const int32_t* d_class_map, int nclass, int64_t* d_counts, int64_t* d_flags, int accumulate, void* stream) {
+    return launch_label_stats(d_label, d_target, B, H, W, K, ignore_index, d_offsets, d_class_map, nclass, d_counts, d_flags, accumulate,
+                              (hipStream_t)stream);
+}
+int lseg_op_stats_fold_lowres(const float* d_low, int B, int rows, int row0, int h, int w, const int64_t* d_target, int16_t* d_label,
+                              float* d_best, float* d_sum, float* d_tlogit, int first, void* stream) {
+    return launch_stats_fold_lowres(d_low, B, rows, row0, h, w, d_target, d_label, d_best, d_sum, d_tlogit, first, (hipStream_t)stream);
+}
+size_t lseg_op_stats_finish_ws_bytes(int B, int H, int W) { return stats_finish_ws_bytes(B, H, W); }
+int lseg_op_stats_finish(const int16_t* d_label, const float* d_best, const float* d_sum, const float* d_tlogit, const int64_t* d_target, int B,
+                         int H, int W, int K, int ignore_index, int64_t* d_counts, double* d_nll, int64_t* d_flags, void* d_ws, size_t ws_bytes,
+                         void* stream) {
+    return launch_stats_finish(d_label, d_best, d_sum, d_tlogit, d_target, B, H, W, K, ignore_index, d_counts, d_nll, d_flags, d_ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
 int lseg_op_corr_argmax_ragged(const void* d_g16pad, const void* d_text16, const float* d_scale, const int32_t* host_counts, int32_t* d_offsets,
                                int16_t* d_label, float* d_score, int16_t* d_label2, float* d_score2, float* d_lse, int B, int H, int W, int C,
                                void* d_ws, size_t ws_bytes, void* stream) {

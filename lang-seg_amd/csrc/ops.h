@@ -132,6 +132,19 @@ size_t episode_stats_ws_bytes(int B, int H, int W);
 int launch_episode_stats(const float* scores, const int64_t* target, const uint8_t* ignore, int B, int H, int W, int up, int ignore_index,
                          const int64_t* class_id, int nclass, int64_t* inter_buf, int64_t* union_buf, int64_t* areas, double* nll,
                          int64_t* flags, void* ws, size_t ws_bytes, hipStream_t st);
+// label_stats.hip -- seg_stats' counters and loss value without the score planes: from a label map (shared label set, ragged per-image
+// lists with device offsets [B + 1], optionally mapped into [0, nclass) by class_map), and from the per-pixel state
+// (label, best, sum of exp(v - best), target logit) that stats_fold_lowres builds panel by panel from low-resolution logits [B,rows,h,w].
+// Every argument check comes before the device is touched.
+int label_stats_plan(int bins, int* out2);                // host only: {route (0 = LDS histograms, 1 = global atomics), bins per workgroup}
+int launch_label_stats(const int16_t* label, const int64_t* target, int B, int H, int W, int K, int ignore_index, const int32_t* offsets,
+                       const int32_t* class_map, int nclass, int64_t* counts, int64_t* flags, int accumulate, hipStream_t st);
+int launch_stats_fold_lowres(const float* low, int B, int rows, int row0, int h, int w, const int64_t* target, int16_t* label, float* best,
+                             float* sum, float* tlogit, int first, hipStream_t st);
+size_t stats_finish_ws_bytes(int B, int H, int W);
+int launch_stats_finish(const int16_t* label, const float* best, const float* sum, const float* tlogit, const int64_t* target, int B, int H,
+                        int W, int K, int ignore_index, int64_t* counts, double* nll, int64_t* flags, void* ws, size_t ws_bytes,
+                        hipStream_t st);
 
 // ---- split-precision ("strict") mode (strict.hip): 16-bit tensors as (hi, lo) fp16 planes `plane` elements apart --------------
 int launch_convert_split(const void* in, int in_dtype, void* out, size_t n, size_t plane, hipStream_t st);

@@ -140,6 +140,11 @@ SIGNATURES = {
     "lseg_op_seg_stats_lowres": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lseg_op_episode_stats_ws_bytes": (_sz, [_i, _i, _i]),
     "lseg_op_episode_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "lseg_op_label_stats_plan": (_i, [_i, _vp]),
+    "lseg_op_label_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "lseg_op_stats_fold_lowres": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "lseg_op_stats_finish_ws_bytes": (_sz, [_i, _i, _i]),
+    "lseg_op_stats_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lseg_op_linear_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lseg_op_attention_backward_ws_bytes": (_sz, [_i, _i, _i]),
     "lseg_op_attention_backward_qkv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

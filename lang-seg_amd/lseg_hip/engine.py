@@ -518,6 +518,24 @@ class HipEngine:
         return {"correct": int(c[0]), "labeled": int(c[1]), "area_inter": inter, "area_pred": pred, "area_lab": lab,
                 "area_union": pred + lab - inter, "nll_sum": float(n[0]), "nll_count": int(n[1])}
 
+    def label_stats(self, labels: torch.Tensor, target: torch.Tensor, ignore_index: int = -1, group_sizes=None, class_map=None, nclass=None,
+                    out=None):
+        """pixAcc / IoU counts of a label map this engine produced (forward_labels, shared or ragged) against `target` [B,H,W]
+        (lseg_op_label_stats): DEVICE tensors (counts int64 [2 + 3n], flags int64 [2]), no host synchronisation.  The label set is the
+        engine's current one: n = K for a shared set; with ragged per-image lists (set_tokens(group_sizes=...), or group_sizes given
+        here) labels and targets index each image's own list and n = the number of list entries -- or nclass, when class_map gives every
+        list entry its id in one vocabulary.  out = (counts, flags) of an earlier call: this batch is added to them."""
+        from .metrics import label_stats
+        if not torch.is_tensor(labels) or not torch.is_tensor(target):
+            raise TypeError("label_stats: labels and target must be tensors")
+        if labels.device != self.device or target.device != self.device:
+            raise ValueError(f"label_stats: labels and target must live on {self.device} (no CPU path), got {labels.device} / {target.device}")
+        if group_sizes is None and self._groups is not None:
+            group_sizes = list(self._groups)
+        if group_sizes is None and self._group > 0:
+            group_sizes = [self._group] * labels.shape[0]
+        return label_stats(labels, target, self._K if group_sizes is None else None, ignore_index, group_sizes, class_map, nclass, out)
+
     def episode_stats(self, target: torch.Tensor, ignore: Optional[torch.Tensor] = None, ignore_index: int = -100, class_id=None,
                       meter=None) -> dict:
         """Few-shot episode evaluation of the last forward's two label planes (lseg_episode_stats; inference or train-mode forward):

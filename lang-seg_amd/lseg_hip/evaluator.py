@@ -313,6 +313,23 @@ class BatchedMultiEval(torch.nn.Module):
         """list of [3,h,w] images in, list of forward_labels results out."""
         return [self.forward_labels(img.unsqueeze(0).cuda(), label_set, confidence, panel) for img in inputs]
 
+    def parallel_forward_metrics(self, inputs: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], label_set=None, panel=64) -> List[dict]:
+        """list of [3,h,w] images and of their [h,w] integer masks in, one dict of pixAcc / IoU counts per image out
+        (lseg_hip.metrics.seg_stats_labels of forward_labels' label plane: correct, labeled, area_inter / area_pred / area_lab /
+        area_union over the label set) -- the multi-scale masks of a label set of any size scored without any [K,h,w] tensor.  What
+        SegmentationMetric.update_labels accumulates from the same planes."""
+        from .metrics import seg_stats_labels
+        if len(inputs) != len(targets):
+            raise ValueError(f"parallel_forward_metrics: {len(inputs)} images for {len(targets)} masks")
+        nclass = self.nclass if label_set is None else len(label_set)
+        out = []
+        for img, tgt in zip(inputs, targets):
+            if tuple(tgt.shape) != tuple(img.shape[1:]):
+                raise ValueError(f"parallel_forward_metrics: a mask of {tuple(tgt.shape)} for an image of {tuple(img.shape[1:])}")
+            label = self.forward_labels(img.unsqueeze(0).cuda(), label_set, False, panel)[0]
+            out.append(seg_stats_labels(label.unsqueeze(0), tgt.unsqueeze(0).to(label.device), nclass))
+        return out
+
     @torch.no_grad()
     def forward_labels(self, image: torch.Tensor, label_set=None, confidence=False, panel=64):
         """torch.max(self.forward(image, label_set), 1) for a label set of ANY size without the [K,h,w] score tensor: (label int16 [h,w],
@@ -324,7 +341,9 @@ class BatchedMultiEval(torch.nn.Module):
         lseg_op_eval_merge_labels.  Peak memory follows the panel, not K.  Every evaluator kernel treats planes independently, so a
         plane's fused scores do not depend on the panel that carried it: label / score / label2 / score2 are the same bits for every
         panel size (DESIGN par. 3.8).  Device images only, the lowres arithmetic whatever self.lowres says; the module must offer
-        hold_features and score_held: there is no fallback."""
+        hold_features and score_held: there is no fallback.
+        The `label` plane is what lseg_hip.metrics.SegmentationMetric.update_labels (and parallel_forward_metrics above) score against
+        a mask: pixAcc / IoU of a label set of any size, without the scores."""
         missing = [m for m in ("hold_features", "score_held") if not callable(getattr(self.module, m, None))]
         if missing:
             raise AttributeError(f"BatchedMultiEval.forward_labels needs module.{' / module.'.join(missing)} "

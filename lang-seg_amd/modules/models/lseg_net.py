@@ -285,8 +285,19 @@ class LSeg(BaseModel):
         self._stamp_epoch = getattr(self, "_stamp_epoch", 0) + 1
         return super().load_state_dict(*a, **k)
 
-    def forward_metrics(self, x, target, labelset="", ignore_index=-1):
-        """evaluate(x, target) of the Lightning module without the full-resolution logits (lseg_forward_stats)."""
+    def forward_metrics(self, x, target, labelset="", ignore_index=-1, panel=None):
+        """evaluate(x, target) of the Lightning module without the full-resolution logits (lseg_forward_stats).
+        panel=p: the same dict with device memory set by p instead of K -- the image tower runs once (hold_features), the label set is
+        walked in panels of p rows and the engine is handed ONLY the panel's token rows, so it is sized for p labels (its label planes
+        are max_batch x max_labels x H/2 x W/2) and no [B,K,H/2,W/2] planes exist anywhere; every panel is folded into a four-plane
+        per-pixel state (lseg_op_stats_fold_lowres / lseg_op_stats_finish).  An engine this network already holds for (H, W) that an
+        earlier call grew to more labels keeps its size.  The counts equal forward_metrics()' wherever forward_lowres takes the generic
+        correlation (any out_c but 512, or K > 157); at out_c = 512 and K <= 157 it takes the fused kernel, whose planes differ from
+        the held-feature planes in their last bits (include/lseg_hip.h, lseg_score_features), so a near-tie may fall the other way.
+        Accepted where lseg_forward_features is: one label set shared by the batch, a network in eval mode, the commuted schedule;
+        anything else raises LSEG_ERR_UNSUPPORTED."""
+        if panel is not None:
+            return self._forward_metrics_panels(x, target, labelset, ignore_index, int(panel))
         was = self.training
         self.eval()
         try:
@@ -296,6 +307,77 @@ class LSeg(BaseModel):
             return eng.forward_stats(target, ignore_index)
         finally:
             self.train(was)
+
+    def _forward_metrics_panels(self, x, target, labelset, ignore_index, panel):
+        from lseg_hip import _lib
+        from lseg_hip.evaluator import plan_panels
+        from lseg_hip.metrics import PanelStats
+        if isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset):
+            raise _lib.LSegError(-5, "forward_metrics(panel=): per-image label lists have no held-features route (lseg_forward_features "
+                                     "takes one label set shared by the batch); LSegNet.label_metrics gives their counts")
+        if self.training:
+            raise _lib.LSegError(-5, "forward_metrics(panel=): the held-features route is an inference route; call it under net.eval()")
+        if not x.is_cuda:
+            raise RuntimeError("LSegNet.forward_metrics needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)       # once, for all panels
+        K = text.shape[0]
+        panels = plan_panels(K, panel)
+        B, _, H, W = x.shape
+        with torch.no_grad():
+            stats = PanelStats(target.to(x.device), K, ignore_index)
+            if tuple(stats.target.shape) != (B, H, W):
+                raise ValueError(f"target shape {tuple(stats.target.shape)} != {(B, H, W)}")
+            self.reserve_batch(B, H, W, max(rows for _, rows in panels), x.device)      # one engine build, sized by the panel
+            held = self.hold_features(x)
+            for row0, rows in panels:
+                low = self._score_held_rows(held, text[row0:row0 + rows])
+                stats.fold(low, row0)
+                del low
+            r = stats.finish()
+        flags = r.pop("flags")
+        if flags[2]:
+            raise RuntimeError(f"forward_metrics(panel=): {flags[2]} valid pixels whose target label was in no panel")
+        return r
+
+    def _score_held_rows(self, held, text_rows):
+        """score_held for token rows given directly: the engine's label set becomes exactly these rows (fp32 [B, rows, H/2, W/2]), so
+        an engine sized for one panel serves a label set of any size."""
+        H, W = held.size
+        rows = text_rows.shape[0]
+        eng = self._engine(held.B, H, W, rows, held.feat.device)
+        if held.stamp != eng._stamp:
+            raise RuntimeError("LSegNet.forward_metrics(panel=): the weights changed since hold_features ran")
+        if eng.training:
+            eng.set_train(False)
+        self._set_tokens(eng, text_rows.contiguous(), "rows")
+        self._last_engine = eng
+        return eng.score_features(held.feat, held.scale, 0, rows)
+
+    def label_metrics(self, x, target, labelset="", class_ids=None, nclass=None):
+        """pixAcc / IoU counts of predict_labels(x, labelset) against `target`, without the logits on any route and for any K <= 32767
+        (lseg_forward_labels + lseg_op_label_stats): the dict forward_metrics returns without the nll_* keys -- the streamed route keeps
+        no loss.  labelset is one label set shared by the batch (string / flat list / "" = the network's own), or B per-image lists:
+        `target` then indexes each image's OWN list and the areas have one entry per list entry (image 0's first).  class_ids gives every
+        list entry its id in a vocabulary of nclass classes (B lists shaped like labelset, or one flat list): the areas then have nclass
+        entries, and per-image lists drawn from one vocabulary add up to per-class IoU."""
+        from lseg_hip.metrics import _counts_dict
+        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != (x.shape[0], x.shape[2], x.shape[3]):
+            raise ValueError(f"label_metrics: target must be [B,H,W] = {(x.shape[0], x.shape[2], x.shape[3])}")
+        ragged = isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset)
+        if class_ids is not None:
+            if not ragged:
+                raise ValueError("label_metrics: class_ids belong to per-image label lists")
+            if len(class_ids) > 0 and all(isinstance(c, (list, tuple)) for c in class_ids):
+                if [len(c) for c in class_ids] != [len(ls) for ls in labelset]:
+                    raise ValueError("label_metrics: class_ids must be shaped like labelset")
+                class_ids = [c for cs in class_ids for c in cs]
+        labels = self.predict_labels(x, labelset)
+        eng = self._last_engine
+        counts, flags = eng.label_stats(labels, target.to(x.device), class_map=class_ids, nclass=nclass)
+        c = counts.cpu()
+        r = _counts_dict(c, (c.numel() - 2) // 3)
+        r["flags"] = [int(f) for f in flags.cpu()]
+        return r
 
     def predict_labels(self, x, labelset="", confidence=False):
         """torch.max(self.forward(x, labelset), 1)[1] (what lseg_app.py:350-355 and every caller of the reference do with the logits) as
