@@ -170,13 +170,22 @@ int lseg_get_text_features(lseg_handle h, void* dev_out_f16 /* [K,out_c] fp16 */
 int lseg_set_text_grouping(lseg_handle h, int labels_per_image);
 /* Open-vocabulary batches: every image brings its own label list, of its OWN length (one list per request, lseg_app.py:350-355).
  * host_counts int32 [B] on the host, each in [1, 32767]: image b owns host_counts[b] consecutive rows of the K = sum of counts token rows
- * of lseg_set_text_tokens / lseg_set_text_features (K <= max_labels as always), image 0's rows first.  NULL or B = 0 clears it.  Takes
+ * of lseg_set_text_tokens / lseg_set_text_features, image 0's rows first.  The SUM of the counts (not only each count) must be <=
+ * max_labels: the lists' text rows are concatenated in the max_labels rows of the text workspace, and the training workspaces
+ * (planes, rows, transposed panels) are sized on that bound; a larger sum returns LSEG_ERR_INVALID.  NULL or B = 0 clears it.  Takes
  * effect at the next forward; setting either grouping clears the other (any lseg_set_text_grouping call clears this one).
  * While set, lseg_forward_labels and lseg_forward_labels_conf run ONE batched forward and stream every image against its own rows
  * (csrc/corr_argmax.hip, the ragged instantiations; labels index the image's own list; a list of one label: label2 = -1, score2 = -inf)
  * under the conditions the shared set streams under: commuted schedule, out_c = 512, arch_option 0, no LSEG_CORR_GENERIC.  Everything
- * else -- lseg_forward (logits, uint8 masks), lseg_forward_lowres, train mode, other widths, head blocks, split precision -- returns
- * LSEG_ERR_UNSUPPORTED before any kernel runs; nothing falls back.  A forward whose B differs from the B given here, or whose K differs
+ * else in inference -- lseg_forward (logits, uint8 masks), lseg_forward_lowres, other widths, head blocks, split precision -- returns
+ * LSEG_ERR_UNSUPPORTED before any kernel runs; nothing falls back.
+ * Train mode (lseg_set_train) takes the lists too, on the fused-loss route only: lseg_forward with NO logits output, then lseg_train_loss /
+ * lseg_backward with a target / lseg_backward_scaled.  dev_target int64 [B,H,W] holds, for image b, values in [0, host_counts[b]) or
+ * ignore_index (anything else contributes no loss, as a target >= K does for a shared set); the loss is sum(nll) / sum(valid pixels) over
+ * the batch, each image's softmax over its OWN labels, BatchNorm on the whole batch; lseg_train_loss' counts are {correct, labeled} of
+ * the batch.  Any out_c % 64 == 0 up to 1024.  A logits output, the d(logits) hand-over of lseg_backward, arch_option 1/2 and the
+ * ResNet-101 tower (flags bit 6) return LSEG_ERR_UNSUPPORTED before any kernel runs; lseg_forward_stats
+ * and lseg_episode_stats after such a forward return LSEG_ERR_STATE.  A forward whose B differs from the B given here, or whose K differs
  * from the sum of the counts, returns LSEG_ERR_INVALID.  Afterwards the state is that of a streamed forward: lseg_forward_stats and the
  * "lowres" tap return LSEG_ERR_STATE.  Text cache, external text features, the overflow sentinel and profiling are unchanged. */
 int lseg_set_text_groups(lseg_handle h, const int32_t* host_counts, int B);
@@ -839,6 +848,46 @@ int lseg_op_corr_group_bwd(const void* d_rows, int rows_dtype, int ldk, const vo
  * correlation backward consumes (all ldk columns written, zeros beyond K; ldk % 8 == 0), d_lse_ws fp32 [B*2h*2w] scratch. */
 int lseg_op_upsample_ce_backward_rows(const float* d_low, const int64_t* d_target, int B, int K, int h, int w, int ignore_index,
                                       double* d_nll, float* d_lse_ws, void* d_rows, int ldk, int out_dtype, void* stream);
+/* The ragged forms of the two loss kernels (csrc/ragged_train.hip), for per-image label lists of any lengths: host_counts int32 [B] on the
+ * host, each in [1, 32767]; d_low fp32 = the images' planes CONCATENATED, image b's [k_b,h,w] at prefix[b] * h * w floats (prefix = the
+ * exclusive prefix sum of the counts); d_target int64 [B,2h,2w] with values in [0, k_b) or ignore_index for image b (anything else
+ * contributes no loss); d_prefix int32 [B + 1] device scratch the call fills on the stream.
+ *   ragged_ce_fwd       d_nll double [2] = {sum of -log_softmax[target] over the valid pixels of the batch, their number}, d_counts2
+ *                       int64 [2] = {correct, labeled} of the arg-max through the x2 bilinear (lseg_op_seg_stats_lowres' rule), d_lse
+ *                       fp32 [B*2h*2w] = the per-pixel log-sum-exp over the image's own labels.
+ *   ragged_ce_bwd_rows  runs the forward, then d_rows [B*h*w, ldk] bf16|fp16 = d loss / d low with ONE row pitch for the batch
+ *                       (ldk % 8 == 0, >= the largest count); columns >= k_b of image b's rows are exactly zero.  1 / (valid pixels) is
+ *                       the batch count; d_grad_scale (device float, or NULL = 1) multiplies the gradient.
+ *   ragged_ce_plan      host only, no device: out8 = {labels in all, largest count, up64(largest count) = the engine's row pitch,
+ *                       workgroups of the forward, workgroups of the backward, lanes per workgroup, sum of up64(k_b) = columns of the
+ *                       per-image transposed text panels of the correlation backward, fp32 values of the concatenated planes}. */
+/* The correlation of the ragged training step (csrc/ragged_train.hip), in its two stages.  `stage`: 1 = per-image launches of the generic
+ * GEMM (the fallback and the yardstick; the engine takes it when the environment variable LSEG_CORR_RAGGED_GEMM is set), 2 = ONE launch
+ * for the whole batch, 0 = whichever the engine takes.  C % 64 == 0, C <= 1024.
+ *   corr_ragged_fwd   d_low (concatenated planes, fp32 holding fp16 values) = fp16(d_a16 fp16 [B*hw,C] . d_tnorm fp16 [sum k_b, C]^T) per
+ *                     image against its own rows, fp32 accumulation, one fp16 rounding per logit (the shared set's rounding points).
+ *                     Stage 2: text rows through LDS in panels of 16 labels, pixel rows read once, v_mfma_f32_16x16x32_f16 over
+ *                     ascending k with the generic GEMM's operand roles -- planes bit-equal to stage 1.
+ *   corr_ragged_bwd   d_df [B*hw,C] (df_dtype, 16-bit) = backward of a = scale * f / ||f|| (d_feat fp32 [B*hw,C]) for dA_b = rt(d_rows_b .
+ *                     T_b), with lseg_op_corr_group_bwd's conventions for rows_dtype (fp16: fp16(scale * dA); bf16: T rounded to bf16, the
+ *                     scale un-rounded).  d_rows [B*hw, ldk], ldk % 64 == 0 and >= up64(largest count); columns >= k_b must be zero.
+ *                     Stage 1: per-image transposed text panels [C, up64(k_b)] and dA in scratch allocated on the stream, B GEMMs + one
+ *                     L2-norm backward.  Stage 2: dA in fp32 fused multiply-adds over ascending labels (text rows through LDS in panels
+ *                     of 16), the scale and the L2-norm backward fused as in corr_group_bwd with its row reductions: no dA in memory.
+ *   corr_ragged_plan  host only: out8 = {stage-1 forward launches, stage-1 backward launches, panel columns = sum of up64(k_b),
+ *                     up64(largest count), labels in all, B*hw*C, stage-2 forward workgroups (64 pixel rows each), stage-2 backward
+ *                     workgroups (16 pixel rows each)}. */
+int lseg_op_corr_ragged_plan(const int32_t* host_counts, int B, int hw, int C, int* out8);
+int lseg_op_corr_ragged_fwd(const void* d_a16, const void* d_tnorm, float* d_low, const int32_t* host_counts, int B, int hw, int C, int stage,
+                            void* stream);
+int lseg_op_corr_ragged_bwd(const void* d_rows, int rows_dtype, int ldk, const void* d_tnorm, const float* d_feat, void* d_df, int df_dtype,
+                            const int32_t* host_counts, int B, int hw, int C, float scale, int stage, void* stream);
+int lseg_op_ragged_ce_plan(const int32_t* host_counts, int B, int h, int w, int* out8);
+int lseg_op_ragged_ce_fwd(const float* d_low, const int64_t* d_target, const int32_t* host_counts, int* d_prefix, int B, int h, int w,
+                          int ignore_index, double* d_nll, int64_t* d_counts2, float* d_lse, void* stream);
+int lseg_op_ragged_ce_bwd_rows(const float* d_low, const int64_t* d_target, const int32_t* host_counts, int* d_prefix, int B, int h, int w,
+                               int ignore_index, double* d_nll, float* d_lse_ws, void* d_rows, int ldk, int out_dtype,
+                               const float* d_grad_scale, void* stream);
 /* The same gradient as fp32 PLANES d_planes [B,K,h,w] (the input of the head blocks' backward) and, if d_ksum is not NULL, its per-pixel
  * sum over the labels d_ksum [B,h,w] (what a bottleneck block routes to its arg-max label).  Rounded to fp16 and transposed, d_planes
  * equals the d_rows of lseg_op_upsample_ce_backward_rows. */
@@ -867,6 +916,10 @@ int lseg_op_head_block_backward(const float* d_in, const float* d_out_saved, con
  *                          ResNet-101 tower (flags bit 5): LSEG_ERR_UNSUPPORTED unless flags bit 6 is set; with it the tower's BatchNorms
  *                          run on batch statistics too and the step trains scratch.* only (see flags bit 6).
  *                          arch_option 1/2 (head blocks) needs lseg_config.flags bit 4, else LSEG_ERR_UNSUPPORTED.
+ *                          Ragged per-image label lists (lseg_set_text_groups) may be set before or after: the fused-loss route then
+ *                          runs per image (see lseg_set_text_groups); with them set, arch_option 1/2 and the ResNet-101 tower
+ *                          are refused here and at the forward.  flags bit 3 holds as for a shared set: the ragged loss kernels
+ *                          have no fp32 atomics, the gradients are bit-reproducible.
  *   lseg_bind_grad         where the gradient of parameter `key` is written: fp32, same shape/layout as the bound parameter (the
  *                          caller's .grad tensor, typically a view into a flat bucket).  Unbound parameters get engine-owned buffers
  *                          (lseg_grad_ptr).  Trainable = pretrained.* and scratch.* tensors the forward touches; the CLIP text tower

@@ -651,6 +651,111 @@ int lseg_op_upsample_ce_backward_rows(const float* d_low, const int64_t* d_targe
     return r;
 }
 
+// ragged per-image label sets on the training path (ragged_train.hip)
+int lseg_op_ragged_ce_plan(const int32_t* host_counts, int B, int h, int w, int* out8) { return ragged_ce_plan(host_counts, B, h, w, out8); }
+static int ragged_op_prefix(const char* what, const int32_t* host_counts, int B, int* d_prefix, int ldk, hipStream_t st) {
+    if (B < 1 || B > 65535) return set_error(LSEG_ERR_INVALID, "%s: B=%d", what, B);
+    std::vector<int> prefix((size_t)B + 1, 0);
+    int kmax = 0;
+    int r = ragged_prefix(host_counts, B, prefix.data(), kmax);
+    if (r) return r;
+    if (ldk && ldk < kmax) return set_error(LSEG_ERR_INVALID, "%s: ldk=%d < the largest count %d", what, ldk, kmax);
+    return launch_ragged_offsets(d_prefix, prefix.data(), B + 1, st);
+}
+int lseg_op_ragged_ce_fwd(const float* d_low, const int64_t* d_target, const int32_t* host_counts, int* d_prefix, int B, int h, int w,
+                          int ignore_index, double* d_nll, int64_t* d_counts2, float* d_lse, void* stream) {
+    if (!d_low || !d_target || !host_counts || !d_prefix || !d_nll || !d_counts2 || !d_lse) return set_error(LSEG_ERR_INVALID, "ragged_ce_fwd: NULL pointer");
+    if (h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "ragged_ce_fwd: bad shape");
+    int r = require_device(); if (r) return r;
+    hipStream_t st = (hipStream_t)stream;
+    r = ragged_op_prefix("ragged_ce_fwd", host_counts, B, d_prefix, 0, st);
+    if (r) return r;
+    return launch_ragged_ce_fwd(d_low, d_target, d_prefix, B, h, w, ignore_index, reinterpret_cast<unsigned long long*>(d_counts2), d_nll, d_lse, st);
+}
+int lseg_op_ragged_ce_bwd_rows(const float* d_low, const int64_t* d_target, const int32_t* host_counts, int* d_prefix, int B, int h, int w,
+                               int ignore_index, double* d_nll, float* d_lse_ws, void* d_rows, int ldk, int out_dtype,
+                               const float* d_grad_scale, void* stream) {
+    if (!d_low || !d_target || !host_counts || !d_prefix || !d_nll || !d_lse_ws || !d_rows) return set_error(LSEG_ERR_INVALID, "ragged_ce_bwd_rows: NULL pointer");
+    if (h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "ragged_ce_bwd_rows: bad shape");
+    int dt;
+    if (out_dtype == LSEG_BF16) dt = DT_BF16; else if (out_dtype == LSEG_F16) dt = DT_F16;
+    else return set_error(LSEG_ERR_INVALID, "ragged_ce_bwd_rows: out_dtype %d", out_dtype);
+    if (ldk < 8 || (ldk & 7)) return set_error(LSEG_ERR_INVALID, "ragged_ce_bwd_rows: ldk=%d must be a multiple of 8", ldk);
+    int r = require_device(); if (r) return r;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* counts = nullptr;
+    LSEG_HIP_TRY(hipMallocAsync((void**)&counts, 2 * sizeof(unsigned long long), st));      // (before anything is launched)
+    r = ragged_op_prefix("ragged_ce_bwd_rows", host_counts, B, d_prefix, ldk, st);
+    if (!r) r = launch_ragged_ce_fwd(d_low, d_target, d_prefix, B, h, w, ignore_index, counts, d_nll, d_lse_ws, st);
+    if (!r) r = launch_ragged_ce_bwd_rows(d_low, d_target, d_lse_ws, d_nll, d_rows, d_prefix, B, h, w, ldk, ignore_index, dt, st, d_grad_scale);
+    (void)hipFreeAsync(counts, st);
+    return r;
+}
+
+int lseg_op_corr_ragged_plan(const int32_t* host_counts, int B, int hw, int C, int* out8) { return corr_ragged_plan(host_counts, B, hw, C, out8); }
+// stage: 0 = what the engine takes (stage two unless LSEG_CORR_RAGGED_GEMM is set), 1 = the per-image GEMMs, 2 = the one-launch kernels
+static int ragged_stage(int stage, int* out) {
+    if (stage < 0 || stage > 2) return set_error(LSEG_ERR_INVALID, "ragged correlation: stage %d (0 engine's, 1 per-image GEMM, 2 one launch)", stage);
+    *out = stage ? stage : (corr_ragged_use_gemm() ? 1 : 2);
+    return 0;
+}
+int lseg_op_corr_ragged_fwd(const void* d_a16, const void* d_tnorm, float* d_low, const int32_t* host_counts, int B, int hw, int C, int stage,
+                            void* stream) {
+    if (!d_a16 || !d_tnorm || !d_low) return set_error(LSEG_ERR_INVALID, "corr_ragged_fwd: NULL pointer");
+    int plan[8], sg;
+    int r = corr_ragged_plan(host_counts, B, hw, C, plan); if (r) return r;
+    if ((r = ragged_stage(stage, &sg))) return r;
+    r = require_device(); if (r) return r;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> prefix((size_t)B + 1, 0);
+    int kmax = 0;
+    if ((r = ragged_prefix(host_counts, B, prefix.data(), kmax))) return r;
+    if (sg == 1) return launch_corr_ragged_fwd(d_a16, d_tnorm, d_low, prefix.data(), B, hw, C, st);
+    int* dp = nullptr;
+    LSEG_HIP_TRY(hipMallocAsync((void**)&dp, ((size_t)B + 1) * sizeof(int), st));
+    r = launch_ragged_offsets(dp, prefix.data(), B + 1, st);
+    if (!r) r = launch_corr_ragged_fwd_fused(d_a16, d_tnorm, d_low, dp, B, hw, C, st);
+    (void)hipFreeAsync(dp, st);
+    return r;
+}
+int lseg_op_corr_ragged_bwd(const void* d_rows, int rows_dtype, int ldk, const void* d_tnorm, const float* d_feat, void* d_df, int df_dtype,
+                            const int32_t* host_counts, int B, int hw, int C, float scale, int stage, void* stream) {
+    if (!d_rows || !d_tnorm || !d_feat || !d_df) return set_error(LSEG_ERR_INVALID, "corr_ragged_bwd: NULL pointer");
+    int plan[8], rd, dd, sg;
+    int r = corr_ragged_plan(host_counts, B, hw, C, plan); if (r) return r;
+    if ((r = op_dt(rows_dtype, &rd)) || (r = op_dt(df_dtype, &dd))) return r;
+    if ((r = ragged_stage(stage, &sg))) return r;
+    if (rd == DT_F32 || dd == DT_F32) return set_error(LSEG_ERR_INVALID, "corr_ragged_bwd: 16-bit rows and df");
+    if (ldk < plan[3] || ldk % 64 != 0) return set_error(LSEG_ERR_INVALID, "corr_ragged_bwd: ldk=%d must be a multiple of 64 and >= %d", ldk, plan[3]);
+    r = require_device(); if (r) return r;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> prefix((size_t)B + 1, 0);
+    int kmax = 0;
+    if ((r = ragged_prefix(host_counts, B, prefix.data(), kmax))) return r;
+    if (sg == 2) {
+        int* dp = nullptr;
+        LSEG_HIP_TRY(hipMallocAsync((void**)&dp, ((size_t)B + 1) * sizeof(int), st));
+        r = launch_ragged_offsets(dp, prefix.data(), B + 1, st);
+        if (!r) r = launch_corr_ragged_bwd_fused(d_rows, rd, ldk, d_tnorm, d_feat, d_df, dd, dp, kmax, B, hw, C, scale, st);
+        (void)hipFreeAsync(dp, st);
+        return r;
+    }
+    // stage one; scratch on the stream: the bf16 rounding of the text rows (bf16 rows only), the transposed panels, dA, a bias of zeros
+    const size_t n_t = (size_t)plan[4] * C, n_p = (size_t)plan[2] * C, n_da = (size_t)plan[5];
+    char* ws = nullptr;
+    const size_t bytes = (n_t + n_p + n_da) * 2 + (size_t)C * sizeof(float);
+    LSEG_HIP_TRY(hipMallocAsync((void**)&ws, bytes, st));
+    uint16_t *t16 = (uint16_t*)ws, *pan = t16 + n_t, *da = pan + n_p;
+    float* zb = (float*)(da + n_da);
+    r = hipMemsetAsync(zb, 0, (size_t)C * sizeof(float), st) == hipSuccess ? 0 : set_error(LSEG_ERR_HIP, "corr_ragged_bwd: memset");
+    const void* tsrc = d_tnorm;
+    if (!r && rd == DT_BF16) { r = launch_convert(d_tnorm, DT_F16, t16, DT_BF16, n_t, st); tsrc = t16; }
+    if (!r) r = launch_corr_ragged_panels(tsrc, pan, prefix.data(), B, C, st);
+    if (!r) r = launch_corr_ragged_bwd(d_rows, rd, ldk, pan, zb, d_feat, da, d_df, dd, prefix.data(), B, hw, C, scale, st);
+    (void)hipFreeAsync(ws, st);
+    return r;
+}
+
 int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int height, int width, int crop, int stride, int h_grids, int w_grids,
                             int flip, const float* host_pad3, void* stream) {
     int r = require_device(); if (r) return r;

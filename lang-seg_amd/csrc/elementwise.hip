@@ -2527,7 +2527,7 @@ int launch_upsample2x_planes_backward_planes(const float* dout, float* planes, i
     return 0;
 }
 // every output row Y whose bilinear footprint touches low row y lies in [2y-1, 2y+2] (same fp32 arithmetic as the kernels)
-static bool x2_footprint_is_4(int H) {
+bool x2_footprint_is_4(int H) {
     const int Ho = 2 * H;
     const float ry = (float)(H - 1) / (float)(Ho - 1);
     for (int yo = 0; yo < Ho; ++yo) {

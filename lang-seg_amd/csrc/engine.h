@@ -179,6 +179,7 @@ private:
     int text_fork(hipStream_t st);
     int text_join(hipStream_t st);
     int check_grouping(int B);
+    int check_ragged_train();                        // ... and of a train-mode forward / lseg_set_train while they are set
     int check_ragged(int B, bool labels_only);       // the refusals of a forward while ragged groups are set
     int check_held(const char* what);                // the refusals of lseg_forward_features / lseg_score_features: where corr_low does not hold
     std::vector<int32_t> groups_;
@@ -302,6 +303,11 @@ private:
     const int64_t* loss_target_ = nullptr; int loss_ignore_ = 0;      // train_loss() already ran seg_stats for this forward and this target
     int train_B_ = 0;
     int train_G_ = 0;             // labels per image of the last train-mode forward (0: one label set shared by the batch)
+    // ragged per-image label sets of the last train-mode forward (empty: none): host prefix sums [B + 1] (d_goff_ holds them on the
+    // device), the largest count, and the per-image transposed text panels [out_c, up64(k_b)] of the correlation backward, concatenated
+    std::vector<int> train_rag_;
+    int train_rag_kmax_ = 0;
+    uint16_t* tnT_rag_ = nullptr;
     std::vector<BlockSave> sv_;
     float* xlast_ = nullptr;               // output of the last block (= xin of a virtual block `depth`)
     LevelSave lv_[4];

@@ -697,7 +697,7 @@ int Engine::check_ragged(int B, bool labels_only) {
     long total = 0;
     for (int k : groups_) total += k;
     if (total != K_) return set_error(LSEG_ERR_INVALID, "ragged label sets: %d token rows != %ld labels over the %d images", K_, total, B);
-    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets are an inference feature (train mode is on)");
+    if (train_mode) return check_ragged_train();      // the fused-loss route (train.hip); forward_train refuses a logits output
     if (!labels_only)
         return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no logits: only lseg_forward_labels / lseg_forward_labels_conf run with them");
     const lseg_config& c = cfg;
@@ -705,6 +705,19 @@ int Engine::check_ragged(int B, bool labels_only) {
     if (!commuted || getenv("LSEG_CORR_FULLRES") || (lw_[0] % 2) != 0 || getenv("LSEG_CORR_GENERIC") || c.arch_option != 0 || c.out_c != 512)
         return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets need the streamed kernel: the commuted schedule (no debug taps, no split precision), "
                                                "out_c 512 (is %d), arch_option 0 (is %d), no LSEG_CORR_GENERIC / LSEG_CORR_FULLRES", c.out_c, c.arch_option);
+    return 0;
+}
+
+// ragged label sets in train mode: the fused-loss route on the plain head only.  Refused before any kernel runs: the arch_option 1/2 head
+// blocks (their planes are rectangular) and the ResNet-101 decoder-training mode (never run with ragged sets: refused rather than left
+// untested).  Deterministic reductions (flags bit 3) need nothing new: the ragged loss kernels hold no fp32 atomic -- the counts are
+// integers and the gradient reads only the valid-pixel count, so the rows are bit-reproducible; the loss VALUE is a double atomic sum,
+// order-dependent in its last bits exactly as seg_stats_kernel's is
+int Engine::check_ragged_train() {
+    if (cfg.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode need arch_option 0 (is %d): the head blocks "
+                                                                      "work on rectangular [B,K,h,w] planes", cfg.arch_option);
+    if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode are not implemented for the ResNet-101 tower (decoder training)");
+    if (!corr_ragged_supported(cfg.out_c)) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode need out_c %% 64 == 0 and <= 1024 (is %d)", cfg.out_c);
     return 0;
 }
 
@@ -1304,6 +1317,7 @@ int Engine::materialize_low(hipStream_t st) {
 int Engine::forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st) {
     if (labels_only_) return set_error(LSEG_ERR_STATE, "the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
     if (!last_low_ || last_B_ < 1) return set_error(LSEG_ERR_STATE, "no forward has run");
+    if (!train_rag_.empty()) return set_error(LSEG_ERR_STATE, "the last forward was a train-mode forward with ragged label sets: its planes are not rectangular (lseg_train_loss reads them)");
     if (!target || !counts || !nll) return set_error(LSEG_ERR_INVALID, "forward_stats: NULL pointer");
     LSEG_HIP_TRY(hipSetDevice(device));
     TRY(materialize_low(st));
@@ -1321,6 +1335,7 @@ int Engine::episode_stats(const int64_t* target, const uint8_t* ignore, int igno
     int B = 0, kout = 0;
     if (train_mode) {
         if (!train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: no forward has run (train mode is on: it needs a train-mode lseg_forward)");
+        if (!train_rag_.empty()) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last train-mode forward had ragged label sets");
         low = train_out_; B = train_B_; kout = train_G_ > 0 ? train_G_ : K_;
     } else {
         if (labels_only_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
@@ -1377,6 +1392,7 @@ int Engine::get_intermediate(const char* name, float* out, size_t cap, size_t* n
         TRY(materialize_low(st));
         const int hw1 = 4 * lh_[0] * lw_[0];
         need_n = (size_t)B * (group_k > 0 ? group_k : K_) * hw1;
+        if (!train_rag_.empty()) need_n = (size_t)K_ * hw1;      // ragged training: the images' planes concatenated, K_ in all
         if (cap < need_n) return set_error(LSEG_ERR_INVALID, "buffer too small: %zu < %zu", cap, need_n);
         LSEG_HIP_TRY(hipMemcpyAsync(out, low_, need_n * sizeof(float), hipMemcpyDeviceToDevice, st));
     } else {

@@ -84,6 +84,31 @@ int launch_corr_group_fwd(const void* a16, const void* tnorm, float* low, int B,
 // df [B*hw, C] = L2-norm/scale backward (feat fp32) of dA = sum_k rows[:, k] T[b*G + k] -- the shared path's GEMM + l2norm_scale_backward
 int launch_corr_group_bwd(const void* rows, int rows_dtype, int ldk, const void* tnorm, const float* feat, void* df, int df_dtype, int B, int hw,
                           int G, int C, float scale, hipStream_t st);
+// ragged_train.hip -- the loss of the training step for ragged per-image label sets: planes of image b at prefix[b] * h * w of `low`
+// prefix [B + 1] (host) = exclusive prefix sum of the validated counts (each in [1, 32767]); kmax = the largest count
+int ragged_prefix(const int32_t* host_counts, int B, int* prefix, int& kmax);
+// launch geometry without a device: out8 = {labels in all, largest count, drows pitch up64(largest), forward workgroups, backward
+// workgroups, lanes per workgroup, columns of the per-image transposed text panels (sum of up64(k_b)), fp32 values of the planes}
+int ragged_ce_plan(const int32_t* host_counts, int B, int h, int w, int* out8);
+// the 4-tap footprint of the x2 bilinear's transpose both fused CE backward kernels assume (elementwise.hip), checked per geometry
+bool x2_footprint_is_4(int H);
+// the per-image correlation of the ragged step on the generic GEMM (see ragged_train.hip): forward planes, transposed text panels, dA + L2-norm backward
+bool corr_ragged_supported(int C);
+int corr_ragged_plan(const int32_t* host_counts, int B, int hw, int C, int* out8);
+int launch_corr_ragged_fwd(const void* a16, const void* tnorm, float* low, const int* host_prefix, int B, int hw, int C, hipStream_t st);
+// stage two: one launch for the batch each way (d_prefix on the device); LSEG_CORR_RAGGED_GEMM selects stage one instead
+bool corr_ragged_use_gemm();
+int launch_corr_ragged_fwd_fused(const void* a16, const void* tnorm, float* low, const int* d_prefix, int B, int hw, int C, hipStream_t st);
+int launch_corr_ragged_bwd_fused(const void* rows, int rows_dtype, int ldk, const void* tnorm, const float* feat, void* df, int df_dtype,
+                                 const int* d_prefix, int kmax, int B, int hw, int C, float scale, hipStream_t st);
+int launch_corr_ragged_panels(const void* tsrc, void* tnT, const int* host_prefix, int B, int C, hipStream_t st);
+int launch_corr_ragged_bwd(const void* rows, int rows_dtype, int ldk, const void* tnT, const float* zero_bias, const float* feat, void* da,
+                           void* df, int df_dtype, const int* host_prefix, int B, int hw, int C, float scale, hipStream_t st);
+int launch_ragged_offsets(int* d_prefix, const int* host_prefix, int n, hipStream_t st);
+int launch_ragged_ce_fwd(const float* low, const int64_t* target, const int* d_prefix, int B, int h, int w, int ignore_index,
+                         unsigned long long* counts2, double* nll, float* lse_out, hipStream_t st);
+int launch_ragged_ce_bwd_rows(const float* low, const int64_t* target, const float* lse, const double* nll, void* rows, const int* d_prefix,
+                              int B, int h, int w, int ldk, int ignore_index, int dtype, hipStream_t st, const float* gscale = nullptr);
 int launch_l2norm_scale_backward(const void* da, int da_dtype, const float* x, void* dx, int dx_dtype, int M, int C, float scale, hipStream_t st);
 int launch_gelu_backward(const void* dy, const void* pre, void* dx, size_t n, int dtype, hipStream_t st, int quick = 0);
 int launch_upsample2x_nhwc_backward(const void* dout, void* din, int B, int H, int W, int C, int dtype, hipStream_t st);

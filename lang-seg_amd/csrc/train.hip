@@ -45,7 +45,7 @@ static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 int Engine::set_train(bool on) {
     if (on) {
-        if (ragged()) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets (lseg_set_text_groups) are an inference feature: clear them before lseg_set_train");
+        if (ragged()) TRY(check_ragged_train());
         // flags bit 6 opts in to training the decoder above the tower (train-mode BatchNorm in the tower, no bottleneck backward)
         if (resnet_ && !rn_train_)
             return set_error(LSEG_ERR_UNSUPPORTED, "the ResNet-101 image tower is inference only (no train-mode BatchNorm / bottleneck backward)");
@@ -59,6 +59,7 @@ int Engine::set_train(bool on) {
     }
     train_mode = on;
     train_fwd_valid_ = false;
+    if (!train_rag_.empty()) { train_rag_.clear(); last_low_ = nullptr; }     // the concatenated planes of a ragged forward are no rectangular [B,K,h,w]
     return 0;
 }
 
@@ -237,6 +238,8 @@ int Engine::train_alloc() {
     TALLOC(lse_px_, float, B * 4 * hw1);
     TALLOC(drows_, uint16_t, B * hw1 * Kp); TALLOC(da_, uint16_t, B * hw1 * c.out_c); TALLOC(df_, uint16_t, B * hw1 * c.out_c);
     TALLOC(tnT_, uint16_t, (size_t)c.out_c * Kp); TALLOC(tn16_, uint16_t, (size_t)c.max_labels * c.out_c);
+    // ragged per-image label sets: one transposed text panel [out_c, up64(k_b)] per image, sum of k_b <= max_labels
+    TALLOC(tnT_rag_, uint16_t, (size_t)c.out_c * (Kp + 64 * B));
     TALLOC(counts_, unsigned long long, 2 + 3 * (size_t)c.max_labels); TALLOC(nll_, double, 2);
     if (c.arch_option == 1 || c.arch_option == 2) {          // head blocks (flags bit 4, checked by set_train): their saved outputs
         hb_n_ = std::max(c.block_depth - 1, 0) + 1;           // lseg_net.py:198-201: block_depth 0 and 1 both mean one block
@@ -474,6 +477,10 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     const int D = c.dim, H = c.heads, F = c.features, M = B * ntok_;
     if (!train_alloc_) return set_error(LSEG_ERR_STATE, "train mode was not enabled (lseg_set_train)");
     TRY(check_grouping(B));
+    // ragged per-image label sets: only the fused loss reads their planes (check_ragged refused everything else before this point)
+    const bool rag = ragged();
+    if (rag && logits) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits in train mode either: pass no logits output "
+                                                              "and take the loss from lseg_train_loss / lseg_backward with a target");
     if (group_k > 0 && !corr_group_supported(group_k, c.out_c))
         return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
                          CORR_GROUP_MAX, group_k);
@@ -530,7 +537,29 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     TRY(launch_gemm(g, img_dt_, st));
     TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale(), st));
     const int kout = group_k > 0 ? group_k : K_;             // label planes per image
-    if (group_k > 0) {
+    train_rag_.clear();
+    if (rag) {
+        // image b against its own groups_[b] text rows, on the generic GEMM with the shared path's rounding points (round_mid = 1: one fp16
+        // rounding per logit): the planes are concatenated in low_, image b's at prefix[b] * hw1.  The dgrad operands are per-image
+        // transposed text panels padded to the GEMM's K-step, zero in the pad columns.
+        std::vector<int> prefix((size_t)B + 1, 0);
+        int kmax = 0;
+        TRY(ragged_prefix(groups_.data(), B, prefix.data(), kmax));
+        TRY(launch_ragged_offsets(d_goff_, prefix.data(), B + 1, st));
+        if (corr_ragged_use_gemm()) {                     // stage one (LSEG_CORR_RAGGED_GEMM): per-image GEMMs, transposed panels for the dgrad
+            TRY(launch_corr_ragged_fwd(a16_, tnorm_, low_, prefix.data(), B, hw1, c.out_c, st));
+            const uint16_t* tsrc = tnorm_;
+            if (cfg.flags & 2) {
+                TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
+                tsrc = tn16_;
+            }
+            TRY(launch_corr_ragged_panels(tsrc, tnT_rag_, prefix.data(), B, c.out_c, st));
+        } else {                                          // stage two: one launch, planes bit-equal to stage one; the backward reads tnorm_ itself
+            TRY(launch_corr_ragged_fwd_fused(a16_, tnorm_, low_, d_goff_, B, hw1, c.out_c, st));
+        }
+        train_rag_ = prefix;
+        train_rag_kmax_ = kmax;
+    } else if (group_k > 0) {
         // per-image correlation (corr_group.hip): the same rounding points as the GEMM below; the grouped backward reads tnorm_ itself,
         // so there is no transposed dgrad operand to make
         TRY(launch_corr_group_fwd(a16_, tnorm_, low_, B, hw1, group_k, c.out_c, st));
@@ -852,7 +881,8 @@ int Engine::train_loss(const int64_t* target, int ignore_index, double* dev_loss
     LSEG_HIP_TRY(hipSetDevice(device));
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
     const int kout = train_G_ > 0 ? train_G_ : K_;
-    TRY(launch_seg_stats_ex(train_out_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
+    if (!train_rag_.empty()) TRY(launch_ragged_ce_fwd(low_, target, d_goff_, train_B_, h1, w1, ignore_index, counts_, nll_, lse_px_, st));
+    else TRY(launch_seg_stats_ex(train_out_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
     if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (dev_counts2) LSEG_HIP_TRY(hipMemcpyAsync(dev_counts2, counts_, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     loss_target_ = target; loss_ignore_ = ignore_index;
@@ -908,7 +938,9 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     const int B = train_B_, D = c.dim, F = c.features, M = B * ntok_, Mr = B * np_;
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp1 = B * hw1;
     // label planes per image and the row pitch of d(low): per-image sets (G <= 8) hand the grouped kernel one 16-byte row per pixel
-    const int G = train_G_, kout = G > 0 ? G : K_, Kp = G > 0 ? 8 : (int)up64(K_);
+    const bool rag = !train_rag_.empty();
+    if (rag && dlogits) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits: lseg_backward takes a target, not d(logits)");
+    const int G = train_G_, kout = G > 0 ? G : K_, Kp = rag ? (int)up64(train_rag_kmax_) : G > 0 ? 8 : (int)up64(K_);
     if (!acc) TRY(zero_begin(zero_bwd_, st));
     // The reference back-propagates through `logit_scale * image_features.half() @ text_features.t()` (lseg_net.py:194) in HALF precision:
     // d(logits) is cast to fp16 (the `.float()` of :196 under autograd), dA = d(logits) @ text_features is an fp16 tensor (fp32
@@ -918,7 +950,12 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
     // for the un-rounded gradient.
     const int hdt = (cfg.flags & 2) ? img_dt_ : DT_F16;
     // ---- loss + x2 upsample^T: the correlation's dY rows ---------------------------------------------------------------------
-    if (hb_n_ > 0) TRY(head_blocks_backward(dlogits, target, ignore_index, acc, dev_loss2, st, dev_grad_scale, hdt, Kp));
+    if (rag) {                // each image over its own planes; one row pitch for the batch, columns past the image's count written as zeros
+        if (!(loss_target_ == target && loss_ignore_ == ignore_index))
+            TRY(launch_ragged_ce_fwd(low_, target, d_goff_, B, h1, w1, ignore_index, counts_, nll_, lse_px_, st));
+        TRY(launch_ragged_ce_bwd_rows(low_, target, lse_px_, nll_, drows_, d_goff_, B, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
+        if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else if (hb_n_ > 0) TRY(head_blocks_backward(dlogits, target, ignore_index, acc, dev_loss2, st, dev_grad_scale, hdt, Kp));
     else if (!dlogits) {      // CrossEntropyLoss(ignore_index) on output_conv(low): one pass for the loss and the per-pixel log-sum-exp, one for the rows
         if (!(loss_target_ == target && loss_ignore_ == ignore_index))      // else: lseg_train_loss left nll_ / lse_px_ of this forward and target
             TRY(launch_seg_stats_ex(train_out_, target, B, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
@@ -929,7 +966,14 @@ int Engine::backward(const float* dlogits, const int64_t* target, int ignore_ind
         TRY(launch_upsample2x_planes_backward_rows(dlogits, drows_, B, kout, h1, w1, Kp, hdt, st));
     }
     // ---- head: correlation, L2-norm, head1 -------------------------------------------------------------------------------------
-    if (G > 0) {
+    if (rag) {
+        // dA_b = d(logits)_b . T_b per image on its transposed text panel (K = up64(k_b): the columns beyond are zeros and are not read),
+        // then the scale and L2-norm backward over all rows at once
+        if (corr_ragged_use_gemm())
+            TRY(launch_corr_ragged_bwd(drows_, hdt, Kp, tnT_rag_, zeros_, feat_, da_, df_, img_dt_, train_rag_.data(), B, hw1, c.out_c, logit_scale(), st));
+        else
+            TRY(launch_corr_ragged_bwd_fused(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, d_goff_, train_rag_kmax_, B, hw1, c.out_c, logit_scale(), st));
+    } else if (G > 0) {
         // per-image label sets: dA from the image's own G text rows, the scale and the L2-norm backward in one pass (corr_group.hip)
         TRY(launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, G, c.out_c, logit_scale(), st));
     } else {

@@ -166,6 +166,12 @@ SIGNATURES = {
     "lseg_op_l2norm_scale_backward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "lseg_op_corr_group_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_corr_group_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "lseg_op_ragged_ce_plan": (_i, [_vp, _i, _i, _i, _vp]),
+    "lseg_op_ragged_ce_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "lseg_op_ragged_ce_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "lseg_op_corr_ragged_plan": (_i, [_vp, _i, _i, _i, _vp]),
+    "lseg_op_corr_ragged_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_corr_ragged_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _i, _vp]),
     "lseg_op_upsample_ce_backward_planes": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lseg_op_head_block_backward_ws": (_sz, [_i, _i, _i, _i, _i]),
     "lseg_op_head_block_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, C.c_int64, _vp]),

@@ -73,6 +73,33 @@ def to_c_config(cfg: LSegConfig, img_h: int, img_w: int, max_batch: int, max_lab
     return c
 
 
+def check_group_sizes(group_sizes, max_labels: int) -> List[int]:
+    """The host-side checks of ragged per-image label lists (set_tokens(group_sizes=...), LSegNet.forward_loss with a list of lists):
+    at least one list, every list non-empty, and no more labels than the engine was planned for -- each list and their sum, since the
+    lists' text rows are concatenated in the max_labels rows of the text workspace.  Returns the sizes as ints.
+    (These are what lseg_set_text_groups refuses as LSEG_ERR_INVALID; since the training step takes the lists they are refused here, as a
+    ValueError before the C call, on the inference path of set_tokens / set_text_features as well.)"""
+    sizes = [int(k) for k in group_sizes]
+    if not sizes:
+        raise ValueError("group_sizes is empty: ragged per-image label sets need one list per image")
+    for b, k in enumerate(sizes):
+        if k < 1:
+            raise ValueError(f"group_sizes {sizes}: image {b} has {k} labels; every image needs >= 1 label")
+        if k > max_labels:
+            raise ValueError(f"group_sizes {sizes}: image {b} has {k} labels > max_labels={max_labels}")
+    if sum(sizes) > max_labels:
+        raise ValueError(f"group_sizes {sizes}: {sum(sizes)} labels in all > max_labels={max_labels}")
+    return sizes
+
+
+def check_ragged_target(target, B: int, H: int, W: int):
+    """The target of the ragged training step: int64 [B, H, W] (image b's values index its own list)."""
+    if not torch.is_tensor(target) or target.dtype != torch.int64:
+        raise ValueError(f"ragged training target must be an int64 tensor, got {getattr(target, 'dtype', type(target))}")
+    if tuple(target.shape) != (B, H, W):
+        raise ValueError(f"ragged training target must be [B,H,W] = {(B, H, W)}, got {tuple(target.shape)}")
+
+
 class HipEngine:
     """One engine = one (backbone, H, W, max_batch, max_labels) plan on one GPU."""
 
@@ -155,7 +182,9 @@ class HipEngine:
         """tokens int64 [K, ctx].  labels_per_image = k > 0 (LSegNetZS, lseg_net_zs.py:177-214): the K = B*k rows are
         per-image label sets, image b is correlated with rows [b*k, (b+1)*k) and forward returns [B, k, H, W].
         group_sizes = [k_0, .., k_{B-1}] (lseg_set_text_groups): ragged per-image label sets -- image b owns k_b consecutive rows of the
-        K = sum(k_b); forward_labels / forward_labels_conf then return labels indexing each image's own list, every other forward raises."""
+        K = sum(k_b); forward_labels / forward_labels_conf then return labels indexing each image's own list, every other inference forward
+        raises.  While training, forward(x, want_logits=False) + train_loss / backward(target=...) take them: the target of image b holds
+        values in [0, k_b) or ignore_index (the fused-loss route; there are no [B,K,H,W] logits and no d(logits) hand-over)."""
         if group_sizes is not None and labels_per_image:
             raise ValueError("labels_per_image and group_sizes are two different groupings: give one")
         tok = tokens.detach().to("cpu", torch.int64).contiguous()
@@ -172,8 +201,8 @@ class HipEngine:
         if group_sizes is None:
             _lib.check(self.lib.lseg_set_text_groups(self._h, None, 0))
             return
-        sizes = [int(k) for k in group_sizes]
-        if not sizes or sum(sizes) != self._K:
+        sizes = check_group_sizes(group_sizes, self.max_labels)
+        if sum(sizes) != self._K:
             raise ValueError(f"group_sizes {sizes} do not add up to the {self._K} text rows")
         _lib.check(self.lib.lseg_set_text_groups(self._h, (C.c_int32 * len(sizes))(*sizes), len(sizes)))
         self._groups = sizes
@@ -225,6 +254,9 @@ class HipEngine:
     def _refuse_ragged(self, x: torch.Tensor):
         """ragged label sets have no logits: the C entry refuses before any kernel runs (LSEG_ERR_UNSUPPORTED), with its own message"""
         if self._groups is not None:
+            if self.training:
+                raise _lib.LSegError(-5, "ragged per-image label sets have no [B,K,H,W] logits: in train mode call forward(x, want_logits=False) "
+                                         "and take the loss from train_loss / backward(target=...)")
             _lib.check(self.lib.lseg_forward(self._h, C.c_void_p(x.data_ptr()), x.shape[0], None, None, C.c_void_p(_stream_ptr(self.device))))
             raise RuntimeError("lseg_forward accepted ragged label sets")
 
@@ -305,7 +337,8 @@ class HipEngine:
 
     def forward(self, x: torch.Tensor, want_logits: bool = True, want_argmax: bool = False):
         x = self._check_input(x)
-        self._refuse_ragged(x)
+        if not (self._groups is not None and self.training and not want_logits and not want_argmax):    # the ragged training step: loss only
+            self._refuse_ragged(x)
         B, Cc, H, W = x.shape
         Kout = self._group if self._group > 0 else self._K
         if want_argmax and not want_logits and Kout > 256:
@@ -387,6 +420,8 @@ class HipEngine:
         no host sync); or dlogits fp32 [B,K,H,W] (autograd hand-over) -> None.  Gradients land in self.grads / grad_buckets.
         grad_scale (fp32 0-dim device tensor, target form only): d(loss) of an autograd caller, read by the kernel (lseg_backward_scaled)."""
         st = C.c_void_p(_stream_ptr(self.device))
+        if target is not None and self._groups is not None:
+            check_ragged_target(target, len(self._groups), self.img_h, self.img_w)
         if dlogits is not None:
             dl = dlogits.contiguous()
             assert dl.dtype == torch.float32 and dl.device == self.device
@@ -410,6 +445,8 @@ class HipEngine:
     def train_loss(self, target: torch.Tensor, ignore_index: int = -1, want_counts: bool = False):
         """Value of the criterion on the last train-mode forward without the backward (lseg_train_loss): the mean cross-entropy as a
         0-dim fp32 device tensor (no host sync) and, optionally, int64[2] = {correct, labeled} of the arg-max mask."""
+        if self._groups is not None:
+            check_ragged_target(target, len(self._groups), self.img_h, self.img_w)
         t = target.contiguous()
         assert t.dtype == torch.int64 and t.device == self.device
         self._loss_target = t                                     # the engine remembers the pointer for the following backward

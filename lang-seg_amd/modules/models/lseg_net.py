@@ -505,13 +505,18 @@ class LSeg(BaseModel):
             p.grad = eng.grads[k]
         return tuple(None for _ in keys)
 
-    def _train_inputs(self, x, labelset):
+    @staticmethod
+    def _is_label_lists(labelset):
+        """B per-image label lists ([["cat", "grass"], ["road", "car", "sky"], ..]) rather than one label set shared by the batch"""
+        return isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset)
+
+    def _train_inputs(self, x, labelset, groups=None):
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet needs CUDA/HIP tensors (no CPU path, like the reference: lseg_vit.py:224)")
         B, _, H, W = x.shape
         eng = self._train_engine(B, H, W, text.shape[0], x.device)
-        self._set_tokens(eng, text, labelset)
+        self._set_tokens(eng, text, labelset, groups)
         if eng._nbt:
             torch._foreach_add_(eng._nbt, 1)             # nn.BatchNorm2d.num_batches_tracked (state-dict parity; momentum is fixed at 0.1)
         self.invalidate_engines(except_=eng)             # train-mode BatchNorm moves the running statistics through raw pointers
@@ -520,10 +525,27 @@ class LSeg(BaseModel):
     def forward_loss(self, x, target, labelset="", ignore_index=-1):
         """`criterion(self(x), target)` for the reference's criterion (mean cross-entropy over pixels != ignore_index) as ONE autograd
         node: the value, and under `loss.backward()` the gradients, without the [B,K,H,W] logits.  Also leaves the pixel-accuracy
-        counts {correct, labeled} of this batch in `self._last_train_counts` (int64[2], device)."""
+        counts {correct, labeled} of this batch in `self._last_train_counts` (int64[2], device).
+        labelset may also be a list of B label lists, one per image and of any lengths (the form predict_labels takes): image b is
+        scored against its OWN list, `target[b]` holds indices into that list (or ignore_index), the softmax of every pixel runs over its
+        image's labels only, the loss is sum(nll) / sum(valid pixels) over the batch and BatchNorm sees the whole batch -- what the
+        reference computes when every image is given its own label list under one train-mode forward of the image tower."""
         if not (self.training and torch.is_grad_enabled()):
             raise RuntimeError("forward_loss is the training-step path: call it under net.train() with grad enabled")
-        eng, keys, params = self._train_inputs(x, labelset)
+        groups = None
+        if self._is_label_lists(labelset):
+            from lseg_hip.engine import check_ragged_target
+            groups = [len(ls) for ls in labelset]
+            if len(groups) != x.shape[0]:
+                raise ValueError(f"per-image label lists: {len(groups)} lists (sizes {groups}) for a batch of {x.shape[0]}")
+            if min(groups) < 1:
+                raise ValueError(f"per-image label lists: sizes {groups}; every image needs >= 1 label")
+            cap = getattr(self, "max_labels", None)
+            if cap is not None and (max(groups) > cap or sum(groups) > cap):
+                raise ValueError(f"per-image label lists: sizes {groups} exceed max_labels={cap}")
+            check_ragged_target(target, x.shape[0], x.shape[2], x.shape[3])
+            labelset = [lab for ls in labelset for lab in ls]               # encoded once per occurrence, image 0's labels first
+        eng, keys, params = self._train_inputs(x, labelset, groups)
         return _EngineLossFn.apply(x.float(), target, self, eng, keys, int(ignore_index), *params)
 
     def _range_guard(self, eng, device):
@@ -567,6 +589,11 @@ class LSeg(BaseModel):
         return False
 
     def forward(self, x, labelset="", _want_logits=True):
+        if self._is_label_lists(labelset):
+            if self.training:
+                raise ValueError("LSegNet.forward: per-image label lists have no [B,K,H,W] logits; in train() mode use "
+                                 "forward_loss(x, target, labelset), which takes the loss without them")
+            raise ValueError("LSegNet.forward: per-image label lists have no [B,K,H,W] logits; use predict_labels(x, labelset)")
         if labelset == "":
             text = self.text
         else:
