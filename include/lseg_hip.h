@@ -231,6 +231,31 @@ int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_l
 int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, int16_t* dev_label2_out,
                              float* dev_score2_out, float* dev_lse_out, void* stream);
 
+/* lseg_forward_labels with the cross-entropy against a target mask, still without the logits: the validation step's loss, pixAcc and IoU
+ * for any label set -- one shared set of any K <= 32767, or the per-image lists of lseg_set_text_groups -- in one forward.
+ * replaces: the criterion's value nn.CrossEntropyLoss(ignore_index)(pred, target) (lsegmentation_module.py:72) and batch_pix_accuracy +
+ *   batch_intersection_union on torch.max(pred, 1)[1] (:49-50,59-60) -- the [B,K,img_h,img_w] logits are neither written nor read.
+ *   dev_target       int64 [B,img_h,img_w]; with per-image lists image b's values index its own list.  A pixel is VALID iff target !=
+ *                    ignore_index and 0 <= target < K (per-image lists: < the image's own count) -- the rule of lseg_op_stats_finish's
+ *                    d_nll and of the ragged training loss
+ *   dev_label_out / dev_score_out: as in lseg_forward_labels, bit for bit
+ *   dev_lse_out      fp32 [B,img_h,img_w]: as in lseg_forward_labels_conf, bit for bit (the same online sum)
+ *   dev_nll_plane_out fp32 [B,img_h,img_w]: lse - logit[target] per valid pixel, 0 elsewhere
+ *   dev_nll          double [2] = {sum over the valid pixels of double(lse) - double(logit[target]), number of valid pixels}: the layout of
+ *                    lseg_forward_stats' dev_nll; fixed-order partials, no atomics -- two calls on the same input give the same bits
+ *   dev_counts       int64: filled exactly as lseg_op_label_stats (accumulate = 0, no class map) fills it from dev_label_out and dev_target:
+ *                    [2+3K] for one shared set (K = labels per image with lseg_set_text_grouping), {correct, labeled} + the three
+ *                    concatenated areas [2 + 3 sum of counts] for per-image lists
+ * Every output but dev_label_out may be NULL.  Streamed under the conditions of lseg_forward_labels (csrc/corr_argmax.hip, the LOSS
+ * instantiation: the target's logit is kept when its label passes through the registers; a label part of the split keeps -inf unless it
+ * holds the target, the merge takes the max); the configurations lseg_forward_labels_conf reduces from the low-resolution logits (other
+ * widths, head blocks, a fixed number of labels per image, LSEG_CORR_GENERIC) are reduced from them here too, with the same outputs; the
+ * per-image lists stay refused where lseg_forward_labels refuses them.  State rules and errors as for lseg_forward_labels_conf; a NULL
+ * target: LSEG_ERR_INVALID; train mode: LSEG_ERR_UNSUPPORTED (lseg_train_loss has the loss there). */
+int lseg_forward_labels_loss(lseg_handle h, const float* dev_x, int B, const int64_t* dev_target, int ignore_index, int16_t* dev_label_out,
+                             float* dev_score_out, float* dev_lse_out, float* dev_nll_plane_out, double* dev_nll, int64_t* dev_counts,
+                             void* stream);
+
 /* The logits BEFORE scratch.output_conv (lseg_net.py:203), for callers that read them through the x2 bilinear themselves (the
  * multi-scale evaluator's lseg_op_eval_accumulate_lowres): the inference forward exactly as lseg_forward runs it -- text cache, external
  * text features, per-image label sets (Kout = labels per image), overflow sentinel, profiling and the arch_option 1/2 head blocks
@@ -638,6 +663,32 @@ int lseg_op_corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, i
  * mapping: out8 = {mid rows/columns per tile band, mid rows/columns of its footprint, base rows/columns of its footprint, labels per
  * panel, LDS pitch of a text row in bytes, labels per interpolation chunk, output rows per wave, dynamic LDS bytes}. */
 int lseg_op_corr_argmax_geometry(int* out8);
+/* lseg_op_corr_argmax with the cross-entropy of lseg_forward_labels_loss, bare: one shared set of K rows (host_counts NULL) or ragged
+ * per-image lists (host_counts int32 [B] on the HOST as for lseg_op_corr_argmax_ragged; K is then not read).
+ * replaces: F.cross_entropy(pred, target, ignore_index, reduction='none' / 'sum') and torch.max(pred, 1) on the logits of
+ *   lseg_net.py:194-203, for any K.
+ * d_target int64 [B, 4H, 4W]; a pixel is VALID iff target != ignore_index and 0 <= target < K (ragged: < host_counts[b]).
+ * d_label / d_score: lseg_op_corr_argmax's bit for bit; d_lse: lseg_op_corr_argmax_conf's bit for bit.
+ * d_tlogit fp32 [B, 4H, 4W]: the value lseg_op_upsample4x_planes_scaled would write to out[b, target, y, x] (where target == label it IS
+ *   d_score); -inf where the pixel is not valid.  d_nll_plane fp32: d_lse - d_tlogit, 0 where not valid.
+ * d_nll double [2] = {sum over the valid pixels of double(lse) - double(tlogit), their number}.  The sum is formed in a fixed order without
+ *   atomics: lseg_op_corr_argmax_loss_plan gives out4 = {threads per workgroup, pixels per workgroup, workgroups, bytes of partials};
+ *   workgroup j owns pixels [j * out4[1], (j + 1) * out4[1]) of the flattened maps, lane t of it pixels j * out4[1] + t + out4[0] * m, and
+ *   the partials are added in ascending order.
+ * Every output after d_label may be NULL.
+ * d_ws / ws_bytes: ONE workspace, 8-byte aligned, pieces in this order, each rounded up to 256 bytes: ragged: B + 1 int32 offsets; d_nll
+ *   given: the partials; d_nll or d_nll_plane given: an fp32 [B, 4H, 4W] plane for each of d_lse / d_tlogit that is NULL (the reduction
+ *   reads both).  lseg_op_corr_argmax_loss_ws_bytes(B, H, W, ragged, want_nll, temp_planes, parts) returns these bytes plus `parts` label
+ *   parts of 224 B H W bytes each (14 per output pixel: score, lse, tlogit, label); what the workspace holds beyond the required pieces
+ *   is used for the label split as in lseg_op_corr_argmax_conf (label / score / tlogit bit-equal to the unsplit form -- tlogit by max:
+ *   exactly one part holds the target's label -- lse by log-add-exp).  A call that needs no piece takes d_ws = NULL.
+ * Refusals as lseg_op_corr_argmax_conf / _ragged, plus LSEG_ERR_INVALID for a NULL target and for a workspace smaller than the required
+ * pieces; every refusal happens before anything is launched and writes no output. */
+int lseg_op_corr_argmax_loss(const void* d_g16pad, const void* d_text16, const float* d_scale, const int64_t* d_target, int ignore_index,
+                             const int32_t* host_counts, int B, int K, int H, int W, int C, int16_t* d_label, float* d_score, float* d_lse,
+                             float* d_tlogit, float* d_nll_plane, double* d_nll, void* d_ws, size_t ws_bytes, void* stream);
+size_t lseg_op_corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts);
+int lseg_op_corr_argmax_loss_plan(int B, int H, int W, int64_t* out4);
 
 /* Device side of the multi-scale / flip sliding-window evaluator that calls the forward (additional_utils/encoding_models.py:54-155
  * MultiEvalModule.forward, module_inference, pad_image, crop_image, flip_image; additional_utils/models.py:55-140).  Per scale:

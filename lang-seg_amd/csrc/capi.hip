@@ -111,6 +111,15 @@ int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* 
     return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out, nullptr, &conf);
 }
 
+int lseg_forward_labels_loss(lseg_handle h, const float* dev_x, int B, const int64_t* dev_target, int ignore_index, int16_t* dev_label_out,
+                             float* dev_score_out, float* dev_lse_out, float* dev_nll_plane_out, double* dev_nll, int64_t* dev_counts, void* stream) {
+    GUARD(h);
+    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
+    if (!dev_target) return set_error(LSEG_ERR_INVALID, "target is NULL");
+    return h->e->forward_labels_loss(dev_x, B, dev_target, ignore_index, dev_label_out, dev_score_out, dev_lse_out, dev_nll_plane_out, dev_nll,
+                                     dev_counts, (hipStream_t)stream);
+}
+
 int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream) {
     GUARD(h);
     if (!dev_low_out) return set_error(LSEG_ERR_INVALID, "low-resolution logits output is NULL");
@@ -606,6 +615,20 @@ int lseg_op_corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, i
 int lseg_op_corr_argmax_geometry(int* out8) {
     if (!out8) return set_error(LSEG_ERR_INVALID, "corr_argmax_geometry: NULL pointer");
     corr_argmax_geometry(out8);
+    return LSEG_OK;
+}
+int lseg_op_corr_argmax_loss(const void* d_g16pad, const void* d_text16, const float* d_scale, const int64_t* d_target, int ignore_index,
+                             const int32_t* host_counts, int B, int K, int H, int W, int C, int16_t* d_label, float* d_score, float* d_lse,
+                             float* d_tlogit, float* d_nll_plane, double* d_nll, void* d_ws, size_t ws_bytes, void* stream) {
+    return corr_argmax_loss_op(d_g16pad, d_text16, d_scale, d_target, ignore_index, host_counts, B, K, H, W, C, d_label, d_score, d_lse, d_tlogit,
+                               d_nll_plane, d_nll, d_ws, ws_bytes, (hipStream_t)stream);
+}
+size_t lseg_op_corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts) {
+    return corr_argmax_loss_ws_bytes(B, H, W, ragged, want_nll, temp_planes, parts);
+}
+int lseg_op_corr_argmax_loss_plan(int B, int H, int W, int64_t* out4) {
+    if (!out4 || B < 1 || H < 1 || W < 1) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss_plan: B=%d H=%d W=%d out4=%p", B, H, W, (void*)out4);
+    corr_loss_plan((size_t)B * 16 * H * W, out4);
     return LSEG_OK;
 }
 

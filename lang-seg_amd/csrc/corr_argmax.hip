@@ -84,12 +84,23 @@ __host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_o
 // (unused by the launcher there) gives way to the image's count.  A label part that lies beyond its image's count returns before it
 // touches anything: the merge kernels skip it (they read the same offsets), no identity element is ever written.  With RAGGED = false
 // nothing of this is compiled: the shared-set instantiations keep their instructions and registers.
-template <bool CONF, bool RAGGED>
+//
+// LOSS = the cross-entropy instantiation (lseg_op_corr_argmax_loss; CONF = false): besides (best, arg) every owned pixel keeps the sum s of
+// exp(value - best) -- CONF's recurrence, so lse is CONF's bit for bit -- and tlogit, the logit of the pixel's TARGET label, taken when that
+// label walks past (it passes through the registers exactly once; -inf until then, and for good where the target is not valid).  There is
+// no runner-up: the target's label rides in the upper half of arg's register where CONF keeps arg2 (0xffff = not valid: no label
+// reaches it), and tlogit takes the place of second -- the same 3 x 15 state registers on top of the arg-max's, so the same 4 labels walk
+// the rows together.  `target` is int64 [B, 4H, 4W]; a pixel is valid iff target != ignore_index and 0 <= target < K (RAGGED: the
+// image's own count) -- label_stats_kernel's pixel_nll rule.  Rows past K enter neither the sum nor tlogit (the `< K` guard CONF has).
+template <bool CONF, bool RAGGED, bool LOSS = false>
 __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ T_all,
                                                             const float* __restrict__ scale, int16_t* __restrict__ label,
                                                             float* __restrict__ score, int B, int K_all, int H, int W, int tiles_y, int tiles_x,
                                                             int nsplit, int split_labels, size_t split_stride, int16_t* __restrict__ label2,
-                                                            float* __restrict__ score2, float* __restrict__ lse, const int* __restrict__ offsets) {
+                                                            float* __restrict__ score2, float* __restrict__ lse, const int* __restrict__ offsets,
+                                                            const long long* __restrict__ target = nullptr, int ignore_index = 0,
+                                                            float* __restrict__ tlogit = nullptr) {
+    static_assert(!(CONF && LOSS), "the loss form keeps no runner-up");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* tlds = lds;
     float* Rs = reinterpret_cast<float*>(lds + CA_P * CA_PITCH);
@@ -158,6 +169,21 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
         s_sc[s] = scale[((size_t)b * Hl + Ya + my) * Wl + Xa + mx];
     }
 
+    // ---- LOSS: the owned pixels' targets, before the fragments fill the registers (already shifted into the upper half of arg) ---------------
+    constexpr int CA_TROWS = LOSS ? CA_ROWS : 1;
+    int tg16[CA_TROWS];
+    if constexpr (LOSS) {
+#pragma unroll
+        for (int j = 0; j < CA_ROWS; ++j) {
+            int tg = 0xffff;
+            if (j < nrow && cvalid) {
+                const long long t = target[((size_t)b * Ho + ys + j) * Wo + xo];
+                if (t != (long long)ignore_index && t >= 0 && t < (long long)K) tg = (int)t;
+            }
+            tg16[j] = (int)((unsigned)tg << 16);
+        }
+    }
+
     // ---- g: the tile's fragments, once (rows / columns clamped into the map: a clamped pixel is a copy nothing reads) ------------------
     i32x4_t gf[CA_KS][4];
     {
@@ -194,6 +220,13 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
     float second[CA_CROWS], esum[CA_CROWS];                              // CONF; arg[j] = arg | arg2 << 16 there
 #pragma unroll
     for (int j = 0; j < CA_CROWS; ++j) { second[j] = -INFINITY; esum[j] = 0.f; }
+    float lsum[CA_TROWS], tl[CA_TROWS];                                  // LOSS; arg[j] = arg | target << 16 there (0xffff: not valid)
+#pragma unroll
+    for (int j = 0; j < CA_TROWS; ++j) { lsum[j] = 0.f; tl[j] = -INFINITY; }
+    if constexpr (LOSS) {
+#pragma unroll
+        for (int j = 0; j < CA_ROWS; ++j) arg[j] = tg16[j];
+    }
 
     for (int pb = k_lo; pb < k_hi; pb += CA_P) {
         // ---- T panel -> LDS (rows past K repeat the last label: computed, never compared) ------------------------------------------------
@@ -255,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
             // CA_LU labels walk the rows together: the row pattern (which mid row is new) is the same for every label, so one uniform
             // branch serves CA_LU independent interpolants and their 2 CA_LU LDS reads are in flight at once (CONF: 4 -- its 45 more state
             // registers leave no room for 8 interpolant pairs, and its per-value arithmetic hides the LDS reads of 4)
-            constexpr int LU = CONF ? 4 : CA_LU;
+            constexpr int LU = CONF || LOSS ? 4 : CA_LU;
             for (int l0 = 0; l0 < CA_LC && pb + cb + l0 < K; l0 += LU) {
                 const float* Ll = Lr + l0 * CA_LP;
                 const int lab0 = pb + cb + l0;
@@ -290,7 +323,19 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
 #pragma unroll
                     for (int u = 0; u < LU; ++u) {
                         const float v = vlerp(h0[u], h1[u], r_ly[j]);
-                        if constexpr (!CONF) {
+                        if constexpr (LOSS) {
+                            if (lab0 + u < K) {                                                   // CONF's sum, the target's logit on its way past
+                                const float e = __expf(-fabsf(v - best[j]));
+                                if ((int)((unsigned)arg[j] >> 16) == lab0 + u) tl[j] = v;
+                                if (v > best[j]) {
+                                    lsum[j] = fmaf(lsum[j], e, 1.f);
+                                    best[j] = v;
+                                    arg[j] = (int)((unsigned)arg[j] & 0xffff0000u) | (lab0 + u);
+                                } else {
+                                    lsum[j] += e;
+                                }
+                            }
+                        } else if constexpr (!CONF) {
                             if (lab0 + u < K && v > best[j]) { best[j] = v; arg[j] = lab0 + u; }      // first maximum wins
                         } else if (lab0 + u < K) {
                             // one exp per value: exp(-|v - best|) rescales the sum when v is the new maximum and is v's own term otherwise
@@ -317,7 +362,12 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
         for (int j = 0; j < CA_ROWS; ++j) {
             if (j >= nrow) continue;
             const size_t o = (size_t)sp * split_stride + ((size_t)b * Ho + ys + j) * Wo + xo;
-            if constexpr (!CONF) {
+            if constexpr (LOSS) {
+                label[o] = (int16_t)(arg[j] & 0xffff);
+                if (score) score[o] = best[j];
+                if (lse) lse[o] = best[j] + logf(lsum[j]);
+                if (tlogit) tlogit[o] = tl[j];
+            } else if constexpr (!CONF) {
                 label[o] = (int16_t)arg[j];
                 if (score) score[o] = best[j];
             } else {
@@ -393,6 +443,103 @@ __global__ __launch_bounds__(256) void corr_argmax_conf_merge_kernel(const int16
     }
 }
 
+// the four planes of the label parts of the LOSS instantiation -> the final outputs: the winner by the strict `>` of the arg-max merge, lse
+// by the log-add-exp of the CONF merge, tlogit by max -- exactly one part holds the target's label, every other part left -inf
+__global__ __launch_bounds__(256) void corr_argmax_loss_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc,
+                                                                     const float* __restrict__ wlse, const float* __restrict__ wtl, int nsplit,
+                                                                     size_t n, int16_t* __restrict__ label, float* __restrict__ score,
+                                                                     float* __restrict__ lse, float* __restrict__ tlogit,
+                                                                     const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float m = wsc[i], l = wlse[i], t = wtl[i];
+        int16_t a = wl[i];
+        const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
+        for (int s = 1; s < parts; ++s) {
+            const size_t o = (size_t)s * n + i;
+            const float v = wsc[o];
+            if (v > m) { m = v; a = wl[o]; }
+            const float pl = wlse[o], hi = fmaxf(l, pl);
+            l = hi + log1pf(expf(-fabsf(l - pl)));
+            t = fmaxf(t, wtl[o]);
+        }
+        label[i] = a;
+        if (score) score[i] = m;
+        if (lse) lse[i] = l;
+        if (tlogit) tlogit[i] = t;
+    }
+}
+
+// ---- the cross-entropy sum of the (lse, tlogit) planes: nll = {sum over the valid pixels of double(lse) - double(tlogit), their number} ------
+// Fixed order, no atomics: workgroup j owns the pixels [j * chunk, (j + 1) * chunk) (chunk a multiple of CL_THREADS: lane t of it takes
+// pixel j * chunk + t + CL_THREADS * m for m = 0, 1, ...), its lanes' sums meet in a shuffle tree and the four wave totals are added in
+// ascending order into partial j; corr_loss_fold_kernel's one wave then adds the partials (lane l: l, l + 64, ... ascending, then the same
+// tree).  Two runs on the same planes give the same bits.  The valid rule is the streamed kernel's (label_stats_kernel's pixel_nll).
+// plane (optional) = float(lse - tlogit), 0 where the pixel is not valid.
+constexpr int CL_THREADS = 256;
+constexpr int CL_MIN_PIXELS = 4096;                       // pixels per workgroup at least (sixteen per lane)
+constexpr int CL_MAX_GROUPS = 1024;                       // partials at most: 16 KB of workspace
+
+// {pixels per workgroup, workgroups} for n pixels
+inline void cl_plan(size_t n, size_t& chunk, int& groups) {
+    size_t g = (n + CL_MIN_PIXELS - 1) / CL_MIN_PIXELS;
+    g = g < 1 ? 1 : (g > (size_t)CL_MAX_GROUPS ? (size_t)CL_MAX_GROUPS : g);
+    chunk = ((n + g - 1) / g + CL_THREADS - 1) / CL_THREADS * CL_THREADS;
+    groups = (int)((n + chunk - 1) / chunk);
+}
+
+__device__ inline void cl_wave_sum(double& s, unsigned& c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_down(s, off, 64);
+        c += __shfl_down(c, off, 64);
+    }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void corr_loss_reduce_kernel(const float* __restrict__ lse, const float* __restrict__ tlogit,
+                                                                      const long long* __restrict__ target, int ignore_index, int K,
+                                                                      const int* __restrict__ offsets, unsigned img_pix, size_t n, size_t chunk,
+                                                                      float* __restrict__ plane, double* __restrict__ partial) {
+    __shared__ double ws[CL_THREADS / 64];
+    __shared__ unsigned wc[CL_THREADS / 64];
+    const size_t lo = blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    double s = 0.0;
+    unsigned c = 0;
+    for (size_t i = lo + threadIdx.x; i < hi; i += CL_THREADS) {
+        const long long t = target[i];
+        int k = K;
+        if (offsets) {
+            const size_t b = i / img_pix;
+            k = offsets[b + 1] - offsets[b];
+        }
+        const bool valid = t != (long long)ignore_index && t >= 0 && t < (long long)k;
+        const float l = lse[i], g = tlogit[i];
+        if (valid) { s += (double)l - (double)g; ++c; }
+        if (plane) plane[i] = valid ? l - g : 0.f;
+    }
+    cl_wave_sum(s, c);
+    if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = s; wc[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0 && partial) {
+        double ts = ws[0];
+        unsigned tc = wc[0];
+#pragma unroll
+        for (int w = 1; w < CL_THREADS / 64; ++w) { ts += ws[w]; tc += wc[w]; }
+        partial[2 * (size_t)blockIdx.x] = ts;
+        partial[2 * (size_t)blockIdx.x + 1] = (double)tc;
+    }
+}
+
+__global__ __launch_bounds__(64) void corr_loss_fold_kernel(const double* __restrict__ partial, int groups, double* __restrict__ nll) {
+    double s = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < groups; i += 64) { s += partial[2 * i]; c += partial[2 * i + 1]; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_down(s, off, 64);
+        c += __shfl_down(c, off, 64);
+    }
+    if (threadIdx.x == 0) { nll[0] = s; nll[1] = c; }
+}
+
 // the arg-max of the x2-upsampled logits read through the bilinear on the fly (seg_stats_kernel's `up` form, masks only) with an int16
 // label and an optional score: what the streamed kernel's callers get when the planes exist in memory
 __global__ __launch_bounds__(256) void seg_argmax16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
@@ -457,6 +604,44 @@ __global__ __launch_bounds__(256) void seg_conf16_kernel(const float* __restrict
     }
 }
 
+// seg_conf16_kernel's loss form, the outputs of the LOSS instantiation from planes in memory: the same sum (so the same lse bits as
+// seg_conf16_kernel), no runner-up, and tlogit = the value of the target's plane at this pixel (-inf where the target is not valid:
+// target == ignore_index or outside [0, K)) -- the very bilerp the loop would have met at k = target
+__global__ __launch_bounds__(256) void seg_loss16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
+                                                         const long long* __restrict__ target, int ignore_index, int16_t* __restrict__ label,
+                                                         float* __restrict__ score, float* __restrict__ lse, float* __restrict__ tlogit) {
+    const int Wo = 2 * w, HW = 4 * h * w;
+    const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
+    const size_t kstride = (size_t)h * w;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i % HW);
+        const size_t b = i / HW;
+        const int yo = p / Wo, xo = p - yo * Wo;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_tap(ry, yo, h, y0, y1, ly);
+        src_tap(rx, xo, w, x0, x1, lx);
+        const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
+        const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
+        const long long t = target[i];
+        const int tg = t != (long long)ignore_index && t >= 0 && t < (long long)K ? (int)t : -1;
+        float m = -INFINITY, es = 0.f, tl = -INFINITY;
+        int arg = 0;
+        for (int k = 0; k < K; ++k) {
+            const float* cc = col + (size_t)k * kstride;
+            const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
+            const float e = __expf(-fabsf(v - m));
+            es = v > m ? fmaf(es, e, 1.f) : es + e;
+            tl = k == tg ? v : tl;
+            if (v > m) { m = v; arg = k; }
+        }
+        label[i] = (int16_t)arg;
+        if (score) score[i] = m;
+        if (lse) lse[i] = m + logf(es);
+        if (tlogit) tlogit[i] = tl;
+    }
+}
+
 // the tile -> footprint mapping for this shape, in the kernel's own arithmetic (tests/test_corr_argmax_host.py is its model)
 bool ca_tiles_fit(int n_base, int n_mid, int n_out, int max_out) {
     const float r1 = (float)(n_base - 1) / (float)(n_mid - 1), r2 = (float)(n_mid - 1) / (float)(n_out - 1);
@@ -508,7 +693,27 @@ __global__ __launch_bounds__(64) void corr_argmax_offsets_kernel(int* __restrict
 
 }  // namespace
 
+// the streaming reduction behind both loss forms (nothing to do when neither the sum nor the plane is wanted)
+static int launch_corr_loss_reduce(const float* lse, const CorrLoss& L, int K, const int* d_offsets, unsigned img_pix, size_t npix, hipStream_t st) {
+    if (!L.nll && !L.nll_plane) return 0;
+    size_t chunk;
+    int groups;
+    cl_plan(npix, chunk, groups);
+    hipLaunchKernelGGL(corr_loss_reduce_kernel, dim3(groups), dim3(CL_THREADS), 0, st, lse, (const float*)L.tlogit,
+                       reinterpret_cast<const long long*>(L.target), L.ignore_index, K, d_offsets, img_pix, npix, chunk, L.nll_plane,
+                       L.nll ? L.partial : (double*)nullptr);
+    LSEG_HIP_TRY(hipGetLastError());
+    if (L.nll) {
+        hipLaunchKernelGGL(corr_loss_fold_kernel, dim3(1), dim3(64), 0, st, (const double*)L.partial, groups, L.nll);
+        LSEG_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 // g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W]; label: int16 [B, 4H, 4W]; score: fp32 [B, 4H, 4W] or NULL
+// loss (optional): the LOSS instantiation -- lse as below, tlogit / nll_plane fp32 [B, 4H, 4W], nll double [2], each optional; the sum and the
+// plane read lse and tlogit, so both must be given with either, and the sum needs `partial` (corr_loss_plan's bytes).  A part takes 14
+// bytes per output pixel of the workspace (score, lse, tlogit fp32; label int16): 224 B H W bytes per part
 // ws (optional, ws_bytes): with 6 bytes x B x 16 H W per split the labels of a tile are split over up to 8 workgroups (whole panels each)
 // and merged afterwards -- a 120 x 120 map has only 81 tiles per image for 256 CUs; without it one workgroup per tile streams all K
 // label2 / score2 / lse (each optional): any of them selects the CONF instantiation; a part then takes 16 bytes per output pixel of the
@@ -517,11 +722,19 @@ __global__ __launch_bounds__(64) void corr_argmax_offsets_kernel(int* __restrict
 // on the stream once every check has passed, K is then the LARGEST count (it sizes the label parts) and T holds host_prefix[B] rows
 static int launch_corr_argmax_any(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2,
                                   float* lse, int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes,
-                                  const int* host_prefix = nullptr, int* d_offsets = nullptr) {
-    const bool conf = label2 || score2 || lse;
+                                  const int* host_prefix = nullptr, int* d_offsets = nullptr, const CorrLoss* loss = nullptr) {
+    const bool conf = !loss && (label2 || score2 || lse);
     const bool ragged = host_prefix != nullptr;
-    const size_t part_bytes = conf ? 16 : 6;
+    const size_t part_bytes = loss ? 14 : conf ? 16 : 6;
     if (!g || !T || !scale || !label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
+    if (loss) {
+        if (!loss->target) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL target");
+        if (label2 || score2) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the loss form keeps no runner-up");
+        if ((loss->nll || loss->nll_plane) && (!lse || !loss->tlogit || (loss->nll && !loss->partial)))
+            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the reduction reads the lse and tlogit planes and writes its partials");
+        if (((uintptr_t)loss->target | (uintptr_t)loss->nll | (uintptr_t)loss->partial) & 7)
+            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: target / nll / partials must be 8-byte aligned");
+    }
     if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
     if (!corr_argmax_supported(K, C)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: K=%d C=%d (C must be 512, K >= 1)", K, C);
     if (B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "corr_argmax: B=%d H=%d W=%d", B, H, W);
@@ -540,6 +753,8 @@ static int launch_corr_argmax_any(const void* g, const void* T, const float* sca
         LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_done.fetch_or(bit, std::memory_order_release);
     }
     const size_t npix = (size_t)B * 16 * H * W;
@@ -558,6 +773,30 @@ static int launch_corr_argmax_any(const void* g, const void* T, const float* sca
             hipLaunchKernelGGL(corr_argmax_offsets_kernel, dim3(1), dim3(64), 0, st, d_offsets + i0, ch, n);
             LSEG_HIP_TRY(hipGetLastError());
         }
+    }
+    if (loss) {
+        // workspace planes: score, lse, tlogit (fp32), label (int16), each [nsplit][npix]; a part always writes all four
+        float *wlse = wsc + pn, *wtl = wsc + 2 * pn;
+        int16_t* wl = reinterpret_cast<int16_t*>(wsc + 3 * pn);
+        const bool split = nsplit > 1;
+        const long long* tgt = reinterpret_cast<const long long*>(loss->target);
+        if (ragged)
+            hipLaunchKernelGGL((corr_argmax_kernel<false, true, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                               (const uint16_t*)T, scale, split ? wl : label, split ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
+                               split ? split_labels : K, split ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, split ? wlse : lse,
+                               (const int*)d_offsets, tgt, loss->ignore_index, split ? wtl : loss->tlogit);
+        else
+            hipLaunchKernelGGL((corr_argmax_kernel<false, false, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
+                               (const uint16_t*)T, scale, split ? wl : label, split ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
+                               split ? split_labels : K, split ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, split ? wlse : lse,
+                               (const int*)nullptr, tgt, loss->ignore_index, split ? wtl : loss->tlogit);
+        LSEG_HIP_TRY(hipGetLastError());
+        if (split) {
+            hipLaunchKernelGGL(corr_argmax_loss_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, wlse, wtl, nsplit, npix, label, score, lse,
+                               loss->tlogit, (const int*)d_offsets, split_labels, img_pix);
+            LSEG_HIP_TRY(hipGetLastError());
+        }
+        return launch_corr_loss_reduce(lse, *loss, K, (const int*)d_offsets, img_pix, npix, st);
     }
     if (conf) {
         // workspace planes: score, score2, lse (fp32), label, label2 (int16), each [nsplit][npix]; a part always writes all five
@@ -663,6 +902,84 @@ int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, in
     out2[0] = nsplit;
     out2[1] = (panels + nsplit - 1) / nsplit * CA_P;
     return 0;
+}
+
+// the reduction's partial layout for n pixels, host only: out4 = {threads per workgroup, pixels per workgroup, workgroups, bytes of partials}
+void corr_loss_plan(size_t npix, int64_t* out4) {
+    size_t chunk;
+    int groups;
+    cl_plan(npix, chunk, groups);
+    out4[0] = CL_THREADS; out4[1] = (int64_t)chunk; out4[2] = groups; out4[3] = (int64_t)groups * 2 * (int64_t)sizeof(double);
+}
+
+size_t corr_loss_partial_bytes_max() { return (size_t)CL_MAX_GROUPS * 2 * sizeof(double); }
+
+// launch_corr_argmax(_ragged) with the cross-entropy: host_counts NULL = one label set of K rows, else the ragged form (K unused, d_offsets
+// required).  lse optional as in launch_corr_argmax_conf; the rest of the outputs in `loss` (see launch_corr_argmax_any)
+int launch_corr_argmax_loss(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
+                            float* score, float* lse, const CorrLoss& loss, int B, int K, int H, int W, int C, hipStream_t st, void* ws,
+                            size_t ws_bytes) {
+    if (!host_counts) return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, lse, B, K, H, W, C, st, ws, ws_bytes, nullptr, nullptr, &loss);
+    if (!g || !T || !scale || !label || !d_offsets) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL pointer");
+    if (C != CA_C) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_loss: C=%d (C must be 512)", C);
+    std::vector<int> prefix;
+    int kmax = 0;
+    if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
+    return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, lse, B, kmax, H, W, C, st, ws, ws_bytes, prefix.data(), d_offsets, &loss);
+}
+
+// the caller's one workspace of lseg_op_corr_argmax_loss, in this order, each piece rounded up to 256 bytes: the offsets of a ragged call
+// (B + 1 int32), the reduction's partials (when the sum is wanted), an lse and a tlogit plane the caller did not pass while asking for
+// the sum or the plane (fp32 [B, 4H, 4W] each), and behind them `parts` label parts of 224 B H W bytes
+static size_t cl_up(size_t v) { return (v + 255) / 256 * 256; }
+size_t corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts) {
+    if (B < 1 || H < 1 || W < 1 || temp_planes < 0 || temp_planes > 2 || parts < 0) return 0;
+    const size_t npix = (size_t)B * 16 * H * W;
+    int64_t plan[4];
+    corr_loss_plan(npix, plan);
+    return (ragged ? cl_up(((size_t)B + 1) * 4) : 0) + (want_nll ? cl_up((size_t)plan[3]) : 0) + (size_t)temp_planes * cl_up(npix * 4) +
+           (parts > 1 ? (size_t)parts * npix * 14 : 0);
+}
+
+int corr_argmax_loss_op(const void* g, const void* T, const float* scale, const int64_t* target, int ignore_index, const int32_t* host_counts,
+                        int B, int K, int H, int W, int C, int16_t* label, float* score, float* lse, float* tlogit, float* nll_plane, double* nll,
+                        void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!g || !T || !scale || !label || !target) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL pointer");
+    if (B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: B=%d H=%d W=%d", B, H, W);
+    if ((size_t)B * 16 * H * W >= ((size_t)1 << 31)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_loss: B=%d %dx%d exceeds the kernel's 32-bit offsets", B, H, W);
+    const bool red = nll || nll_plane;
+    const int temps = red ? (lse ? 0 : 1) + (tlogit ? 0 : 1) : 0;
+    const size_t head = corr_argmax_loss_ws_bytes(B, H, W, host_counts != nullptr, nll != nullptr, temps, 0);
+    if (head && (!ws || ws_bytes < head || ((uintptr_t)ws & 7)))
+        return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: this call needs an 8-byte aligned workspace of at least %zu bytes "
+                                           "(lseg_op_corr_argmax_loss_ws_bytes), got %zu", head, ws ? ws_bytes : (size_t)0);
+    const size_t npix = (size_t)B * 16 * H * W;
+    char* p = static_cast<char*>(ws);
+    auto take = [&](size_t bytes) { char* q = p; p += cl_up(bytes); return q; };
+    int* d_offsets = host_counts ? reinterpret_cast<int*>(take(((size_t)B + 1) * 4)) : nullptr;
+    int64_t plan[4];
+    corr_loss_plan(npix, plan);
+    CorrLoss L{target, ignore_index, tlogit, nll_plane, nll, nll ? reinterpret_cast<double*>(take((size_t)plan[3])) : nullptr};
+    if (red && !lse) lse = reinterpret_cast<float*>(take(npix * 4));
+    if (red && !tlogit) L.tlogit = reinterpret_cast<float*>(take(npix * 4));
+    const size_t rest = ws ? ws_bytes - head : 0;
+    return launch_corr_argmax_loss(g, T, scale, host_counts, d_offsets, label, score, lse, L, B, K, H, W, C, st, rest ? p : nullptr, rest);
+}
+
+// launch_seg_conf16's loss form: label / score / lse as there, tlogit / nll_plane / nll as launch_corr_argmax_loss (one label set of K planes
+// per image: a fixed number of labels per image is K of them with targets in [0, K))
+int launch_seg_loss16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, float* lse, const CorrLoss& loss, hipStream_t st) {
+    if (!low || !label || !loss.target) return set_error(LSEG_ERR_INVALID, "seg_loss16: NULL pointer");
+    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_loss16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
+    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_loss16: B=%d h=%d w=%d", B, h, w);
+    if ((loss.nll || loss.nll_plane) && (!lse || !loss.tlogit || (loss.nll && !loss.partial)))
+        return set_error(LSEG_ERR_INVALID, "seg_loss16: the reduction reads the lse and tlogit planes and writes its partials");
+    const size_t npix = (size_t)B * 4 * h * w;
+    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(seg_loss16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, reinterpret_cast<const long long*>(loss.target),
+                       loss.ignore_index, label, score, lse, loss.tlogit);
+    LSEG_HIP_TRY(hipGetLastError());
+    return launch_corr_loss_reduce(lse, loss, K, nullptr, (unsigned)(4 * h * w), npix, st);
 }
 
 // low: fp32 [B, K, h, w] (the (2h, 2w) logits of the engine); label int16 [B, 2h, 2w]; score fp32 [B, 2h, 2w] or NULL

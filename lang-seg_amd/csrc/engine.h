@@ -105,8 +105,15 @@ public:
     // held (lseg_forward_features): the forward stops behind the scale plane and copies what the correlation reads -- g16pad_ and
     // nscale_ -- into the caller's buffers; no text is read, the gram is pixel_gram's whatever K is set
     struct HeldOut { void* feat; float* scale; };
+    // loss (lseg_forward_labels_loss; needs label_out, excludes conf's runner-up): the cross-entropy beside the arg-max -- conf->lse is its
+    // lse output, the rest is ops.h' CorrLoss; streamed where the labels stream, seg_loss16 on the planes in memory elsewhere
     int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
-                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr, const HeldOut* held = nullptr);
+                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr, const HeldOut* held = nullptr,
+                const CorrLoss* loss = nullptr);
+    // lseg_forward_labels_loss: the labels forward with the loss, then (dev_counts given) lseg_op_label_stats on the label map it wrote.
+    // The planes nobody asked for (lse, tlogit), the reduction's partials and label_stats' flag words live in loss_ws_, made on first use
+    int forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out, float* lse_out,
+                            float* nll_plane_out, double* nll, int64_t* counts, hipStream_t st);
     // label panels over held features (lseg_forward_features / lseg_score_features): the bytes of the two held buffers for B images, and
     // the low-resolution logits of text rows [row0, row0 + rows) from them -- correlate_planes + upsample2x_planes_scaled, the K > 157
     // route of lseg_forward_lowres plane for plane
@@ -183,6 +190,7 @@ private:
     int check_ragged(int B, bool labels_only);       // the refusals of a forward while ragged groups are set
     int check_held(const char* what);                // the refusals of lseg_forward_features / lseg_score_features: where corr_low does not hold
     std::vector<int32_t> groups_;
+    char* loss_ws_ = nullptr;                        // forward_labels_loss: {lse, tlogit} fp32 [max_batch,img_h,img_w], partials, flags
     int* d_goff_ = nullptr;                          // [max_batch + 1] prefix sum of groups_, written by the ragged launch
     int flush_events();
     int materialize_low(hipStream_t st);

@@ -1036,9 +1036,11 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
 }
 
 int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
-                    float* low_out, const LabelConf* conf, const HeldOut* held) {
+                    float* low_out, const LabelConf* conf, const HeldOut* held, const CorrLoss* loss) {
     const LabelConf cf = conf ? *conf : LabelConf{nullptr, nullptr, nullptr};
     if ((cf.label2 || cf.score2 || cf.lse) && !label_out) return set_error(LSEG_ERR_INVALID, "the confidence outputs need the label output");
+    if (loss && (!label_out || !loss->target || cf.label2 || cf.score2 || logits || argmax_out || low_out || held))
+        return set_error(LSEG_ERR_INVALID, "the loss outputs need the label output and a target, and come with no other output");
     if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
     if (K_ < 1 && !held) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
     if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
@@ -1204,16 +1206,22 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         if (ragged()) {
             // per-image label sets of any size (check_ragged let only the streamed labels through): the scale plane from pixel_gram, as for
             // K > 157 above -- corr_planes has no per-image form; low_ is the workspace of the label parts, sized from the largest list
-            TRY(launch_corr_argmax_ragged(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.label2, cf.score2, cf.lse, B,
-                                          lh_[0], lw_[0], c.out_c, st, low_, (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
+            const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
+            if (loss) TRY(launch_corr_argmax_loss(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.lse, *loss, B, 0, lh_[0],
+                                                  lw_[0], c.out_c, st, low_, ws_bytes));
+            else TRY(launch_corr_argmax_ragged(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.label2, cf.score2, cf.lse, B,
+                                               lh_[0], lw_[0], c.out_c, st, low_, ws_bytes));
             labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
         }
         if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
             // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
-            TRY(launch_corr_argmax_conf(g16pad_, tnorm_, nscale_, label_out, score_out, cf.label2, cf.score2, cf.lse, B, K_, lh_[0], lw_[0], c.out_c, st,
-                                        low_, (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float)));
+            const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
+            if (loss) TRY(launch_corr_argmax_loss(g16pad_, tnorm_, nscale_, nullptr, nullptr, label_out, score_out, cf.lse, *loss, B, K_, lh_[0], lw_[0],
+                                                  c.out_c, st, low_, ws_bytes));
+            else TRY(launch_corr_argmax_conf(g16pad_, tnorm_, nscale_, label_out, score_out, cf.label2, cf.score2, cf.lse, B, K_, lh_[0], lw_[0], c.out_c,
+                                             st, low_, ws_bytes));
             labels_only_ = true; last_low_ = nullptr; last_kout_ = K_;
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
@@ -1296,13 +1304,40 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     if (argmax_out && Kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", Kout);
     if (argmax_out) TRY(launch_seg_stats_ex(low, nullptr, B, Kout, 4 * hw1, -1, nullptr, nullptr, argmax_out, 1, h1, w1, st));
     // the int16 form, on the planes in memory (with the runner-up and the log-sum-exp when lseg_forward_labels_conf asks for them)
-    if (label_out) TRY(launch_seg_conf16(low, B, Kout, h1, w1, label_out, score_out, cf.label2, cf.score2, cf.lse, st));
+    if (label_out && loss) TRY(launch_seg_loss16(low, B, Kout, h1, w1, label_out, score_out, cf.lse, *loss, st));
+    else if (label_out) TRY(launch_seg_conf16(low, B, Kout, h1, w1, label_out, score_out, cf.label2, cf.score2, cf.lse, st));
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
     if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
     // every other schedule (head blocks, the full-resolution correlation, debug / split-precision) has them in engine memory: a copy
     if (low_out) LSEG_HIP_TRY(hipMemcpyAsync(low_out, low, (size_t)B * Kout * hw1 * sizeof(float), hipMemcpyDeviceToDevice, st));
     prof_end(PF_FWD, fwd0, 0.0, st);
     return 0;
+}
+
+// lseg_forward_labels_loss: the labels forward with the cross-entropy (streamed: the LOSS instantiation of corr_argmax.hip; elsewhere
+// seg_loss16 on the planes in memory), then the counters of lseg_op_label_stats from the label map just written
+int Engine::forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out,
+                                float* lse_out, float* nll_plane_out, double* nll, int64_t* counts, hipStream_t st) {
+    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_forward_labels_loss is an inference feature (train mode is on: lseg_train_loss has the loss)");
+    if (!label_out || !target) return set_error(LSEG_ERR_INVALID, "forward_labels_loss: NULL label output or target");
+    const size_t plane = (((size_t)cfg.max_batch * cfg.img_h * cfg.img_w * sizeof(float)) + 255) / 256 * 256;
+    const size_t part = corr_loss_partial_bytes_max();       // any B <= max_batch: the most workgroups the reduction ever takes
+    if (!loss_ws_) {
+        LSEG_HIP_TRY(hipSetDevice(device));
+        ALLOC(loss_ws_, char, 2 * plane + part + 256);
+    }
+    float* lse = lse_out ? lse_out : reinterpret_cast<float*>(loss_ws_);
+    const bool red = nll || nll_plane_out;
+    const CorrLoss loss{target, ignore_index, red ? reinterpret_cast<float*>(loss_ws_ + plane) : nullptr, nll_plane_out, nll,
+                        reinterpret_cast<double*>(loss_ws_ + 2 * plane)};
+    const LabelConf conf{nullptr, nullptr, red || lse_out ? lse : nullptr};
+    TRY(forward(x, B, nullptr, nullptr, st, label_out, score_out, nullptr, &conf, nullptr, &loss));
+    if (!counts) return 0;
+    int64_t* flags = reinterpret_cast<int64_t*>(loss_ws_ + 2 * plane + part);
+    int kmax = 0;
+    for (int k : groups_) kmax = k > kmax ? k : kmax;
+    return launch_label_stats(label_out, target, B, cfg.img_h, cfg.img_w, ragged() ? kmax : last_kout_ > 0 ? last_kout_ : K_, ignore_index,
+                              ragged() ? d_goff_ : nullptr, nullptr, 0, counts, flags, 0, st);
 }
 
 // the (2h, 2w) logits of the last forward in memory (the one-pass x4 upsample skipped them)

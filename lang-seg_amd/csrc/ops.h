@@ -150,6 +150,23 @@ int launch_corr_argmax_ragged(const void* g, const void* T, const float* scale, 
                               void* ws = nullptr, size_t ws_bytes = 0);
 // host only: out2 = {label parts, labels per part} of that launch when it plans for `cus` compute units
 int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2);
+// the cross-entropy on the streamed route (the LOSS instantiation; no runner-up): beside label / score / lse, tlogit fp32 = the logit of the
+// pixel's target label (-inf where the target is not valid: == ignore_index or outside [0, K), ragged: [0, count_b)), nll_plane fp32 =
+// lse - tlogit (0 where not valid) and nll double [2] = {sum over the valid pixels of double(lse) - double(tlogit), their number} in a
+// fixed order (partial: corr_loss_plan's bytes of device scratch).  tlogit / nll_plane / nll each optional; the sum and the plane read the
+// lse and tlogit planes, so those must be given with either.  target int64 [B, 4H, 4W].  ws: 14 B x B x 16 H W per label part
+struct CorrLoss { const int64_t* target; int ignore_index; float* tlogit; float* nll_plane; double* nll; double* partial; };
+void corr_loss_plan(size_t npix, int64_t* out4);          // host only: {threads, pixels per workgroup, workgroups, bytes of partials}
+size_t corr_loss_partial_bytes_max();                     // the partials of the largest plan
+int launch_corr_argmax_loss(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
+                            float* score, float* lse, const CorrLoss& loss, int B, int K, int H, int W, int C, hipStream_t st,
+                            void* ws = nullptr, size_t ws_bytes = 0);   // host_counts NULL: one label set of K rows; else ragged (K unused)
+int launch_seg_loss16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, float* lse, const CorrLoss& loss, hipStream_t st);
+// lseg_op_corr_argmax_loss: the launch above with everything it needs beside the outputs carved from ONE caller workspace
+size_t corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts);
+int corr_argmax_loss_op(const void* g, const void* T, const float* scale, const int64_t* target, int ignore_index, const int32_t* host_counts,
+                        int B, int K, int H, int W, int C, int16_t* label, float* score, float* lse, float* tlogit, float* nll_plane, double* nll,
+                        void* ws, size_t ws_bytes, hipStream_t st);
 // episode.hip -- few-shot episode evaluation (Evaluator.classify_prediction + AverageMeter.update + the 2-class criterion): scores fp32
 // [B,2,H,W] (up = 0) or low-resolution logits [B,2,H/2,W/2] read through the x2 bilinear (up = 1), target int64 / ignore uint8 (or NULL)
 // [B,H,W] -> areas int64 [B,6], nll double [B,2], flags int64 [2], optional scatter into the meter's int64 [2,nclass] buffers

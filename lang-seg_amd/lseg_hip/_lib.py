@@ -77,6 +77,7 @@ SIGNATURES = {
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels_conf": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lseg_forward_labels_loss": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_forward_lowres": (_i, [_vp, _vp, _i, _vp, _vp]),
     "lseg_features_bytes": (_i, [_vp, _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "lseg_forward_features": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -110,6 +111,9 @@ SIGNATURES = {
     "lseg_op_corr_argmax_conf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_corr_argmax_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lseg_op_corr_argmax_ragged_split": (_i, [_vp, _i, _i, _i, _i, C.c_size_t, _i, _vp]),
+    "lseg_op_corr_argmax_loss": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lseg_op_corr_argmax_loss_ws_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "lseg_op_corr_argmax_loss_plan": (_i, [_i, _i, _i, _vp]),
     "lseg_op_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_vit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_gemm_res32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -291,6 +291,33 @@ class HipEngine:
         self._raise_callback_error()
         return out
 
+    def forward_labels_loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -1, plane: bool = False) -> Dict[str, torch.Tensor]:
+        """forward_labels with the cross-entropy against `target` int64 [B,H,W] (lseg_forward_labels_loss), without the [B,K,H,W] logits,
+        for one shared label set of any K or ragged per-image lists (the target of image b then indexes its own list).  A dict of DEVICE
+        tensors, no host synchronisation: "label" int16 / "score" / "lse" fp32 [B,H,W] as forward_labels_conf gives them; "nll" float64 [2]
+        = {sum over the valid pixels (target != ignore_index and inside the image's label range) of lse - logit[target], their number};
+        "counts" int64 = label_stats' counters of "label" against the target ([2 + 3K]; ragged: [2 + 3 sum of the list lengths]); with
+        plane=True also "nll_plane" fp32 [B,H,W], the per-pixel loss (0 where the pixel is not valid)."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        if not torch.is_tensor(target) or tuple(target.shape) != (B, H, W) or target.dtype.is_floating_point:
+            raise ValueError(f"forward_labels_loss: target must be an integer tensor [{B},{H},{W}]")
+        t = target.detach().to(self.device, torch.int64).contiguous()
+        n = sum(self._groups) if self._groups is not None else (self._group if self._group > 0 else self._K)
+        out = {"label": torch.empty((B, H, W), dtype=torch.int16, device=self.device),
+               "score": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
+               "lse": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
+               "nll": torch.empty(2, dtype=torch.float64, device=self.device),
+               "counts": torch.empty(2 + 3 * n, dtype=torch.int64, device=self.device)}
+        if plane:
+            out["nll_plane"] = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
+        P = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None       # noqa: E731
+        _lib.check(self.lib.lseg_forward_labels_loss(
+            self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(t.data_ptr()), int(ignore_index), P("label"), P("score"), P("lse"), P("nll_plane"),
+            P("nll"), P("counts"), C.c_void_p(_stream_ptr(self.device))))
+        self._raise_callback_error()
+        return out
+
     def forward_lowres(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 [B,Kout,H/2,W/2]: the logits before output_conv's x2 bilinear (lseg_forward_lowres) -- lseg_op_upsample2x_planes of them is
         bit-identical to forward(x); the [B,Kout,H,W] tensor is never written."""

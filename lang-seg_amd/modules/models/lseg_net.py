@@ -285,8 +285,12 @@ class LSeg(BaseModel):
         self._stamp_epoch = getattr(self, "_stamp_epoch", 0) + 1
         return super().load_state_dict(*a, **k)
 
-    def forward_metrics(self, x, target, labelset="", ignore_index=-1, panel=None):
+    def forward_metrics(self, x, target, labelset="", ignore_index=-1, panel=None, streamed=False):
         """evaluate(x, target) of the Lightning module without the full-resolution logits (lseg_forward_stats).
+        streamed=True: the same dict -- counts and nll_* keys -- from the streamed label route (lseg_forward_labels_loss): no logits at any
+        resolution, any K <= 32767, and labelset may be B per-image lists (`target` then indexes each image's OWN list, the areas have
+        one entry per list entry and the loss is each image's softmax over its own labels: the value train_loss gives in train mode).
+        The fp16 range guard behaves as in predict_labels.  It excludes panel= (ValueError): the two are different routes.
         panel=p: the same dict with device memory set by p instead of K -- the image tower runs once (hold_features), the label set is
         walked in panels of p rows and the engine is handed ONLY the panel's token rows, so it is sized for p labels (its label planes
         are max_batch x max_labels x H/2 x W/2) and no [B,K,H/2,W/2] planes exist anywhere; every panel is folded into a four-plane
@@ -296,6 +300,10 @@ class LSeg(BaseModel):
         the held-feature planes in their last bits (include/lseg_hip.h, lseg_score_features), so a near-tie may fall the other way.
         Accepted where lseg_forward_features is: one label set shared by the batch, a network in eval mode, the commuted schedule;
         anything else raises LSEG_ERR_UNSUPPORTED."""
+        if streamed and panel is not None:
+            raise ValueError("forward_metrics: streamed=True and panel= are two different routes: give one")
+        if streamed:
+            return self._forward_metrics_streamed(x, target, labelset, ignore_index)
         if panel is not None:
             return self._forward_metrics_panels(x, target, labelset, ignore_index, int(panel))
         was = self.training
@@ -307,6 +315,39 @@ class LSeg(BaseModel):
             return eng.forward_stats(target, ignore_index)
         finally:
             self.train(was)
+
+    def _forward_metrics_streamed(self, x, target, labelset, ignore_index):
+        from lseg_hip.metrics import _counts_dict
+        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != (x.shape[0], x.shape[2], x.shape[3]):
+            raise ValueError(f"forward_metrics: target must be [B,H,W] = {(x.shape[0], x.shape[2], x.shape[3])}")
+        groups, flat = None, labelset
+        if isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset):
+            groups = [len(ls) for ls in labelset]
+            if len(groups) != x.shape[0] or min(groups) < 1:
+                raise ValueError(f"per-image label lists: {len(groups)} lists (sizes {groups}) for a batch of {x.shape[0]}; every image needs >= 1 label")
+            flat = [lab for ls in labelset for lab in ls]
+        text = self.text if flat == "" else tokenize(flat, self.cfg.text.ctx, self.cfg.text.vocab)
+        if not x.is_cuda:
+            raise RuntimeError("LSegNet.forward_metrics needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
+        B, _, H, W = x.shape
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                eng = self._engine(B, H, W, text.shape[0], x.device)
+                if eng.training:
+                    eng.set_train(False)
+                self._set_tokens(eng, text, flat, groups)
+                self._last_engine = eng
+                r = eng.forward_labels_loss(x.float(), target.to(x.device), ignore_index)
+                if self._range_guard(eng, x.device):                            # fell back to bf16: run again on a bf16 engine
+                    return self._forward_metrics_streamed(x, target, labelset, ignore_index)
+        finally:
+            self.train(was)
+        c, n = r["counts"].cpu(), r["nll"].cpu()
+        out = _counts_dict(c, (c.numel() - 2) // 3)
+        out["nll_sum"], out["nll_count"] = float(n[0]), int(n[1])
+        return out
 
     def _forward_metrics_panels(self, x, target, labelset, ignore_index, panel):
         from lseg_hip import _lib
