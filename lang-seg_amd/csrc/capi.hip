@@ -566,12 +566,12 @@ int lseg_op_head_features(const void* x_bf16, const void* w_bf16, const float* b
 
 int lseg_op_corr_argmax(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int B, int K, int H, int W,
                         int C, void* d_ws, size_t ws_bytes, void* stream) {
-    return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, d_label, d_score, B, K, H, W, C, (hipStream_t)stream, d_ws, ws_bytes);
+    return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, CorrOut{d_label, d_score}, B, K, H, W, C, (hipStream_t)stream, d_ws, ws_bytes);
 }
 int lseg_op_corr_argmax_conf(const void* d_g16pad, const void* d_tnorm, const float* d_scale, int16_t* d_label, float* d_score, int16_t* d_label2,
                              float* d_score2, float* d_lse, int B, int K, int H, int W, int C, void* d_ws, size_t ws_bytes, void* stream) {
-    return launch_corr_argmax_conf(d_g16pad, d_tnorm, d_scale, d_label, d_score, d_label2, d_score2, d_lse, B, K, H, W, C, (hipStream_t)stream, d_ws,
-                                   ws_bytes);
+    return launch_corr_argmax(d_g16pad, d_tnorm, d_scale, CorrOut{d_label, d_score, d_label2, d_score2, d_lse}, B, K, H, W, C, (hipStream_t)stream,
+                              d_ws, ws_bytes);
 }
 
 size_t lseg_op_episode_stats_ws_bytes(int B, int H, int W) { return episode_stats_ws_bytes(B, H, W); }
@@ -606,8 +606,9 @@ int lseg_op_stats_finish(const int16_t* d_label, const float* d_best, const floa
 int lseg_op_corr_argmax_ragged(const void* d_g16pad, const void* d_text16, const float* d_scale, const int32_t* host_counts, int32_t* d_offsets,
                                int16_t* d_label, float* d_score, int16_t* d_label2, float* d_score2, float* d_lse, int B, int H, int W, int C,
                                void* d_ws, size_t ws_bytes, void* stream) {
-    return launch_corr_argmax_ragged(d_g16pad, d_text16, d_scale, host_counts, d_offsets, d_label, d_score, d_label2, d_score2, d_lse, B, H, W, C,
-                                     (hipStream_t)stream, d_ws, ws_bytes);
+    if (!host_counts) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: NULL pointer");       // (the entry would take one shared set)
+    return launch_corr_argmax(d_g16pad, d_text16, d_scale, CorrOut{d_label, d_score, d_label2, d_score2, d_lse}, B, 0, H, W, C, (hipStream_t)stream,
+                              d_ws, ws_bytes, nullptr, host_counts, d_offsets);
 }
 int lseg_op_corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2) {
     return corr_argmax_ragged_split(host_counts, B, H, W, conf, ws_bytes, cus, out2);

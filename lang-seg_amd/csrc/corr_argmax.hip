@@ -29,6 +29,11 @@
 //     scratch) -- and 16 B per pixel are written: label, score, runner-up label and score, lse = best + log(sum).  A label part writes
 //     the same five planes (16 B x pixels x splits) and the merge combines them in ascending order: top-2 by the same strict `>` rule,
 //     lse by log-add-exp.  The arg-max instantiation compiles to the instructions it had before the template parameter existed.
+// Around the kernel there is ONE of everything, each a template over the mode (CaMode: arg-max / CONF / LOSS): one host plan of a launch
+// (CaPlan: tiles, panels, label parts), one launch site (ca_launch, the six instantiations listed once in CA_VARIANTS), one merge of
+// the label parts (corr_argmax_merge_kernel), one fallback on planes in memory (seg_labels16_kernel).  The per-value rules -- the valid
+// target, the one-exp log-sum-exp step, the top-2 push, the log-add-exp, the write-out -- are device functions the three share, so
+// "the same bits" between the forms holds by construction.
 // LDS: T 49 920 + Rs 49 920 + Lr 54 016 + row taps 1 024 = 154 880 B of the CU's 160 KB.
 // Traffic per image at 120 x 120, K = 1000 (81 tiles, 21 panels): g 21 MB (halo included) from HBM, T 81 x 1 MB from L2, 1.4 MB written --
 // against the 922 MB logits write (and read) this replaces.  The panel-outer alternative would read g 15 MB x 21 panels and carry the
@@ -74,6 +79,27 @@ __host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_o
     return o;
 }
 
+// what a run keeps per pixel beside (best, arg): nothing / the runner-up and the exp-sum / the exp-sum and the target's logit
+enum class CaMode { ARGMAX, CONF, LOSS };
+inline CaMode ca_mode(const CorrOut& out, const CorrLoss* loss) {
+    return loss ? CaMode::LOSS : (out.label2 || out.score2 || out.lse) ? CaMode::CONF : CaMode::ARGMAX;
+}
+// bytes per output pixel of the planes a label part writes: label int16 + score fp32, CONF label2 int16 + score2 + lse fp32, LOSS lse + tlogit fp32
+constexpr size_t ca_part_bytes(CaMode m) { return 2 + 4 + (m == CaMode::CONF ? 2 + 4 + 4 : m == CaMode::LOSS ? 4 + 4 : 0); }
+
+// a pixel enters the loss iff its target is a label of the set at hand (label_stats_kernel's pixel_nll rule)
+__device__ __forceinline__ bool valid_target(long long t, int ignore_index, int K) {
+    return t != (long long)ignore_index && t >= 0 && t < (long long)K;
+}
+
+// one more value v into an online log-sum-exp whose running maximum is `best` (updated by the caller afterwards): one exp per value --
+// exp(-|v - best|) rescales the sum when v is the new maximum and is v's own term otherwise (best = -inf before the first value:
+// exp(-inf) = 0 and the sum starts at 1)
+__device__ __forceinline__ void lse_push(float& sum, float v, float best) {
+    const float e = __expf(-fabsf(v - best));
+    sum = v > best ? fmaf(sum, e, 1.f) : sum + e;
+}
+
 // CONF = the label-confidence instantiation (lseg_op_corr_argmax_conf): besides (best, arg) every owned pixel keeps the runner-up
 // (second, arg2) -- the largest value among the labels != arg, ties to the lower label, i.e. entry 1 of a stable descending sort over k
 // -- and the sum s of exp(value - best) over all labels seen, so that lse = best + log(s) (the running maximum of an online
@@ -82,7 +108,7 @@ __host__ __device__ inline int ca_end_out(float r, int first, int a_end, int n_o
 // RAGGED = per-image label sets of any size (lseg_op_corr_argmax_ragged): `offsets` int32 [B + 1] is the prefix sum of the images' label
 // counts; image b streams rows [offsets[b], offsets[b + 1]) of T_all only and reports labels local to its own list, and the kernel's K
 // (unused by the launcher there) gives way to the image's count.  A label part that lies beyond its image's count returns before it
-// touches anything: the merge kernels skip it (they read the same offsets), no identity element is ever written.  With RAGGED = false
+// touches anything: the merge kernel skips it (it reads the same offsets), no identity element is ever written.  With RAGGED = false
 // nothing of this is compiled: the shared-set instantiations keep their instructions and registers.
 //
 // LOSS = the cross-entropy instantiation (lseg_op_corr_argmax_loss; CONF = false): besides (best, arg) every owned pixel keeps the sum s of
@@ -178,7 +204,7 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
             int tg = 0xffff;
             if (j < nrow && cvalid) {
                 const long long t = target[((size_t)b * Ho + ys + j) * Wo + xo];
-                if (t != (long long)ignore_index && t >= 0 && t < (long long)K) tg = (int)t;
+                if (t != (long long)ignore_index && t >= 0 && t < (long long)K) tg = (int)t;   // valid_target, spelled out: the call reorders this body's code
             }
             tg16[j] = (int)((unsigned)tg << 16);
         }
@@ -338,8 +364,8 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
                         } else if constexpr (!CONF) {
                             if (lab0 + u < K && v > best[j]) { best[j] = v; arg[j] = lab0 + u; }      // first maximum wins
                         } else if (lab0 + u < K) {
-                            // one exp per value: exp(-|v - best|) rescales the sum when v is the new maximum and is v's own term otherwise
-                            // (best = -inf before the first label: exp(-inf) = 0 and the sum starts at 1)
+                            // lse_push spelled out with the branch it shares (as a call it costs this body scratch): one exp per value --
+                            // exp(-|v - best|) rescales the sum when v is the new maximum and is v's own term otherwise
                             const float e = __expf(-fabsf(v - best[j]));
                             if (v > best[j]) {                                                    // first maximum wins; the old one is the runner-up
                                 esum[j] = fmaf(esum[j], e, 1.f);
@@ -381,28 +407,21 @@ __global__ __launch_bounds__(256, 1) void corr_argmax_kernel(const uint16_t* __r
     }
 }
 
-// (label, score) planes of the label splits -> the final pair: ascending splits = ascending labels, strict `>` = the first maximum wins
-// ragged label sets (offsets != NULL): image i / img_pix owns ceil(count / split_labels) parts, the rest were never written and are not read
-__device__ inline int ca_parts_of(const int* __restrict__ offsets, int split_labels, unsigned img_pix, size_t i, int nsplit) {
-    if (!offsets) return nsplit;
-    const size_t b = i / img_pix;
-    const int parts = (offsets[b + 1] - offsets[b] + split_labels - 1) / split_labels;
-    return parts < nsplit ? parts : nsplit;
-}
-
-__global__ __launch_bounds__(256) void corr_argmax_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc, int nsplit, size_t n,
-                                                                int16_t* __restrict__ label, float* __restrict__ score,
-                                                                const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float m = wsc[i];
-        int16_t a = wl[i];
-        const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
-        for (int s = 1; s < parts; ++s) {
-            const float v = wsc[(size_t)s * n + i];
-            if (v > m) { m = v; a = wl[(size_t)s * n + i]; }
-        }
-        label[i] = a;
-        if (score) score[i] = m;
+// a pixel's results -> the planes of its mode, each but the label optional (the merge and the fallback; the streamed kernel's own
+// write-out forms lse only where it is wanted)
+template <CaMode MODE>
+__device__ __forceinline__ void ca_store(const CorrOut& out, size_t o, int a, float m, int a2, float m2, float l, float t) {
+    out.label[o] = (int16_t)a;
+    if (out.score) out.score[o] = m;
+    if constexpr (MODE == CaMode::CONF) {
+        if (out.label2) out.label2[o] = (int16_t)a2;
+        if (out.score2) out.score2[o] = m2;
+    }
+    if constexpr (MODE != CaMode::ARGMAX) {
+        if (out.lse) out.lse[o] = l;
+    }
+    if constexpr (MODE == CaMode::LOSS) {
+        if (out.tlogit) out.tlogit[o] = t;
     }
 }
 
@@ -416,56 +435,44 @@ __device__ inline void top2_push(float v, int k, float& best, int& arg, float& s
     arg = nb ? k : arg;
 }
 
-// the five planes of the label parts -> the final outputs.  Parts in ascending order = labels in ascending order: a part's winner and then
-// its runner-up are pushed like single labels (the runner-up can only matter when the winner became the new best); lse by log-add-exp
-__global__ __launch_bounds__(256) void corr_argmax_conf_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc,
-                                                                     const int16_t* __restrict__ wl2, const float* __restrict__ wsc2,
-                                                                     const float* __restrict__ wlse, int nsplit, size_t n,
-                                                                     int16_t* __restrict__ label, float* __restrict__ score,
-                                                                     int16_t* __restrict__ label2, float* __restrict__ score2, float* __restrict__ lse,
-                                                                     const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float m = wsc[i], m2 = wsc2[i], l = wlse[i];
-        int a = wl[i], a2 = wl2[i];
-        const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
-        for (int s = 1; s < parts; ++s) {
-            const size_t o = (size_t)s * n + i;
-            top2_push(wsc[o], wl[o], m, a, m2, a2);
-            top2_push(wsc2[o], wl2[o], m, a, m2, a2);                  // -inf (a part of one label) never enters
-            const float pl = wlse[o], hi = fmaxf(l, pl);
-            l = hi + log1pf(expf(-fabsf(l - pl)));
-        }
-        label[i] = (int16_t)a;
-        if (score) score[i] = m;
-        if (label2) label2[i] = (int16_t)a2;
-        if (score2) score2[i] = m2;
-        if (lse) lse[i] = l;
-    }
+// log(exp(l) + exp(pl)): the log-sum-exp of two label parts
+__device__ __forceinline__ float lse_add(float l, float pl) { return fmaxf(l, pl) + log1pf(expf(-fabsf(l - pl))); }
+
+// ragged label sets (offsets != NULL): image i / img_pix owns ceil(count / split_labels) parts, the rest were never written and are not read
+__device__ inline int ca_parts_of(const int* __restrict__ offsets, int split_labels, unsigned img_pix, size_t i, int nsplit) {
+    if (!offsets) return nsplit;
+    const size_t b = i / img_pix;
+    const int parts = (offsets[b + 1] - offsets[b] + split_labels - 1) / split_labels;
+    return parts < nsplit ? parts : nsplit;
 }
 
-// the four planes of the label parts of the LOSS instantiation -> the final outputs: the winner by the strict `>` of the arg-max merge, lse
-// by the log-add-exp of the CONF merge, tlogit by max -- exactly one part holds the target's label, every other part left -inf
-__global__ __launch_bounds__(256) void corr_argmax_loss_merge_kernel(const int16_t* __restrict__ wl, const float* __restrict__ wsc,
-                                                                     const float* __restrict__ wlse, const float* __restrict__ wtl, int nsplit,
-                                                                     size_t n, int16_t* __restrict__ label, float* __restrict__ score,
-                                                                     float* __restrict__ lse, float* __restrict__ tlogit,
-                                                                     const int* __restrict__ offsets, int split_labels, unsigned img_pix) {
+// the planes of the label parts (w, each [nsplit][n]) -> the final outputs.  Parts in ascending order = labels in ascending order: the
+// winner by strict `>`, the first maximum wins (CONF: a part's winner and then its runner-up are pushed like single labels -- the
+// runner-up can only matter when the winner became the new best); lse by log-add-exp; tlogit by max -- exactly one part holds the
+// target's label, every other part left -inf
+template <CaMode MODE>
+__global__ __launch_bounds__(256) void corr_argmax_merge_kernel(CorrOut w, CorrOut out, int nsplit, size_t n, const int* __restrict__ offsets,
+                                                                int split_labels, unsigned img_pix) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float m = wsc[i], l = wlse[i], t = wtl[i];
-        int16_t a = wl[i];
+        float m = w.score[i], m2 = -INFINITY, l = 0.f, t = 0.f;
+        int a = w.label[i], a2 = -1;
+        if constexpr (MODE == CaMode::CONF) { m2 = w.score2[i]; a2 = w.label2[i]; }
+        if constexpr (MODE != CaMode::ARGMAX) l = w.lse[i];
+        if constexpr (MODE == CaMode::LOSS) t = w.tlogit[i];
         const int parts = ca_parts_of(offsets, split_labels, img_pix, i, nsplit);
         for (int s = 1; s < parts; ++s) {
             const size_t o = (size_t)s * n + i;
-            const float v = wsc[o];
-            if (v > m) { m = v; a = wl[o]; }
-            const float pl = wlse[o], hi = fmaxf(l, pl);
-            l = hi + log1pf(expf(-fabsf(l - pl)));
-            t = fmaxf(t, wtl[o]);
+            if constexpr (MODE == CaMode::CONF) {
+                top2_push(w.score[o], w.label[o], m, a, m2, a2);
+                top2_push(w.score2[o], w.label2[o], m, a, m2, a2);      // -inf (a part of one label) never enters
+            } else {
+                const float v = w.score[o];
+                if (v > m) { m = v; a = w.label[o]; }
+            }
+            if constexpr (MODE != CaMode::ARGMAX) l = lse_add(l, w.lse[o]);
+            if constexpr (MODE == CaMode::LOSS) t = fmaxf(t, w.tlogit[o]);
         }
-        label[i] = a;
-        if (score) score[i] = m;
-        if (lse) lse[i] = l;
-        if (tlogit) tlogit[i] = t;
+        ca_store<MODE>(out, i, a, m, a2, m2, l, t);
     }
 }
 
@@ -487,7 +494,8 @@ inline void cl_plan(size_t n, size_t& chunk, int& groups) {
     groups = (int)((n + chunk - 1) / chunk);
 }
 
-__device__ inline void cl_wave_sum(double& s, unsigned& c) {
+template <typename Count>                                 // (unsigned in the reduction, double once the counts are partials)
+__device__ inline void cl_wave_sum(double& s, Count& c) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         s += __shfl_down(s, off, 64);
@@ -511,7 +519,7 @@ __global__ __launch_bounds__(CL_THREADS) void corr_loss_reduce_kernel(const floa
             const size_t b = i / img_pix;
             k = offsets[b + 1] - offsets[b];
         }
-        const bool valid = t != (long long)ignore_index && t >= 0 && t < (long long)k;
+        const bool valid = valid_target(t, ignore_index, k);
         const float l = lse[i], g = tlogit[i];
         if (valid) { s += (double)l - (double)g; ++c; }
         if (plane) plane[i] = valid ? l - g : 0.f;
@@ -532,18 +540,18 @@ __global__ __launch_bounds__(CL_THREADS) void corr_loss_reduce_kernel(const floa
 __global__ __launch_bounds__(64) void corr_loss_fold_kernel(const double* __restrict__ partial, int groups, double* __restrict__ nll) {
     double s = 0.0, c = 0.0;
     for (int i = threadIdx.x; i < groups; i += 64) { s += partial[2 * i]; c += partial[2 * i + 1]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_down(s, off, 64);
-        c += __shfl_down(c, off, 64);
-    }
+    cl_wave_sum(s, c);
     if (threadIdx.x == 0) { nll[0] = s; nll[1] = c; }
 }
 
-// the arg-max of the x2-upsampled logits read through the bilinear on the fly (seg_stats_kernel's `up` form, masks only) with an int16
-// label and an optional score: what the streamed kernel's callers get when the planes exist in memory
-__global__ __launch_bounds__(256) void seg_argmax16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
-                                                           int16_t* __restrict__ label, float* __restrict__ score) {
+// the fallback: what the streamed kernel's callers get when the (2h, 2w) planes exist in memory -- the x2-upsampled logits read through
+// the bilinear on the fly (seg_stats_kernel's `up` form), labels in ascending order through the streamed kernel's per-value rules: the
+// winner by strict `>`; CONF the runner-up through top2_push; CONF / LOSS the online log-sum-exp whose running maximum is the winner
+// (lse_push); LOSS tlogit = the value of the target's plane at this pixel, the very bilerp the loop meets at k = target (-inf where
+// the target is not valid).  K = 1: label2 = -1, score2 = -inf, lse = score
+template <CaMode MODE>
+__global__ __launch_bounds__(256) void seg_labels16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
+                                                           const long long* __restrict__ target, int ignore_index, CorrOut out) {
     const int Wo = 2 * w, HW = 4 * h * w;
     const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
     const size_t kstride = (size_t)h * w;
@@ -557,88 +565,26 @@ __global__ __launch_bounds__(256) void seg_argmax16_kernel(const float* __restri
         src_tap(rx, xo, w, x0, x1, lx);
         const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
         const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
-        float m = -INFINITY;
-        int arg = 0;
-        for (int k = 0; k < K; ++k) {
-            const float* cc = col + (size_t)k * kstride;
-            const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
-            if (v > m) { m = v; arg = k; }
+        int tg = -1;
+        if constexpr (MODE == CaMode::LOSS) {
+            const long long t = target[i];
+            if (valid_target(t, ignore_index, K)) tg = (int)t;
         }
-        label[i] = (int16_t)arg;
-        if (score) score[i] = m;
-    }
-}
-
-// seg_argmax16_kernel with the confidence outputs: the same values in the same order through top2_push and an online log-sum-exp whose
-// running maximum is `best` (one exp per value, as in the streamed kernel).  K = 1: label2 = -1, score2 = -inf, lse = score
-__global__ __launch_bounds__(256) void seg_conf16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix, int16_t* __restrict__ label,
-                                                         float* __restrict__ score, int16_t* __restrict__ label2, float* __restrict__ score2,
-                                                         float* __restrict__ lse) {
-    const int Wo = 2 * w, HW = 4 * h * w;
-    const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
-    const size_t kstride = (size_t)h * w;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % HW);
-        const size_t b = i / HW;
-        const int yo = p / Wo, xo = p - yo * Wo;
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_tap(ry, yo, h, y0, y1, ly);
-        src_tap(rx, xo, w, x0, x1, lx);
-        const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
-        const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
-        float m = -INFINITY, m2 = -INFINITY, es = 0.f;
+        float m = -INFINITY, m2 = -INFINITY, es = 0.f, tl = -INFINITY;
         int arg = 0, arg2 = -1;
         for (int k = 0; k < K; ++k) {
             const float* cc = col + (size_t)k * kstride;
             const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
-            const float e = __expf(-fabsf(v - m));
-            es = v > m ? fmaf(es, e, 1.f) : es + e;
-            top2_push(v, k, m, arg, m2, arg2);
+            if constexpr (MODE != CaMode::ARGMAX) lse_push(es, v, m);
+            if constexpr (MODE == CaMode::LOSS) tl = k == tg ? v : tl;
+            if constexpr (MODE == CaMode::CONF) {
+                top2_push(v, k, m, arg, m2, arg2);
+            } else if (v > m) {
+                m = v;
+                arg = k;
+            }
         }
-        label[i] = (int16_t)arg;
-        if (score) score[i] = m;
-        if (label2) label2[i] = m2 == -INFINITY ? (int16_t)-1 : (int16_t)arg2;
-        if (score2) score2[i] = m2;
-        if (lse) lse[i] = m + logf(es);
-    }
-}
-
-// seg_conf16_kernel's loss form, the outputs of the LOSS instantiation from planes in memory: the same sum (so the same lse bits as
-// seg_conf16_kernel), no runner-up, and tlogit = the value of the target's plane at this pixel (-inf where the target is not valid:
-// target == ignore_index or outside [0, K)) -- the very bilerp the loop would have met at k = target
-__global__ __launch_bounds__(256) void seg_loss16_kernel(const float* __restrict__ low, int K, int h, int w, size_t npix,
-                                                         const long long* __restrict__ target, int ignore_index, int16_t* __restrict__ label,
-                                                         float* __restrict__ score, float* __restrict__ lse, float* __restrict__ tlogit) {
-    const int Wo = 2 * w, HW = 4 * h * w;
-    const float ry = (float)(h - 1) / (float)(2 * h - 1), rx = (float)(w - 1) / (float)(2 * w - 1);
-    const size_t kstride = (size_t)h * w;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % HW);
-        const size_t b = i / HW;
-        const int yo = p / Wo, xo = p - yo * Wo;
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_tap(ry, yo, h, y0, y1, ly);
-        src_tap(rx, xo, w, x0, x1, lx);
-        const float* col = low + b * (size_t)K * kstride + (size_t)y0 * w + x0;
-        const int o01 = x1 - x0, o10 = (y1 - y0) * w, o11 = o10 + o01;
-        const long long t = target[i];
-        const int tg = t != (long long)ignore_index && t >= 0 && t < (long long)K ? (int)t : -1;
-        float m = -INFINITY, es = 0.f, tl = -INFINITY;
-        int arg = 0;
-        for (int k = 0; k < K; ++k) {
-            const float* cc = col + (size_t)k * kstride;
-            const float v = bilerp(cc[0], cc[o01], cc[o10], cc[o11], lx, ly);
-            const float e = __expf(-fabsf(v - m));
-            es = v > m ? fmaf(es, e, 1.f) : es + e;
-            tl = k == tg ? v : tl;
-            if (v > m) { m = v; arg = k; }
-        }
-        label[i] = (int16_t)arg;
-        if (score) score[i] = m;
-        if (lse) lse[i] = m + logf(es);
-        if (tlogit) tlogit[i] = tl;
+        ca_store<MODE>(out, i, arg, m, m2 == -INFINITY ? -1 : arg2, m2, m + logf(es), tl);
     }
 }
 
@@ -685,6 +631,81 @@ int ca_pick_split(int panels, long ntiles, size_t npix, size_t part_bytes, bool 
     return nsplit;
 }
 
+// the merge of the label parts and the fallback on planes in memory, by mode
+void (*const CA_MERGE[3])(CorrOut, CorrOut, int, size_t, const int*, int, unsigned) = {
+    corr_argmax_merge_kernel<CaMode::ARGMAX>, corr_argmax_merge_kernel<CaMode::CONF>, corr_argmax_merge_kernel<CaMode::LOSS>};
+void (*const CA_FALLBACK[3])(const float*, int, int, int, size_t, const long long*, int, CorrOut) = {
+    seg_labels16_kernel<CaMode::ARGMAX>, seg_labels16_kernel<CaMode::CONF>, seg_labels16_kernel<CaMode::LOSS>};
+
+// one launch: the tiles of the map, the panels of the (largest) label set and how they are split into parts of whole panels
+struct CaPlan {
+    int tiles_y, tiles_x;
+    long ntiles;               // over the batch
+    int panels, nsplit, split_labels;
+    size_t npix;               // output pixels of the batch = values per plane of one part
+    unsigned img_pix;          // of one image
+};
+CaPlan ca_plan(int B, int Kmax, int H, int W, CaMode mode, size_t ws_bytes, int cus) {
+    CaPlan p;
+    p.tiles_y = (2 * H + CA_LB - 1) / CA_LB;
+    p.tiles_x = (2 * W + CA_LB - 1) / CA_LB;
+    p.ntiles = (long)B * p.tiles_y * p.tiles_x;
+    p.img_pix = (unsigned)(16 * H * W);
+    p.npix = (size_t)B * p.img_pix;
+    p.panels = (Kmax + CA_P - 1) / CA_P;
+    p.nsplit = ca_pick_split(p.panels, p.ntiles, p.npix, ca_part_bytes(mode), ws_bytes > 0, ws_bytes, cus);
+    p.split_labels = (p.panels + p.nsplit - 1) / p.nsplit * CA_P;
+    return p;
+}
+
+// the planes the streamed kernel writes: the caller's when one workgroup per tile streams all labels, else the workspace's, each
+// [nsplit][npix] -- the fp32 planes first (score; CONF score2, lse; LOSS lse, tlogit), the int16 planes (label; CONF label2) behind them.
+// A part always writes all the planes of its mode
+CorrOut ca_part_planes(const CorrOut& out, void* ws, const CaPlan& p, CaMode mode) {
+    if (p.nsplit == 1) return out;
+    const size_t pn = (size_t)p.nsplit * p.npix;
+    float* f = reinterpret_cast<float*>(ws);
+    CorrOut w{};
+    w.score = f; f += pn;
+    if (mode == CaMode::CONF) { w.score2 = f; f += pn; }
+    if (mode != CaMode::ARGMAX) { w.lse = f; f += pn; }
+    if (mode == CaMode::LOSS) { w.tlogit = f; f += pn; }
+    w.label = reinterpret_cast<int16_t*>(f);
+    if (mode == CaMode::CONF) w.label2 = w.label + pn;
+    return w;
+}
+
+// what the streamed kernel reads (offsets: the device prefix sum of a ragged launch; target / ignore_index: LOSS)
+struct CaIn { const uint16_t* g; const uint16_t* T; const float* scale; int B, K, H, W; const int* offsets; const long long* target; int ignore_index; };
+
+// the one launch site.  A single part covers all labels (split_labels >= K) and its plane offset is 0: the same arguments serve both forms
+template <bool CONF, bool RAGGED, bool LOSS>
+void ca_launch(const CaPlan& p, const CaIn& in, const CorrOut& w, hipStream_t st) {
+    hipLaunchKernelGGL((corr_argmax_kernel<CONF, RAGGED, LOSS>), dim3((unsigned)(p.ntiles * p.nsplit)), dim3(256), CA_LDS, st, in.g, in.T, in.scale,
+                       w.label, w.score, in.B, in.K, in.H, in.W, p.tiles_y, p.tiles_x, p.nsplit, p.split_labels, p.npix, w.label2, w.score2, w.lse,
+                       in.offsets, in.target, in.ignore_index, w.tlogit);
+}
+
+// the instantiations, listed once: the opt-in to > 64 KB of dynamic LDS walks the list, the dispatch picks from it
+struct CaVariant { const void* kernel; void (*launch)(const CaPlan&, const CaIn&, const CorrOut&, hipStream_t); };
+template <bool CONF, bool RAGGED, bool LOSS = false>
+CaVariant ca_variant() { return {reinterpret_cast<const void*>(corr_argmax_kernel<CONF, RAGGED, LOSS>), ca_launch<CONF, RAGGED, LOSS>}; }
+const CaVariant CA_VARIANTS[6] = {ca_variant<false, false>(), ca_variant<true, false>(), ca_variant<false, true>(), ca_variant<true, true>(),
+                                  ca_variant<false, false, true>(), ca_variant<false, true, true>()};
+const CaVariant& ca_variant_of(CaMode mode, bool ragged) {
+    switch (mode) {
+        case CaMode::LOSS: return CA_VARIANTS[4 + ragged];
+        case CaMode::CONF: return CA_VARIANTS[2 * ragged + 1];
+        default: return CA_VARIANTS[2 * ragged];
+    }
+}
+
+// workgroups of the streaming kernels behind it (the merge, the fallback): grid-stride over npix pixels
+int ca_stream_grid(size_t npix) { return (int)std::min<size_t>((npix + 255) / 256, 256 * 16); }
+
+// the sum and the plane read the lse and tlogit planes; the sum writes its partials
+bool ca_reduction_ok(const float* lse, const CorrLoss& L) { return !(L.nll || L.nll_plane) || (lse && L.tlogit && (!L.nll || L.partial)); }
+
 // the offsets of a ragged launch travel as kernel arguments, 64 per launch: nothing of the caller's host memory is read after the call returns
 struct CaOffsetChunk { int v[64]; };
 __global__ __launch_bounds__(64) void corr_argmax_offsets_kernel(int* __restrict__ dst, CaOffsetChunk c, int n) {
@@ -710,151 +731,6 @@ static int launch_corr_loss_reduce(const float* lse, const CorrLoss& L, int K, c
     return 0;
 }
 
-// g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W]; label: int16 [B, 4H, 4W]; score: fp32 [B, 4H, 4W] or NULL
-// loss (optional): the LOSS instantiation -- lse as below, tlogit / nll_plane fp32 [B, 4H, 4W], nll double [2], each optional; the sum and the
-// plane read lse and tlogit, so both must be given with either, and the sum needs `partial` (corr_loss_plan's bytes).  A part takes 14
-// bytes per output pixel of the workspace (score, lse, tlogit fp32; label int16): 224 B H W bytes per part
-// ws (optional, ws_bytes): with 6 bytes x B x 16 H W per split the labels of a tile are split over up to 8 workgroups (whole panels each)
-// and merged afterwards -- a 120 x 120 map has only 81 tiles per image for 256 CUs; without it one workgroup per tile streams all K
-// label2 / score2 / lse (each optional): any of them selects the CONF instantiation; a part then takes 16 bytes per output pixel of the
-// workspace (score, score2, lse fp32; label, label2 int16) instead of 6: 256 B H W bytes per part
-// host_prefix / d_offsets (both or neither): ragged per-image label sets -- host_prefix int32 [B + 1] (host) is written to d_offsets (device)
-// on the stream once every check has passed, K is then the LARGEST count (it sizes the label parts) and T holds host_prefix[B] rows
-static int launch_corr_argmax_any(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2,
-                                  float* lse, int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes,
-                                  const int* host_prefix = nullptr, int* d_offsets = nullptr, const CorrLoss* loss = nullptr) {
-    const bool conf = !loss && (label2 || score2 || lse);
-    const bool ragged = host_prefix != nullptr;
-    const size_t part_bytes = loss ? 14 : conf ? 16 : 6;
-    if (!g || !T || !scale || !label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
-    if (loss) {
-        if (!loss->target) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL target");
-        if (label2 || score2) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the loss form keeps no runner-up");
-        if ((loss->nll || loss->nll_plane) && (!lse || !loss->tlogit || (loss->nll && !loss->partial)))
-            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the reduction reads the lse and tlogit planes and writes its partials");
-        if (((uintptr_t)loss->target | (uintptr_t)loss->nll | (uintptr_t)loss->partial) & 7)
-            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: target / nll / partials must be 8-byte aligned");
-    }
-    if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
-    if (!corr_argmax_supported(K, C)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: K=%d C=%d (C must be 512, K >= 1)", K, C);
-    if (B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "corr_argmax: B=%d H=%d W=%d", B, H, W);
-    const int tiles_y = (2 * H + CA_LB - 1) / CA_LB, tiles_x = (2 * W + CA_LB - 1) / CA_LB;
-    const long ntiles = (long)B * tiles_y * tiles_x;
-    if (ntiles >= (1L << 31) || (size_t)B * (H + 2) * (W + 2) * CA_C * 2 >= ((size_t)1 << 32) || (size_t)B * 16 * H * W >= ((size_t)1 << 31))
-        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: B=%d %dx%d exceeds the kernel's 32-bit offsets", B, H, W);
-    if (!ca_tiles_fit(H, 2 * H, 4 * H, CA_OMAX_Y) || !ca_tiles_fit(W, 2 * W, 4 * W, CA_OMAX_X))
-        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: %dx%d: a tile's footprint exceeds %dx%d base pixels", H, W, CA_BT, CA_BT);
-    int dev = 0;
-    LSEG_HIP_TRY(hipGetDevice(&dev));
-    static std::atomic<unsigned long long> attr_done{0};             // per-device opt-in to > 64 KB of dynamic LDS (cf. corr.hip)
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSEG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_argmax_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const size_t npix = (size_t)B * 16 * H * W;
-    const int panels = (K + CA_P - 1) / CA_P, cus = device_cu_count(dev) > 0 ? device_cu_count(dev) : 1;
-    const int nsplit = ca_pick_split(panels, ntiles, npix, part_bytes, ws != nullptr, ws_bytes, cus);
-    const int split_labels = (panels + nsplit - 1) / nsplit * CA_P;
-    const size_t pn = (size_t)nsplit * npix;                           // values per workspace plane
-    float* wsc = reinterpret_cast<float*>(ws);
-    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
-    const unsigned img_pix = (unsigned)(16 * H * W);
-    if (ragged) {
-        for (int i0 = 0; i0 <= B; i0 += 64) {
-            CaOffsetChunk ch;
-            const int n = std::min(64, B + 1 - i0);
-            for (int i = 0; i < 64; ++i) ch.v[i] = i < n ? host_prefix[i0 + i] : 0;
-            hipLaunchKernelGGL(corr_argmax_offsets_kernel, dim3(1), dim3(64), 0, st, d_offsets + i0, ch, n);
-            LSEG_HIP_TRY(hipGetLastError());
-        }
-    }
-    if (loss) {
-        // workspace planes: score, lse, tlogit (fp32), label (int16), each [nsplit][npix]; a part always writes all four
-        float *wlse = wsc + pn, *wtl = wsc + 2 * pn;
-        int16_t* wl = reinterpret_cast<int16_t*>(wsc + 3 * pn);
-        const bool split = nsplit > 1;
-        const long long* tgt = reinterpret_cast<const long long*>(loss->target);
-        if (ragged)
-            hipLaunchKernelGGL((corr_argmax_kernel<false, true, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                               (const uint16_t*)T, scale, split ? wl : label, split ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
-                               split ? split_labels : K, split ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, split ? wlse : lse,
-                               (const int*)d_offsets, tgt, loss->ignore_index, split ? wtl : loss->tlogit);
-        else
-            hipLaunchKernelGGL((corr_argmax_kernel<false, false, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                               (const uint16_t*)T, scale, split ? wl : label, split ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
-                               split ? split_labels : K, split ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, split ? wlse : lse,
-                               (const int*)nullptr, tgt, loss->ignore_index, split ? wtl : loss->tlogit);
-        LSEG_HIP_TRY(hipGetLastError());
-        if (split) {
-            hipLaunchKernelGGL(corr_argmax_loss_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, wlse, wtl, nsplit, npix, label, score, lse,
-                               loss->tlogit, (const int*)d_offsets, split_labels, img_pix);
-            LSEG_HIP_TRY(hipGetLastError());
-        }
-        return launch_corr_loss_reduce(lse, *loss, K, (const int*)d_offsets, img_pix, npix, st);
-    }
-    if (conf) {
-        // workspace planes: score, score2, lse (fp32), label, label2 (int16), each [nsplit][npix]; a part always writes all five
-        float *wsc2 = wsc + pn, *wlse = wsc + 2 * pn;
-        int16_t *wl = reinterpret_cast<int16_t*>(wsc + 3 * pn), *wl2 = wl + pn;
-        if (ragged && nsplit > 1)
-            hipLaunchKernelGGL((corr_argmax_kernel<true, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                               (const uint16_t*)T, scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse,
-                               (const int*)d_offsets);
-        else if (ragged)
-            hipLaunchKernelGGL((corr_argmax_kernel<true, true>), dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
-                               scale, label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse, (const int*)d_offsets);
-        else if (nsplit > 1)
-            hipLaunchKernelGGL((corr_argmax_kernel<true, false>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                               (const uint16_t*)T, scale, wl, wsc, B, K, H, W, tiles_y, tiles_x, nsplit, split_labels, npix, wl2, wsc2, wlse,
-                               (const int*)nullptr);
-        else
-            hipLaunchKernelGGL((corr_argmax_kernel<true, false>), dim3((unsigned)ntiles), dim3(256), CA_LDS, st, (const uint16_t*)g, (const uint16_t*)T,
-                               scale, label, score, B, K, H, W, tiles_y, tiles_x, 1, K, (size_t)0, label2, score2, lse, (const int*)nullptr);
-        LSEG_HIP_TRY(hipGetLastError());
-        if (nsplit > 1) {
-            hipLaunchKernelGGL(corr_argmax_conf_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, wl2, wsc2, wlse, nsplit, npix, label, score, label2,
-                               score2, lse, (const int*)d_offsets, split_labels, img_pix);
-            LSEG_HIP_TRY(hipGetLastError());
-        }
-        return 0;
-    }
-    int16_t* wl = nsplit > 1 ? reinterpret_cast<int16_t*>(wsc + pn) : nullptr;
-    if (ragged)
-        hipLaunchKernelGGL((corr_argmax_kernel<false, true>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                           (const uint16_t*)T, scale, nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
-                           nsplit > 1 ? split_labels : K, nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr,
-                           (const int*)d_offsets);
-    else
-        hipLaunchKernelGGL((corr_argmax_kernel<false, false>), dim3((unsigned)(ntiles * nsplit)), dim3(256), CA_LDS, st, (const uint16_t*)g,
-                           (const uint16_t*)T, scale, nsplit > 1 ? wl : label, nsplit > 1 ? wsc : score, B, K, H, W, tiles_y, tiles_x, nsplit,
-                           nsplit > 1 ? split_labels : K, nsplit > 1 ? npix : (size_t)0, (int16_t*)nullptr, (float*)nullptr, (float*)nullptr,
-                           (const int*)nullptr);
-    LSEG_HIP_TRY(hipGetLastError());
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(corr_argmax_merge_kernel, dim3(grid), dim3(256), 0, st, wl, wsc, nsplit, npix, label, score, (const int*)d_offsets,
-                           split_labels, img_pix);
-        LSEG_HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
-                       hipStream_t st, void* ws, size_t ws_bytes) {
-    return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, nullptr, B, K, H, W, C, st, ws, ws_bytes);
-}
-
-// launch_corr_argmax + the runner-up (label2 int16 / score2 fp32) and lse fp32 = log-sum-exp over all K, each [B, 4H, 4W] or NULL
-int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
-                            int B, int K, int H, int W, int C, hipStream_t st, void* ws, size_t ws_bytes) {
-    return launch_corr_argmax_any(g, T, scale, label, score, label2, score2, lse, B, K, H, W, C, st, ws, ws_bytes);
-}
-
 // the counts of a ragged launch -> their prefix sum (B + 1 entries) and the largest; LSEG_ERR_INVALID for a count outside [1, 32767]
 static int ca_ragged_prefix(const int32_t* host_counts, int B, std::vector<int>& prefix, int& kmax) {
     if (!host_counts) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: NULL counts");
@@ -874,18 +750,78 @@ static int ca_ragged_prefix(const int32_t* host_counts, int B, std::vector<int>&
     return 0;
 }
 
-// per-image label sets of any size: image b against rows [sum counts[0..b), + counts[b]) of T, labels local to its own list.
-// host_counts int32 [B] on the HOST (validated here, before anything is launched); d_offsets int32 [B + 1] device scratch the launch fills
-// with their prefix sum on the stream.  label2 / score2 / lse all NULL = the plain arg-max instantiation.
-int launch_corr_argmax_ragged(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
-                              float* score, int16_t* label2, float* score2, float* lse, int B, int H, int W, int C, hipStream_t st, void* ws,
-                              size_t ws_bytes) {
-    if (!g || !T || !scale || !label || !d_offsets || !host_counts) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged: NULL pointer");
-    if (C != CA_C) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_ragged: C=%d (C must be 512)", C);
+// The streamed route, every form of it.  g: padded NHWC fp16 [B, H+2, W+2, 512]; T: fp16 [K, 512]; scale: fp32 [B, 2H, 2W].
+// out: label int16 [B, 4H, 4W] and, each optional, score fp32 / label2 int16 / score2 fp32 / lse fp32 of that shape.  The mode follows from
+// what is asked for: `loss` = the LOSS instantiation (no runner-up; out.tlogit is taken from loss->tlogit), else any of label2 / score2 /
+// lse = CONF, else the arg-max.
+// loss (optional): tlogit / nll_plane fp32 [B, 4H, 4W], nll double [2], each optional; the sum and the plane read lse and tlogit, so both
+// must be given with either, and the sum needs `partial` (corr_loss_plan's bytes)
+// ws (optional, ws_bytes): with ca_part_bytes(mode) x B x 16 H W bytes per part the labels of a tile are split over up to 8 workgroups
+// (whole panels each, planes as ca_part_planes lays them out) and merged afterwards -- a 120 x 120 map has only 81 tiles per image for
+// 256 CUs; without it one workgroup per tile streams all K
+// host_counts / d_offsets (both or neither): ragged per-image label sets -- image b against host_counts[b] consecutive rows of T, labels
+// local to its own list.  host_counts int32 [B] on the HOST is validated here, before anything is launched; its prefix sum is written
+// to d_offsets (device, int32 [B + 1]) on the stream once every check has passed.  K is unused: the LARGEST count sizes the label parts
+int launch_corr_argmax(const void* g, const void* T, const float* scale, const CorrOut& out_, int B, int K, int H, int W, int C, hipStream_t st,
+                       void* ws, size_t ws_bytes, const CorrLoss* loss, const int32_t* host_counts, int* d_offsets) {
+    const bool ragged = host_counts != nullptr;
+    CorrOut out = out_;
+    out.tlogit = loss ? loss->tlogit : nullptr;
+    const CaMode mode = ca_mode(out, loss);
     std::vector<int> prefix;
-    int kmax = 0;
-    if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
-    return launch_corr_argmax_any(g, T, scale, label, score, label2, score2, lse, B, kmax, H, W, C, st, ws, ws_bytes, prefix.data(), d_offsets);
+    if (ragged) {
+        const char* who = loss ? "corr_argmax_loss" : "corr_argmax_ragged";
+        if (!g || !T || !scale || !out.label || !d_offsets) return set_error(LSEG_ERR_INVALID, "%s: NULL pointer", who);
+        if (C != CA_C) return set_error(LSEG_ERR_UNSUPPORTED, "%s: C=%d (C must be 512)", who, C);
+        if (const int r = ca_ragged_prefix(host_counts, B, prefix, K)) return r;
+    }
+    if (!g || !T || !scale || !out.label) return set_error(LSEG_ERR_INVALID, "corr_argmax: NULL pointer");
+    if (loss) {
+        if (!loss->target) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL target");
+        if (out.label2 || out.score2) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the loss form keeps no runner-up");
+        if (!ca_reduction_ok(out.lse, *loss))
+            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: the reduction reads the lse and tlogit planes and writes its partials");
+        if (((uintptr_t)loss->target | (uintptr_t)loss->nll | (uintptr_t)loss->partial) & 7)
+            return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: target / nll / partials must be 8-byte aligned");
+    }
+    if (K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: int16 labels need K <= 32767 (K=%d)", K);
+    if (!corr_argmax_supported(K, C)) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: K=%d C=%d (C must be 512, K >= 1)", K, C);
+    if (B < 1 || H < 2 || W < 2) return set_error(LSEG_ERR_INVALID, "corr_argmax: B=%d H=%d W=%d", B, H, W);
+    // (there are fewer tiles than base pixels, ceil(2H / 28) <= H: the bound on the output pixels keeps their number far below 2^31 too)
+    if ((size_t)B * (H + 2) * (W + 2) * CA_C * 2 >= ((size_t)1 << 32) || (size_t)B * 16 * H * W >= ((size_t)1 << 31))
+        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: B=%d %dx%d exceeds the kernel's 32-bit offsets", B, H, W);
+    if (!ca_tiles_fit(H, 2 * H, 4 * H, CA_OMAX_Y) || !ca_tiles_fit(W, 2 * W, 4 * W, CA_OMAX_X))
+        return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax: %dx%d: a tile's footprint exceeds %dx%d base pixels", H, W, CA_BT, CA_BT);
+    int dev = 0;
+    LSEG_HIP_TRY(hipGetDevice(&dev));
+    static std::atomic<unsigned long long> attr_done{0};             // per-device opt-in to > 64 KB of dynamic LDS (cf. corr.hip)
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+        for (const CaVariant& v : CA_VARIANTS) LSEG_HIP_TRY(hipFuncSetAttribute(v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_done.fetch_or(bit, std::memory_order_release);
+    }
+    const CaPlan p = ca_plan(B, K, H, W, mode, ws ? ws_bytes : 0, device_cu_count(dev) > 0 ? device_cu_count(dev) : 1);
+    if (ragged) {
+        for (int i0 = 0; i0 <= B; i0 += 64) {
+            CaOffsetChunk ch;
+            const int n = std::min(64, B + 1 - i0);
+            for (int i = 0; i < 64; ++i) ch.v[i] = i < n ? prefix[i0 + i] : 0;
+            hipLaunchKernelGGL(corr_argmax_offsets_kernel, dim3(1), dim3(64), 0, st, d_offsets + i0, ch, n);
+            LSEG_HIP_TRY(hipGetLastError());
+        }
+    }
+    const int* offsets = ragged ? d_offsets : nullptr;
+    const CaIn in{(const uint16_t*)g, (const uint16_t*)T, scale, B, K, H, W, offsets, loss ? reinterpret_cast<const long long*>(loss->target) : nullptr,
+                  loss ? loss->ignore_index : 0};
+    const CorrOut w = ca_part_planes(out, ws, p, mode);
+    ca_variant_of(mode, ragged).launch(p, in, w, st);
+    LSEG_HIP_TRY(hipGetLastError());
+    if (p.nsplit > 1) {
+        const auto merge = CA_MERGE[(int)mode];
+        hipLaunchKernelGGL(merge, dim3(ca_stream_grid(p.npix)), dim3(256), 0, st, w, out, p.nsplit, p.npix, offsets, p.split_labels, p.img_pix);
+        LSEG_HIP_TRY(hipGetLastError());
+    }
+    return loss ? launch_corr_loss_reduce(out.lse, *loss, K, offsets, p.img_pix, p.npix, st) : 0;
 }
 
 // the label split a ragged launch of this shape would take, without a device: out2 = {parts, labels per part}.  Part s of image b covers the
@@ -896,11 +832,9 @@ int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, in
     int kmax = 0;
     if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
     if (H < 2 || W < 2 || cus < 1) return set_error(LSEG_ERR_INVALID, "corr_argmax_ragged_split: H=%d W=%d cus=%d", H, W, cus);
-    const long ntiles = (long)B * ((2 * H + CA_LB - 1) / CA_LB) * ((2 * W + CA_LB - 1) / CA_LB);
-    const int panels = (kmax + CA_P - 1) / CA_P;
-    const int nsplit = ca_pick_split(panels, ntiles, (size_t)B * 16 * H * W, conf ? 16 : 6, ws_bytes > 0, ws_bytes, cus);
-    out2[0] = nsplit;
-    out2[1] = (panels + nsplit - 1) / nsplit * CA_P;
+    const CaPlan p = ca_plan(B, kmax, H, W, conf ? CaMode::CONF : CaMode::ARGMAX, ws_bytes, cus);
+    out2[0] = p.nsplit;
+    out2[1] = p.split_labels;
     return 0;
 }
 
@@ -914,23 +848,9 @@ void corr_loss_plan(size_t npix, int64_t* out4) {
 
 size_t corr_loss_partial_bytes_max() { return (size_t)CL_MAX_GROUPS * 2 * sizeof(double); }
 
-// launch_corr_argmax(_ragged) with the cross-entropy: host_counts NULL = one label set of K rows, else the ragged form (K unused, d_offsets
-// required).  lse optional as in launch_corr_argmax_conf; the rest of the outputs in `loss` (see launch_corr_argmax_any)
-int launch_corr_argmax_loss(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
-                            float* score, float* lse, const CorrLoss& loss, int B, int K, int H, int W, int C, hipStream_t st, void* ws,
-                            size_t ws_bytes) {
-    if (!host_counts) return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, lse, B, K, H, W, C, st, ws, ws_bytes, nullptr, nullptr, &loss);
-    if (!g || !T || !scale || !label || !d_offsets) return set_error(LSEG_ERR_INVALID, "corr_argmax_loss: NULL pointer");
-    if (C != CA_C) return set_error(LSEG_ERR_UNSUPPORTED, "corr_argmax_loss: C=%d (C must be 512)", C);
-    std::vector<int> prefix;
-    int kmax = 0;
-    if (const int r = ca_ragged_prefix(host_counts, B, prefix, kmax)) return r;
-    return launch_corr_argmax_any(g, T, scale, label, score, nullptr, nullptr, lse, B, kmax, H, W, C, st, ws, ws_bytes, prefix.data(), d_offsets, &loss);
-}
-
 // the caller's one workspace of lseg_op_corr_argmax_loss, in this order, each piece rounded up to 256 bytes: the offsets of a ragged call
 // (B + 1 int32), the reduction's partials (when the sum is wanted), an lse and a tlogit plane the caller did not pass while asking for
-// the sum or the plane (fp32 [B, 4H, 4W] each), and behind them `parts` label parts of 224 B H W bytes
+// the sum or the plane (fp32 [B, 4H, 4W] each), and behind them `parts` label parts of the LOSS mode (ca_part_bytes per output pixel)
 static size_t cl_up(size_t v) { return (v + 255) / 256 * 256; }
 size_t corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts) {
     if (B < 1 || H < 1 || W < 1 || temp_planes < 0 || temp_planes > 2 || parts < 0) return 0;
@@ -938,7 +858,7 @@ size_t corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, 
     int64_t plan[4];
     corr_loss_plan(npix, plan);
     return (ragged ? cl_up(((size_t)B + 1) * 4) : 0) + (want_nll ? cl_up((size_t)plan[3]) : 0) + (size_t)temp_planes * cl_up(npix * 4) +
-           (parts > 1 ? (size_t)parts * npix * 14 : 0);
+           (parts > 1 ? (size_t)parts * npix * ca_part_bytes(CaMode::LOSS) : 0);
 }
 
 int corr_argmax_loss_op(const void* g, const void* T, const float* scale, const int64_t* target, int ignore_index, const int32_t* host_counts,
@@ -963,49 +883,29 @@ int corr_argmax_loss_op(const void* g, const void* T, const float* scale, const 
     if (red && !lse) lse = reinterpret_cast<float*>(take(npix * 4));
     if (red && !tlogit) L.tlogit = reinterpret_cast<float*>(take(npix * 4));
     const size_t rest = ws ? ws_bytes - head : 0;
-    return launch_corr_argmax_loss(g, T, scale, host_counts, d_offsets, label, score, lse, L, B, K, H, W, C, st, rest ? p : nullptr, rest);
+    return launch_corr_argmax(g, T, scale, CorrOut{label, score, nullptr, nullptr, lse}, B, K, H, W, C, st, rest ? p : nullptr, rest, &L, host_counts,
+                              d_offsets);
 }
 
-// launch_seg_conf16's loss form: label / score / lse as there, tlogit / nll_plane / nll as launch_corr_argmax_loss (one label set of K planes
-// per image: a fixed number of labels per image is K of them with targets in [0, K))
-int launch_seg_loss16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, float* lse, const CorrLoss& loss, hipStream_t st) {
-    if (!low || !label || !loss.target) return set_error(LSEG_ERR_INVALID, "seg_loss16: NULL pointer");
-    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_loss16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
-    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_loss16: B=%d h=%d w=%d", B, h, w);
-    if ((loss.nll || loss.nll_plane) && (!lse || !loss.tlogit || (loss.nll && !loss.partial)))
-        return set_error(LSEG_ERR_INVALID, "seg_loss16: the reduction reads the lse and tlogit planes and writes its partials");
+// The fallback on planes in memory, the streamed route's outputs in its three modes (chosen as there): low fp32 [B, K, h, w] = the
+// (2h, 2w) logits of the engine -> out's planes [B, 2h, 2w]; loss as launch_corr_argmax (one label set of K planes per image: a fixed
+// number of labels per image is K of them with targets in [0, K))
+int launch_seg_labels16(const float* low, int B, int K, int h, int w, const CorrOut& out_, const CorrLoss* loss, hipStream_t st) {
+    CorrOut out = out_;
+    out.tlogit = loss ? loss->tlogit : nullptr;
+    const CaMode mode = ca_mode(out, loss);
+    const char* who = mode == CaMode::LOSS ? "seg_loss16" : mode == CaMode::CONF ? "seg_conf16" : "seg_argmax16";
+    if (!low || !out.label || (loss && !loss->target)) return set_error(LSEG_ERR_INVALID, "%s: NULL pointer", who);
+    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "%s: int16 labels need 1 <= K <= 32767 (K=%d)", who, K);
+    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "%s: B=%d h=%d w=%d", who, B, h, w);
+    if (loss && !ca_reduction_ok(out.lse, *loss))
+        return set_error(LSEG_ERR_INVALID, "%s: the reduction reads the lse and tlogit planes and writes its partials", who);
     const size_t npix = (size_t)B * 4 * h * w;
-    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(seg_loss16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, reinterpret_cast<const long long*>(loss.target),
-                       loss.ignore_index, label, score, lse, loss.tlogit);
+    const auto kernel = CA_FALLBACK[(int)mode];
+    hipLaunchKernelGGL(kernel, dim3(ca_stream_grid(npix)), dim3(256), 0, st, low, K, h, w, npix,
+                       loss ? reinterpret_cast<const long long*>(loss->target) : nullptr, loss ? loss->ignore_index : 0, out);
     LSEG_HIP_TRY(hipGetLastError());
-    return launch_corr_loss_reduce(lse, loss, K, nullptr, (unsigned)(4 * h * w), npix, st);
-}
-
-// low: fp32 [B, K, h, w] (the (2h, 2w) logits of the engine); label int16 [B, 2h, 2w]; score fp32 [B, 2h, 2w] or NULL
-int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st) {
-    if (!low || !label) return set_error(LSEG_ERR_INVALID, "seg_argmax16: NULL pointer");
-    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_argmax16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
-    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_argmax16: B=%d h=%d w=%d", B, h, w);
-    const size_t npix = (size_t)B * 4 * h * w;
-    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(seg_argmax16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, label, score);
-    LSEG_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// launch_seg_argmax16 + label2 int16 / score2 fp32 / lse fp32 [B, 2h, 2w], each or NULL
-int launch_seg_conf16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
-                      hipStream_t st) {
-    if (!label2 && !score2 && !lse) return launch_seg_argmax16(low, B, K, h, w, label, score, st);
-    if (!low || !label) return set_error(LSEG_ERR_INVALID, "seg_conf16: NULL pointer");
-    if (K < 1 || K > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "seg_conf16: int16 labels need 1 <= K <= 32767 (K=%d)", K);
-    if (B < 1 || h < 2 || w < 2) return set_error(LSEG_ERR_INVALID, "seg_conf16: B=%d h=%d w=%d", B, h, w);
-    const size_t npix = (size_t)B * 4 * h * w;
-    const int grid = (int)std::min<size_t>((npix + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(seg_conf16_kernel, dim3(grid), dim3(256), 0, st, low, K, h, w, npix, label, score, label2, score2, lse);
-    LSEG_HIP_TRY(hipGetLastError());
-    return 0;
+    return loss ? launch_corr_loss_reduce(out.lse, *loss, K, nullptr, (unsigned)(4 * h * w), npix, st) : 0;
 }
 
 }  // namespace lseg

@@ -106,7 +106,7 @@ public:
     // nscale_ -- into the caller's buffers; no text is read, the gram is pixel_gram's whatever K is set
     struct HeldOut { void* feat; float* scale; };
     // loss (lseg_forward_labels_loss; needs label_out, excludes conf's runner-up): the cross-entropy beside the arg-max -- conf->lse is its
-    // lse output, the rest is ops.h' CorrLoss; streamed where the labels stream, seg_loss16 on the planes in memory elsewhere
+    // lse output, the rest is ops.h' CorrLoss; streamed where the labels stream, seg_labels16 on the planes in memory elsewhere
     int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
                 float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr, const HeldOut* held = nullptr,
                 const CorrLoss* loss = nullptr);

@@ -1038,6 +1038,7 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
 int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
                     float* low_out, const LabelConf* conf, const HeldOut* held, const CorrLoss* loss) {
     const LabelConf cf = conf ? *conf : LabelConf{nullptr, nullptr, nullptr};
+    const CorrOut out16{label_out, score_out, cf.label2, cf.score2, cf.lse, nullptr};   // the int16 masks and what rides with them
     if ((cf.label2 || cf.score2 || cf.lse) && !label_out) return set_error(LSEG_ERR_INVALID, "the confidence outputs need the label output");
     if (loss && (!label_out || !loss->target || cf.label2 || cf.score2 || logits || argmax_out || low_out || held))
         return set_error(LSEG_ERR_INVALID, "the loss outputs need the label output and a target, and come with no other output");
@@ -1207,10 +1208,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
             // per-image label sets of any size (check_ragged let only the streamed labels through): the scale plane from pixel_gram, as for
             // K > 157 above -- corr_planes has no per-image form; low_ is the workspace of the label parts, sized from the largest list
             const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
-            if (loss) TRY(launch_corr_argmax_loss(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.lse, *loss, B, 0, lh_[0],
-                                                  lw_[0], c.out_c, st, low_, ws_bytes));
-            else TRY(launch_corr_argmax_ragged(g16pad_, tnorm_, nscale_, groups_.data(), d_goff_, label_out, score_out, cf.label2, cf.score2, cf.lse, B,
-                                               lh_[0], lw_[0], c.out_c, st, low_, ws_bytes));
+            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, out16, B, 0, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, loss, groups_.data(), d_goff_));
             labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
@@ -1218,10 +1216,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
             // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
             const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
-            if (loss) TRY(launch_corr_argmax_loss(g16pad_, tnorm_, nscale_, nullptr, nullptr, label_out, score_out, cf.lse, *loss, B, K_, lh_[0], lw_[0],
-                                                  c.out_c, st, low_, ws_bytes));
-            else TRY(launch_corr_argmax_conf(g16pad_, tnorm_, nscale_, label_out, score_out, cf.label2, cf.score2, cf.lse, B, K_, lh_[0], lw_[0], c.out_c,
-                                             st, low_, ws_bytes));
+            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, out16, B, K_, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, loss));
             labels_only_ = true; last_low_ = nullptr; last_kout_ = K_;
             prof_end(PF_FWD, fwd0, 0.0, st);
             return 0;
@@ -1304,8 +1299,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     if (argmax_out && Kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", Kout);
     if (argmax_out) TRY(launch_seg_stats_ex(low, nullptr, B, Kout, 4 * hw1, -1, nullptr, nullptr, argmax_out, 1, h1, w1, st));
     // the int16 form, on the planes in memory (with the runner-up and the log-sum-exp when lseg_forward_labels_conf asks for them)
-    if (label_out && loss) TRY(launch_seg_loss16(low, B, Kout, h1, w1, label_out, score_out, cf.lse, *loss, st));
-    else if (label_out) TRY(launch_seg_conf16(low, B, Kout, h1, w1, label_out, score_out, cf.label2, cf.score2, cf.lse, st));
+    if (label_out) TRY(launch_seg_labels16(low, B, Kout, h1, w1, out16, loss, st));
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
     if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
     // every other schedule (head blocks, the full-resolution correlation, debug / split-precision) has them in engine memory: a copy
@@ -1315,7 +1309,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
 }
 
 // lseg_forward_labels_loss: the labels forward with the cross-entropy (streamed: the LOSS instantiation of corr_argmax.hip; elsewhere
-// seg_loss16 on the planes in memory), then the counters of lseg_op_label_stats from the label map just written
+// seg_labels16's loss form on the planes in memory), then the counters of lseg_op_label_stats from the label map just written
 int Engine::forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out,
                                 float* lse_out, float* nll_plane_out, double* nll, int64_t* counts, hipStream_t st) {
     if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_forward_labels_loss is an inference feature (train mode is on: lseg_train_loss has the loss)");

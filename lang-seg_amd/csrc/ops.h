@@ -132,37 +132,32 @@ int launch_seg_stats(const float* scores, const int64_t* target, int B, int K, i
 // [B, 2H, 2W] (launch_norm_scale_plane) -> label int16 / score fp32 (optional) [B, 4H, 4W], no label planes in memory
 bool corr_argmax_supported(int K, int C);
 void corr_argmax_geometry(int* out8);
-int launch_corr_argmax(const void* g, const void* T, const float* scale, int16_t* label, float* score, int B, int K, int H, int W, int C,
-                       hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);   // ws: label-split planes, 6 B x B x 16 H W each (optional)
-// the int16 form of launch_seg_stats_ex's mask output (up = 1, no target): low fp32 [B, K, h, w] -> label / score (optional) [B, 2h, 2w]
-int launch_seg_argmax16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, hipStream_t st);
-// label confidence: the two above + the runner-up (label2 int16 / score2 fp32: entry 1 of a stable descending sort over k; -1 / -inf when
-// K = 1) and lse fp32 = log-sum-exp over all K, each the outputs' shape or NULL.  ws: 16 B x B x 16 H W per label part
-int launch_corr_argmax_conf(const void* g, const void* T, const float* scale, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
-                            int B, int K, int H, int W, int C, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
-int launch_seg_conf16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, int16_t* label2, float* score2, float* lse,
-                      hipStream_t st);
-// ragged per-image label sets: image b against host_counts[b] consecutive rows of T, labels local to its list.  host_counts int32 [B] on
-// the host (each in [1, 32767]); d_offsets int32 [B + 1] device scratch, filled with their prefix sum on the stream.  label2 / score2 / lse
-// all NULL = the arg-max instantiation.  ws as above, the parts sized from the largest count
-int launch_corr_argmax_ragged(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
-                              float* score, int16_t* label2, float* score2, float* lse, int B, int H, int W, int C, hipStream_t st,
-                              void* ws = nullptr, size_t ws_bytes = 0);
-// host only: out2 = {label parts, labels per part} of that launch when it plans for `cus` compute units
-int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2);
-// the cross-entropy on the streamed route (the LOSS instantiation; no runner-up): beside label / score / lse, tlogit fp32 = the logit of the
-// pixel's target label (-inf where the target is not valid: == ignore_index or outside [0, K), ragged: [0, count_b)), nll_plane fp32 =
-// lse - tlogit (0 where not valid) and nll double [2] = {sum over the valid pixels of double(lse) - double(tlogit), their number} in a
-// fixed order (partial: corr_loss_plan's bytes of device scratch).  tlogit / nll_plane / nll each optional; the sum and the plane read the
-// lse and tlogit planes, so those must be given with either.  target int64 [B, 4H, 4W].  ws: 14 B x B x 16 H W per label part
+// The outputs of the route, each the maps' shape: label int16 always; score fp32, and for label confidence the runner-up (label2 int16 /
+// score2 fp32: entry 1 of a stable descending sort over k; -1 / -inf when K = 1) and lse fp32 = log-sum-exp over all K, each optional.
+// tlogit belongs to the loss form: the launchers take it from CorrLoss, callers leave it NULL
+struct CorrOut { int16_t* label; float* score; int16_t* label2; float* score2; float* lse; float* tlogit; };
+// the cross-entropy (no runner-up with it): beside label / score / lse, tlogit fp32 = the logit of the pixel's target label (-inf where the
+// target is not valid: == ignore_index or outside [0, K), ragged: [0, count_b)), nll_plane fp32 = lse - tlogit (0 where not valid) and
+// nll double [2] = {sum over the valid pixels of double(lse) - double(tlogit), their number} in a fixed order (partial: corr_loss_plan's
+// bytes of device scratch).  tlogit / nll_plane / nll each optional; the sum and the plane read the lse and tlogit planes, so those must
+// be given with either.  target int64, the maps' shape
 struct CorrLoss { const int64_t* target; int ignore_index; float* tlogit; float* nll_plane; double* nll; double* partial; };
 void corr_loss_plan(size_t npix, int64_t* out4);          // host only: {threads, pixels per workgroup, workgroups, bytes of partials}
 size_t corr_loss_partial_bytes_max();                     // the partials of the largest plan
-int launch_corr_argmax_loss(const void* g, const void* T, const float* scale, const int32_t* host_counts, int* d_offsets, int16_t* label,
-                            float* score, float* lse, const CorrLoss& loss, int B, int K, int H, int W, int C, hipStream_t st,
-                            void* ws = nullptr, size_t ws_bytes = 0);   // host_counts NULL: one label set of K rows; else ragged (K unused)
-int launch_seg_loss16(const float* low, int B, int K, int h, int w, int16_t* label, float* score, float* lse, const CorrLoss& loss, hipStream_t st);
-// lseg_op_corr_argmax_loss: the launch above with everything it needs beside the outputs carved from ONE caller workspace
+// the ONE streamed entry, maps [B, 4H, 4W].  What is asked for selects the kernel's mode: loss = the cross-entropy form, else any of
+// label2 / score2 / lse = label confidence, else the arg-max.  ws (optional): room for the label parts of a tile, per part and output
+// pixel the planes of the mode (ca_part_bytes there: 6 / 16 / 14 bytes).  host_counts / d_offsets (both or neither) = ragged per-image label sets: image
+// b against host_counts[b] consecutive rows of T, labels local to its list; host_counts int32 [B] on the host (each in [1, 32767]),
+// d_offsets int32 [B + 1] device scratch, filled with their prefix sum on the stream; K is unused, the parts are sized from the largest count
+int launch_corr_argmax(const void* g, const void* T, const float* scale, const CorrOut& out, int B, int K, int H, int W, int C, hipStream_t st,
+                       void* ws = nullptr, size_t ws_bytes = 0, const CorrLoss* loss = nullptr, const int32_t* host_counts = nullptr,
+                       int* d_offsets = nullptr);
+// host only: out2 = {label parts, labels per part} of a ragged launch when it plans for `cus` compute units
+int corr_argmax_ragged_split(const int32_t* host_counts, int B, int H, int W, int conf, size_t ws_bytes, int cus, int* out2);
+// the ONE fallback entry, the same outputs in the same modes from planes in memory (the int16 form of launch_seg_stats_ex's mask output,
+// up = 1): low fp32 [B, K, h, w] -> maps [B, 2h, 2w]
+int launch_seg_labels16(const float* low, int B, int K, int h, int w, const CorrOut& out, const CorrLoss* loss, hipStream_t st);
+// lseg_op_corr_argmax_loss: the streamed entry with everything it needs beside the outputs carved from ONE caller workspace
 size_t corr_argmax_loss_ws_bytes(int B, int H, int W, int ragged, int want_nll, int temp_planes, int parts);
 int corr_argmax_loss_op(const void* g, const void* T, const float* scale, const int64_t* target, int ignore_index, const int32_t* host_counts,
                         int B, int K, int H, int W, int C, int16_t* label, float* score, float* lse, float* tlogit, float* nll_plane, double* nll,

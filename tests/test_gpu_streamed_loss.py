@@ -254,6 +254,43 @@ def test_guards_refuse_before_anything_is_launched(lib):
     assert o.untouched(), "a refused call wrote an output"
 
 
+def _same_bits_across_the_modes(argmax, conf, loss):
+    """(label, score) of the arg-max, the confidence and the loss form, lse of the last two: the three modes share their per-value code,
+    so they agree bit for bit.  No pixel may tie in its top two (score > score2), so an equal label cannot hide behind the tie order"""
+    assert (conf["score"] > conf["score2"]).all(), "a tie in the top two: pick another seed"
+    for k in ("label", "score"):
+        assert torch.equal(argmax[k], conf[k]) and torch.equal(loss[k], conf[k]), k
+    assert torch.equal(loss["lse"], conf["lse"])
+
+
+def test_the_three_modes_agree_bit_for_bit_on_split_labels(lib):
+    """B = 2, 15 x 15 (30 mid rows: two tiles per axis, the last one ragged), K = 100 = three panels of 48 / 48 / 4 labels, so the 4-wide and
+    the 8-wide walk both meet a `< K` tail, and a workspace for 8 parts: three parts of unequal fill, merged.  Seed 11: the fp64
+    composition's smallest top-2 gap is 4.9e-3 at max|logit| 14.3 (2900 fp32 ulps) -- no ties; the run re-checks it on its own scores"""
+    K, H, W = 100, 15, 15
+    g, T, scale, _ = _op_case(B, K + 1, H, W, 11)
+    T = T[:K].contiguous()                                                        # (without the builder's duplicate of a label: a tie)
+    n = B * 16 * H * W
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    out2 = (C.c_int * 2)()
+    for conf, part in ((0, 6), (1, 16)):
+        _lib.check(lib.lseg_op_corr_argmax_ragged_split((C.c_int32 * B)(*([K] * B)), B, H, W, conf, 8 * n * part, cus, out2))
+        assert out2[0] > 1 and out2[1] < K, "the workspace must force the label split"
+    ws = torch.empty((8 * n * 16,), dtype=torch.uint8).cuda()
+    a = dict(label=torch.full((B, 4 * H, 4 * W), -7, dtype=torch.int16).cuda(), score=torch.full((B, 4 * H, 4 * W), float("nan")).cuda())
+    _lib.check(lib.lseg_op_corr_argmax(P(g), P(T), P(scale), P(a["label"]), P(a["score"]), B, K, H, W, 512, P(ws), 8 * n * 6, stream()))
+    c = dict(label=torch.full_like(a["label"], -7), label2=torch.full_like(a["label"], -7),
+             **{k: torch.full_like(a["score"], float("nan")) for k in ("score", "score2", "lse")})
+    _lib.check(lib.lseg_op_corr_argmax_conf(P(g), P(T), P(scale), P(c["label"]), P(c["score"]), P(c["label2"]), P(c["score2"]), P(c["lse"]), B, K,
+                                            H, W, 512, P(ws), 8 * n * 16, stream()))
+    torch.cuda.synchronize()
+    target = make_target(a["label"], K, 255, seed=11).cuda()                      # ignore_index, values >= K, label K - 1 of the last panel
+    assert (target == 255).any() and ((target >= K) & (target != 255)).any() and (target == K - 1).any()
+    run = _run(lib, g, T, scale, target, 255, B, K, H, W, parts=8)
+    _same_bits_across_the_modes(a, c, {k: run.get(k) for k in ("label", "score", "lse")})
+    assert (c["label"] >= 96).any(), "no winner in the last panel"
+
+
 # ---- engine / network level ----------------------------------------------------------------------------------------------------------
 def _tiny512():
     cfg = get_config("tiny16")
@@ -372,6 +409,22 @@ def test_fallback_head_blocks_against_own_logits(golden_dir):
     assert d <= bar and (r["nll_plane"][~valid] == 0).all()
     nv = int(valid.sum())
     assert int(r["nll"][1].item()) == nv and abs(r["nll"][0].item() - ce.sum().item()) <= nv * bar
+    eng.close()
+
+
+def test_the_three_modes_of_the_fallback_agree_bit_for_bit():
+    """the small network as it is (out_c 128 cannot stream): 100 labels on the (32, 32) logits in memory, the three modes of the fallback"""
+    cfg = get_config("tiny16")
+    K = 100
+    eng = HipEngine(cfg, 64, 64, max_batch=2, max_labels=K, image_dtype="fp16")
+    eng.load_state_dict(synthetic_state_dict(cfg, seed=3))
+    eng.set_tokens(synthetic_tokens([f"thing {i}" for i in range(K)], cfg.text.vocab, cfg.text.ctx))
+    x = synthetic_images(2, 64, 64, seed=3).cuda()
+    label, score = eng.forward_labels(x, want_score=True)
+    conf = eng.forward_labels_conf(x)
+    loss = eng.forward_labels_loss(x, _engine_target(2, 64, 64, K, 255, seed=4), 255)
+    torch.cuda.synchronize()
+    _same_bits_across_the_modes(dict(label=label, score=score), conf, loss)
     eng.close()
 
 
