@@ -479,6 +479,57 @@ int lseg_op_rn_stem(const float* d_x, const float* d_w, const float* d_bias, voi
 int lseg_op_rn_maxpool(const void* d_in, void* d_out, int B, int H, int W, int C, int dtype, void* stream);
 int lseg_op_conv(const void* d_in, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_out, int B, int H, int W,
                  int Cin, int Cout, int ksize, int stride, int relu_out, int relu_after_res, int dtype, void* stream);
+/* One implicit-GEMM conv of the family the engine launches, described the way Engine::conv3x3 describes it, with the launcher's tools-only
+ * knobs exposed: the operator tests reach every conv tile, epilogue and schedule at small shapes through it (tests/test_gpu_conv_family.py).
+ * in: padded NHWC [B, H+2, W+2, Cin] (the border is READ: it is the conv's padding, zero in the engine); w [Cout, taps * Cin] tap-major
+ * (taps = 9 for ksize 3, pad 1; 1 for ksize 1, pad 0, which reads the interior only); out: padded NHWC [B, Ho+2, Wo+2, Cout], interior
+ * written, Ho = (H - 1) / stride + 1.  out = T(relu?(conv(relu_in ? relu(in) : in) + bias) + residual + residual2), or with relu_after_res
+ * T(relu(conv + bias + residual [+ residual2])); residual / residual2 have the geometry and type of out (out may alias residual).
+ * out_relu (optional, geometry of out): the stored out with its negative halves cleared (-0 -> +0); needs the specialised padded-NHWC
+ * epilogue (Cout % 128 == 0, a bias, 16-byte aligned maps), refused otherwise.  relu_in is implemented for bf16 and fp16 alike.
+ * nsplit > 1: the split-K form Engine::conv3x3 launches at small batch: out = fp32 slabs, slab s = out + s * c_split_stride floats holds
+ * the [B*Ho*Wo, Cout] partial product over K-steps [s * split_steps, (s + 1) * split_steps) of 64; no bias, residual, ReLU or out_relu.
+ * tile 0: the launcher's cost model; 1 = 64x64, 2 = 128x128, 6 = 256x256.  max_grid: 0 or a multiple of 8, caps the persistent grid.
+ * Every refusal (LSEG_ERR_INVALID / LSEG_ERR_UNSUPPORTED) comes before a device is asked for. */
+typedef struct lseg_conv_case {
+    const void* in; const void* w; const float* bias; const void* residual; const void* residual2;
+    void* out; void* out_relu;
+    int B, H, W, Cin, Cout, ksize, stride, dtype;
+    int relu_in, relu_out, relu_after_res;
+    int tile, max_grid;
+    int nsplit, split_steps; size_t c_split_stride;
+} lseg_conv_case;
+int lseg_op_conv_ex(const lseg_conv_case* c, void* stream);
+/* What that launch decides on a device of `cus` compute units, host only: out4 = {epilogue id (0 generic, 5 PAD16, 8 PART32), tile
+ * (1 | 2 | 6), workgroups, most work items one workgroup walks}.  Refuses what lseg_op_conv_ex refuses. */
+int lseg_op_conv_ex_plan(const lseg_conv_case* c, int cus, int* out4);
+/* The split-K plan Engine::conv3x3 makes for a conv of M = B*Ho*Wo rows, N = Cout columns and K = taps * Cin with a slab workspace of
+ * ws_floats floats, host only: *ns slabs of *steps K-steps of 64 (the last range possibly shorter); *ns = 1: the conv runs unsplit. */
+int lseg_op_conv_splitk_plan(int M, int N, int K, size_t ws_floats, int* ns, int* steps);
+/* The reduction behind a split-K conv: out (padded NHWC [B, Ho+2, Wo+2, C], interior written) = T(f(bias + sum of `ns` fp32 slabs
+ * [B*Ho*Wo, C], `stride` floats apart)) with the ReLU / residual / residual2 / out_relu forms of lseg_op_conv_ex.  C % 8 == 0,
+ * stride % 4 == 0, and d_part, d_res, d_res2, d_out, d_out_relu 16-byte aligned (the kernel moves 8 channels per access).  Argument refusals come before a device is asked for. */
+int lseg_op_conv_reduce_pad(const float* d_part, int ns, size_t stride, const float* d_bias, const void* d_res, const void* d_res2, void* d_out,
+                            void* d_out_relu, int B, int Ho, int Wo, int C, int relu, int relu_after_res, int dtype, void* stream);
+/* 3x3 conv weight gradient on the K-major operand path: d_dw fp32 [Cout, 9 * Cin] (tap-major) = sum over the padded pixels of
+ * dy_pad[p, co] * f(x_pad)[p + tap shift, ci], f = ReLU when relu_x; dy_pad [B, H+2, W+2, Cout] with a ZERO border, x_pad [B, H+2, W+2, Cin].
+ * d_ws: ws_floats floats of scratch for the split-K slabs -- its size bounds the slab count.  Returns the slab count (>= 1) or a negative
+ * status; refused before anything is launched: Cin % 128 != 0, ws_floats < Cout * 9 * Cin. */
+int lseg_op_conv_wgrad(const void* d_dy_pad, const void* d_x_pad, float* d_dw, int relu_x, int B, int H, int W, int Cin, int Cout, float* d_ws,
+                       size_t ws_floats, int dtype, void* stream);
+/* Linear weight gradient on the same path: d_dw fp32 [rows_out, cols_out] (+)= dy[:, :rows_out]^T x[:, :cols_out] over the M rows of
+ * dy [M, ldy] and x [M, ldx] (16-bit).  Refused before anything is launched: cols_out % 128 != 0, ws_floats < rows_out * cols_out. */
+int lseg_op_wgrad_kmajor(const void* d_dy, int ldy, const void* d_x, int ldx, int M, int rows_out, int cols_out, float* d_dw, int accumulate,
+                         float* d_ws, size_t ws_floats, int dtype, void* stream);
+/* Weight packers, one launch each.  conv_dgrad_pack: wd[ci, t, co] = wp[co, 8 - t, ci] (16-bit, a permutation).  pack_conv3x3: w fp32
+ * [Co, Ci, 3, 3] (+ eval BatchNorm fold when bn_w != NULL, + conv bias) -> wp [Co, 9, Cip] of dtype (fp32 allowed), channels ci >= Ci are NOT
+ * written (the caller's zeros stay), bias_out fp32 [Co] (optional).  pack_conv1x1: w fp32 [Co, Ci] (+ BatchNorm fold when bn_w != NULL)
+ * -> wp [Co, Ci], bias_out fp32 [Co] (zeros without BatchNorm). */
+int lseg_op_conv_dgrad_pack(const void* d_wp, void* d_wd, int Co, int Ci, void* stream);
+int lseg_op_pack_conv3x3(const float* d_w, const float* d_bn_w, const float* d_bn_b, const float* d_bn_m, const float* d_bn_v, float bn_eps,
+                         const float* d_conv_bias, void* d_wp, float* d_bias_out, int Co, int Ci, int Cip, int dtype, void* stream);
+int lseg_op_pack_conv1x1(const float* d_w, const float* d_bn_w, const float* d_bn_b, const float* d_bn_m, const float* d_bn_v, float bn_eps,
+                         void* d_wp, float* d_bias_out, int Co, int Ci, int dtype, void* stream);
 /* bilinear x2, align_corners=True, NHWC bf16: in [B,H+2,W+2,C] (padded) -> out [B,2H,2W,C] */
 int lseg_op_upsample2x_nhwc(const void* d_in, void* d_out, int B, int H, int W, int C, void* stream);
 /* bilinear x2, align_corners=True, NCHW fp32 planes: in [P,H,W] -> out [P,2H,2W]

@@ -1,4 +1,5 @@
 // capi.hip -- extern "C" surface of liblseg_hip.so (declared in include/lseg_hip.h).
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -441,18 +442,26 @@ int lseg_op_attention_strict(const void* q, const void* k, const void* vt, void*
     return launch_attention_strict(q, k, vt, out, qk_plane, vt_plane, out_plane, B, H, Ntok, Npad, scale, (hipStream_t)stream);
 }
 
+// One description of an implicit-GEMM conv on padded NHWC maps, the way Engine::conv3x3 builds it: lseg_op_conv3x3, lseg_op_conv and
+// lseg_op_conv_ex all launch what this returns.
+static GemmArgs conv_args(const void* in, const void* w_packed, const float* bias, const void* residual, const void* residual2, void* out, int B,
+                          int H, int W, int Cin, int Cout, int ksize, int stride, int relu_in, int relu_out, int relu_after_res, int dt) {
+    GemmArgs g;
+    gemm_args_init(g);
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1, taps = ksize == 1 ? 1 : 9;
+    g.A = (const uint16_t*)in; g.W = (const uint16_t*)w_packed; g.M = B * Ho * Wo; g.N = Cout; g.K = taps * Cin;
+    g.lda = Cin; g.ldw = taps * Cin;
+    g.conv = 1; g.ksize = ksize; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride; g.relu_in = relu_in;
+    g.bias = bias; g.act = relu_out ? ACT_RELU : ACT_NONE;
+    if (residual) { g.res_mode = RES_DEST; g.res = residual; g.res_dtype = dt; g.res2 = residual2; g.relu_after_res = relu_after_res; }
+    g.C = out; g.out_dtype = dt; g.ldc = Cout; g.map_mode = MAP_PADDED;
+    return g;
+}
+
 int lseg_op_conv3x3(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B,
                     int H, int W, int Cin, int Cout, int stride, int relu_in, int relu_out, void* stream) {
     int r = require_device(); if (r) return r;
-    GemmArgs g;
-    gemm_args_init(g);
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    g.A = (const uint16_t*)in; g.W = (const uint16_t*)w_packed; g.M = B * Ho * Wo; g.N = Cout; g.K = 9 * Cin;
-    g.lda = Cin; g.ldw = 9 * Cin;
-    g.conv = 1; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride; g.relu_in = relu_in;
-    g.bias = bias; g.act = relu_out ? ACT_RELU : ACT_NONE;
-    if (residual) { g.res_mode = RES_DEST; g.res = residual; g.res_dtype = DT_BF16; }
-    g.C = out; g.out_dtype = DT_BF16; g.ldc = Cout; g.map_mode = MAP_PADDED;
+    const GemmArgs g = conv_args(in, w_packed, bias, residual, nullptr, out, B, H, W, Cin, Cout, 3, stride, relu_in, relu_out, 0, DT_BF16);
     return launch_gemm(g, DT_BF16, (hipStream_t)stream);
 }
 
@@ -478,16 +487,138 @@ int lseg_op_conv(const void* in, const void* w_packed, const float* bias, const 
     if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: 16-bit maps only");
     if (ksize != 1 && ksize != 3) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: ksize %d (1 or 3)", ksize);
     if (stride != 1 && stride != 2) return set_error(LSEG_ERR_INVALID, "lseg_op_conv: stride %d (1 or 2)", stride);
-    GemmArgs g;
-    gemm_args_init(g);
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1, taps = ksize == 1 ? 1 : 9;
-    g.A = (const uint16_t*)in; g.W = (const uint16_t*)w_packed; g.M = B * Ho * Wo; g.N = Cout; g.K = taps * Cin;
-    g.lda = Cin; g.ldw = taps * Cin;
-    g.conv = 1; g.ksize = ksize; g.cin = Cin; g.hp = H + 2; g.wp = W + 2; g.ho = Ho; g.wo = Wo; g.stride = stride;
-    g.bias = bias; g.act = relu_out ? ACT_RELU : ACT_NONE;
-    if (residual) { g.res_mode = RES_DEST; g.res = residual; g.res_dtype = dt; g.relu_after_res = relu_after_res; }
-    g.C = out; g.out_dtype = dt; g.ldc = Cout; g.map_mode = MAP_PADDED;
+    const GemmArgs g = conv_args(in, w_packed, bias, residual, nullptr, out, B, H, W, Cin, Cout, ksize, stride, 0, relu_out, relu_after_res, dt);
     return launch_gemm(g, dt, (hipStream_t)stream);
+}
+
+// lseg_conv_case -> the GemmArgs Engine::conv3x3 would build for it; every refusal of a malformed case
+static int conv_case_args(const lseg_conv_case* c, GemmArgs& g, int* dt) {
+    if (!c) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: NULL case");
+    int r;
+    if ((r = op_dt(c->dtype, dt))) return r;
+    if (*dt == DT_F32) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: 16-bit maps only");
+    if (!c->in || !c->w || !c->out) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: NULL operand or output");
+    if (c->B < 1 || c->H < 1 || c->W < 1 || c->Cin < 1 || c->Cout < 1) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: empty problem");
+    if (c->ksize != 1 && c->ksize != 3) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: ksize %d (1 or 3)", c->ksize);
+    if (c->stride != 1 && c->stride != 2) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: stride %d (1 or 2)", c->stride);
+    if (c->tile != 0 && c->tile != 1 && c->tile != 2 && c->tile != 6) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: tile %d (0, 1, 2, 6)", c->tile);
+    if (c->max_grid < 0 || (c->max_grid % 8)) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: max_grid %d (0 or a multiple of 8)", c->max_grid);
+    if (c->residual2 && !c->residual) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: residual2 without residual");
+    if (c->relu_after_res && (!c->residual || !c->relu_out)) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: relu_after_res needs relu_out and a residual");
+    if (c->nsplit < 0 || c->split_steps < 0) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: negative split-K range");
+    g = conv_args(c->in, c->w, c->bias, c->residual, c->residual2, c->out, c->B, c->H, c->W, c->Cin, c->Cout, c->ksize, c->stride,
+                  c->relu_in ? 1 : 0, c->relu_out ? 1 : 0, c->relu_after_res ? 1 : 0, *dt);
+    g.C_relu = c->out_relu;
+    if (c->nsplit > 1) {                       // what Engine::conv3x3 launches before conv_reduce_pad: fp32 slabs, MAP_LINEAR, no epilogue terms
+        if (c->bias || c->residual || c->out_relu || c->relu_out || c->relu_in)
+            return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: the split-K form takes no bias, residual, ReLU or out_relu");
+        if (c->c_split_stride < (size_t)g.M * g.N) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex: c_split_stride is smaller than one slab");
+        g.out_dtype = DT_F32; g.map_mode = MAP_LINEAR;
+        g.nsplit = c->nsplit; g.split_steps = c->split_steps; g.c_split_stride = c->c_split_stride;
+    }
+    g.tile_hint = c->tile; g.max_grid = c->max_grid;
+    return 0;
+}
+
+int lseg_op_conv_ex(const lseg_conv_case* c, void* stream) {
+    GemmArgs g;
+    int dt, r = conv_case_args(c, g, &dt);
+    if (r) return r;
+    if ((r = gemm_check(g, dt))) return r;                 // every refusal of the launcher, before a device is asked for
+    if ((r = require_device())) return r;
+    return launch_gemm(g, dt, (hipStream_t)stream);
+}
+
+int lseg_op_conv_ex_plan(const lseg_conv_case* c, int cus, int* out4) {
+    if (!out4) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_ex_plan: NULL pointer");
+    GemmArgs g;
+    int dt, r = conv_case_args(c, g, &dt);
+    if (r) return r;
+    GemmPlan p;
+    if ((r = gemm_plan(g, dt, cus, p))) return r;
+    out4[0] = p.epi; out4[1] = p.tile; out4[2] = p.grid; out4[3] = p.items;
+    return 0;
+}
+
+int lseg_op_conv_splitk_plan(int M, int N, int K, size_t ws_floats, int* ns, int* steps) {
+    if (!ns || !steps) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_splitk_plan: NULL pointer");
+    if (M < 1 || N < 64 || (N % 64) || K < 64 || (K % 64)) return set_error(LSEG_ERR_INVALID, "lseg_op_conv_splitk_plan: M >= 1, N and K multiples of 64");
+    conv_splitk_plan(M, N, K, ws_floats, ns, steps);
+    return 0;
+}
+
+int lseg_op_conv_reduce_pad(const float* part, int ns, size_t stride, const float* bias, const void* res, const void* res2, void* out, void* out_relu,
+                            int B, int Ho, int Wo, int C, int relu, int relu_after_res, int dtype, void* stream) {
+    int dt, r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: 16-bit maps only");
+    if (!part || !out) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: NULL slabs or output");
+    if (ns < 1 || B < 1 || Ho < 1 || Wo < 1 || C < 1) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: ns, B, Ho, Wo, C >= 1");
+    if (C % 8) return set_error(LSEG_ERR_UNSUPPORTED, "conv_reduce_pad: C=%d must be a multiple of 8", C);
+    if (ns > 1 && stride < (size_t)B * Ho * Wo * C) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: stride=%zu is smaller than one slab", stride);
+    if (stride % 4) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: stride must be a multiple of 4 floats");
+    if (res2 && !res) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: res2 without res");
+    const void* const vec[5] = {part, res, res2, out, out_relu};                                        // float4 slab loads, uint4 map loads and stores
+    for (const void* p : vec)
+        if ((uintptr_t)p % 16) return set_error(LSEG_ERR_INVALID, "conv_reduce_pad: part, res, res2, out and out_relu must be 16-byte aligned");
+    if ((r = require_device())) return r;
+    return launch_conv_reduce_pad(part, ns, stride, bias, res, res2, out, out_relu, B, Ho, Wo, C, relu ? 1 : 0, dt, (hipStream_t)stream,
+                                  res && relu_after_res ? 1 : 0);
+}
+
+int lseg_op_conv_wgrad(const void* dy_pad, const void* x_pad, float* dw, int relu_x, int B, int H, int W, int Cin, int Cout, float* ws, size_t ws_floats,
+                       int dtype, void* stream) {
+    int dt, r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "conv_wgrad: 16-bit maps only");
+    if (!dy_pad || !x_pad || !dw || !ws || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return set_error(LSEG_ERR_INVALID, "conv_wgrad: bad arguments");
+    if ((Cin % 128) != 0 || !wgrad_kmajor_ok(Cout, 9 * Cin, ws_floats))
+        return set_error(LSEG_ERR_UNSUPPORTED, "conv_wgrad: needs Cin %% 128 == 0 and a workspace of Cout * 9 * Cin floats (Cin=%d Cout=%d)", Cin, Cout);
+    if ((r = require_device())) return r;
+    int ns = 0;
+    if ((r = launch_conv_wgrad_kmajor(dy_pad, x_pad, relu_x ? 1 : 0, B, H, W, Cin, Cout, ws, ws_floats, dt, &ns, (hipStream_t)stream))) return r;
+    const size_t n = (size_t)Cout * 9 * Cin;
+    if ((r = launch_sum_partials(ws, dw, ns, n, n, 0, (hipStream_t)stream))) return r;
+    return ns;
+}
+
+int lseg_op_wgrad_kmajor(const void* dy, int ldy, const void* x, int ldx, int M, int rows_out, int cols_out, float* dw, int accumulate, float* ws,
+                         size_t ws_floats, int dtype, void* stream) {
+    int dt, r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "wgrad_kmajor: 16-bit operands only");
+    if (!dy || !x || !dw || !ws || M < 1 || rows_out < 1 || cols_out < 1 || ldy < rows_out || ldx < cols_out || (ldy % 8) || (ldx % 8))
+        return set_error(LSEG_ERR_INVALID, "wgrad_kmajor: bad arguments (ldy >= rows_out, ldx >= cols_out, both multiples of 8)");
+    if (!wgrad_kmajor_ok(rows_out, cols_out, ws_floats))
+        return set_error(LSEG_ERR_UNSUPPORTED, "wgrad_kmajor: needs cols_out %% 128 == 0 and a workspace of rows_out * cols_out floats (%d x %d)", rows_out, cols_out);
+    if ((r = require_device())) return r;
+    return launch_wgrad_kmajor(dy, ldy, x, ldx, M, rows_out, cols_out, dw, accumulate ? 1 : 0, ws, ws_floats, dt, (hipStream_t)stream);
+}
+
+int lseg_op_conv_dgrad_pack(const void* wp, void* wd, int Co, int Ci, void* stream) {
+    if (!wp || !wd || Co < 1 || Ci < 1) return set_error(LSEG_ERR_INVALID, "conv_dgrad_pack: bad arguments");
+    int r = require_device(); if (r) return r;
+    return launch_conv_dgrad_pack(wp, wd, Co, Ci, (hipStream_t)stream);
+}
+
+int lseg_op_pack_conv3x3(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float bn_eps, const float* conv_bias,
+                         void* wp, float* bias_out, int Co, int Ci, int Cip, int dtype, void* stream) {
+    int dt, r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (!w || !wp || Co < 1 || Ci < 1 || Cip < Ci) return set_error(LSEG_ERR_INVALID, "pack_conv3x3: bad arguments (Cip >= Ci)");
+    if (bn_w && (!bn_b || !bn_m || !bn_v)) return set_error(LSEG_ERR_INVALID, "pack_conv3x3: BatchNorm needs weight, bias, mean and variance");
+    if ((r = require_device())) return r;
+    return launch_pack_conv3x3(w, bn_w, bn_b, bn_m, bn_v, bn_eps, conv_bias, wp, bias_out, Co, Ci, Cip, dt, (hipStream_t)stream);
+}
+
+int lseg_op_pack_conv1x1(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float bn_eps, void* wp,
+                         float* bias_out, int Co, int Ci, int dtype, void* stream) {
+    int dt, r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (!w || !wp || !bias_out || Co < 1 || Ci < 1) return set_error(LSEG_ERR_INVALID, "pack_conv1x1: bad arguments");
+    if (bn_w && (!bn_b || !bn_m || !bn_v)) return set_error(LSEG_ERR_INVALID, "pack_conv1x1: BatchNorm needs weight, bias, mean and variance");
+    if ((r = require_device())) return r;
+    return launch_pack_conv1x1(w, bn_w, bn_b, bn_m, bn_v, bn_eps, wp, bias_out, Co, Ci, dt, (hipStream_t)stream);
 }
 
 int lseg_op_upsample2x_nhwc(const void* in, void* out, int B, int H, int W, int C, void* stream) {

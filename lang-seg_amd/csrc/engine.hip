@@ -775,6 +775,23 @@ static bool splitk_enabled() {                         // LSEG_SPLITK=0 (tools) 
     return on != 0;
 }
 
+// Split-K plan of a small-batch conv [M x N] over K (Engine::conv3x3): enough (64 x 64 tile, K-range) work items for two per CU, ranges of
+// at least 8 K-steps, at most 8 slabs, slabs within the workspace; every range non-empty, the last one possibly shorter.  *ns = 1: no split.
+void conv_splitk_plan(int M, int N, int K, size_t ws_floats, int* ns_out, int* steps_out) {
+    const int nk = K / 64;
+    const long tiles = (long)((M + 63) / 64) * (N / 64);
+    long ns = tiles > 0 ? 512 / tiles : 1;
+    if (ns > nk / 8) ns = nk / 8;
+    if (ns > 8) ns = 8;
+    while (ns > 1 && (size_t)ns * M * N > ws_floats) --ns;
+    if (ns >= 2) {
+        const int steps = (int)((nk + ns - 1) / ns);
+        ns = (nk + steps - 1) / steps;
+    }
+    if (ns < 2) { *ns_out = 1; *steps_out = nk; return; }
+    *ns_out = (int)ns; *steps_out = (nk + (int)ns - 1) / (int)ns;
+}
+
 int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* res2, void* out, int B, int H, int W,
                     int stride, int relu_in, int relu_out, hipStream_t st, void* out_relu, bool* relu_written, int ksize, int relu_after_res) {
     // in: padded NHWC [B,H+2,W+2,Cin]; out: padded NHWC [B,Ho+2,Wo+2,Cout]
@@ -794,21 +811,13 @@ int Engine::conv3x3(const void* in, const Lin& w, const void* res, const void* r
     // Small batches: the deep levels of the pyramid are a handful of tiles with a 36..144-step contraction (layer3_rn at B = 1: 60 tiles of
     // 64 x 64, K = 9216, 95 us on a quarter of the chip).  Split-K work items into fp32 slabs + one streaming epilogue kernel.
     if (splitk_enabled() && !(cfg.flags & 4) && !train_mode && !strict_ && !relu_in && (w.n % 64) == 0) {
-        const int nk = w.k / 64;
-        const long tiles = (long)((g.M + 63) / 64) * (w.n / 64);
-        long ns = 512 / tiles;
-        if (ns > nk / 8) ns = nk / 8;
-        if (ns > 8) ns = 8;
-        while (ns > 1 && (size_t)ns * g.M * w.n > ws_split_n_) --ns;
-        if (ns >= 2) {
-            const int steps = (int)((nk + ns - 1) / ns);
-            ns = (nk + steps - 1) / steps;
-        }
+        int ns = 1, steps = 0;
+        conv_splitk_plan(g.M, w.n, w.k, ws_split_n_, &ns, &steps);
         if (ns >= 2) {
             GemmArgs p = g;
             p.bias = nullptr; p.act = ACT_NONE; p.res_mode = RES_NONE; p.res = nullptr; p.res2 = nullptr; p.relu_after_res = 0;
             p.C = ws_split_; p.out_dtype = DT_F32; p.ldc = w.n; p.map_mode = MAP_LINEAR;
-            p.nsplit = (int)ns; p.split_steps = (nk + (int)ns - 1) / (int)ns; p.c_split_stride = (size_t)g.M * w.n;
+            p.nsplit = ns; p.split_steps = steps; p.c_split_stride = (size_t)g.M * w.n;
             TRY(launch_gemm(p, img_dt_, st));
             TRY(launch_conv_reduce_pad(ws_split_, (int)ns, p.c_split_stride, w.b, res, res2, out, out_relu, B, Ho, Wo, w.n, relu_out, img_dt_, st,
                                        res ? relu_after_res : 0));

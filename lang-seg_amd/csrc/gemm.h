@@ -32,7 +32,7 @@ struct GemmArgs {
     int cin, hp, wp;        // padded input geometry
     int ho, wo;             // output spatial size (also used by MAP_PADDED / MAP_PIXSHUF)
     int stride;             // conv stride (1|2)
-    int relu_in;            // apply ReLU to A fragments (bf16 only)
+    int relu_in;            // apply ReLU to the A fragments: a sign-bit test on the 16-bit halves, the same for bf16 and fp16 (-0 -> +0)
     // epilogue
     const float* bias;      // fp32 [N] (or [bias_mod]) or null
     int bias_mod;           // 0: bias[n]; else bias[n % bias_mod]

@@ -17,6 +17,9 @@ int launch_layernorm_reduce(float* x, const float* part, int nsplit, size_t stri
 // relu_after_res: the ReLU after the skip add (ResNet bottleneck) instead of before it
 int launch_conv_reduce_pad(const float* part, int ns, size_t stride, const float* bias, const void* res, const void* res2, void* out, void* out_relu,
                            int B, int Ho, int Wo, int C, int relu, int dtype, hipStream_t st, int relu_after_res = 0);
+// split-K plan of a small-batch conv [M x N] over K (engine.hip, Engine::conv3x3): *ns slabs of *steps 64-wide K-steps (the last range possibly
+// shorter), slabs within ws_floats; *ns = 1: the conv runs unsplit.  Host only.
+void conv_splitk_plan(int M, int N, int K, size_t ws_floats, int* ns, int* steps);
 int launch_im2col_patch(const float* x, void* A, int B, int H, int W, int P, int dtype, hipStream_t st);
 int launch_pos_resize(const float* pos, float* out, int g_old, int gh, int gw, int D, hipStream_t st);
 int launch_cls_rows(const float* cls, const float* pos, float* x, int B, int ntok, int D, hipStream_t st);

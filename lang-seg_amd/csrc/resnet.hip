@@ -103,15 +103,15 @@ __global__ __launch_bounds__(256) void rn_maxpool_kernel(const uint16_t* __restr
     }
 }
 
-// 1x1 conv + BN: wp[co, ci] = w[co, ci] * s[co], bias[co] = bn_b - bn_m * s, s = bn_w / sqrt(bn_v + eps)
+// 1x1 conv + BN: wp[co, ci] = w[co, ci] * s[co], bias[co] = bn_b - bn_m * s, s = bn_w / sqrt(bn_v + eps); bn_w NULL: no BatchNorm (s = 1, bias 0)
 __global__ void pack_conv1x1_kernel(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float eps,
                                     void* wp, float* bias_out, int Co, int Ci, int dtype) {
     const size_t n = (size_t)Co * Ci;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int co = (int)(i / Ci), ci = (int)(i % Ci);
-        const float s = bn_w[co] * rsqrtf(bn_v[co] + eps);
+        const float s = bn_w ? bn_w[co] * rsqrtf(bn_v[co] + eps) : 1.f;
         store_from_f32(wp, i, dtype, w[i] * s);
-        if (ci == 0) bias_out[co] = bn_b[co] - bn_m[co] * s;
+        if (ci == 0) bias_out[co] = bn_w ? bn_b[co] - bn_m[co] * s : 0.f;
     }
 }
 

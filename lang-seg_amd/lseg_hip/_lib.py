@@ -50,6 +50,18 @@ class LSegGemmCase(C.Structure):
     ]
 
 
+class LSegConvCase(C.Structure):
+    """lseg_conv_case of include/lseg_hip.h (lseg_op_conv_ex, lseg_op_conv_ex_plan)."""
+    _fields_ = [
+        ("inp", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p), ("residual2", C.c_void_p),
+        ("out", C.c_void_p), ("out_relu", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("ksize", C.c_int), ("stride", C.c_int), ("dtype", C.c_int),
+        ("relu_in", C.c_int), ("relu_out", C.c_int), ("relu_after_res", C.c_int),
+        ("tile", C.c_int), ("max_grid", C.c_int),
+        ("nsplit", C.c_int), ("split_steps", C.c_int), ("c_split_stride", C.c_size_t),
+    ]
+
+
 class LSegError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -133,6 +145,15 @@ SIGNATURES = {
     "lseg_op_rn_stem": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_rn_maxpool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_conv_ex": (_i, [C.POINTER(LSegConvCase), _vp]),
+    "lseg_op_conv_ex_plan": (_i, [C.POINTER(LSegConvCase), _i, C.POINTER(_i * 4)]),
+    "lseg_op_conv_splitk_plan": (_i, [_i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i)]),
+    "lseg_op_conv_reduce_pad": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_conv_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "lseg_op_wgrad_kmajor": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
+    "lseg_op_conv_dgrad_pack": (_i, [_vp, _vp, _i, _i, _vp]),
+    "lseg_op_pack_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_pack_conv1x1": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
     "lseg_op_upsample2x_planes": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "lseg_op_upsample4x_planes_scaled": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lseg_op_pixel_gram": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -91,15 +91,18 @@ def _pattern(n, dtype, device):
 
 class Out:
     """[PRE | coff | payload | POST]; `must` (bool, payload-shaped) marks the cells that have to be written.  fill: None = NaN, a number,
-    or a payload-shaped tensor (the residual of an in-place launch)."""
+    or a payload-shaped tensor (the residual of an in-place launch).  outside: None = the payload cells outside `must` hold the guard
+    pattern, a number = they hold that value (a caller's zeros); either way they must come back bit for bit."""
 
-    def __init__(self, shape, dt, must, device="cpu", coff=0, fill=None):
+    def __init__(self, shape, dt, must, device="cpu", coff=0, fill=None, outside=None):
         self.shape, self.dt, self.coff = tuple(shape), dt, coff
         self.n = int(np.prod(shape))
         self.flat = _pattern(PRE + coff + self.n + PRE, TD[dt], device)
         self.must = must.to(device)
         assert tuple(must.shape) == self.shape
         pay = self.payload()
+        if outside is not None:
+            pay[~self.must] = outside
         if fill is None:
             pay[self.must] = float("nan")
         elif torch.is_tensor(fill):
