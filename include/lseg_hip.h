@@ -633,6 +633,18 @@ int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const 
  * Before anything is launched or the device is touched: LSEG_ERR_INVALID for a NULL required pointer, B, H, W or K < 1, a map without
  *   offsets or with nclass < 1, pointers not aligned to their element; LSEG_ERR_UNSUPPORTED for K > 32767 or H W > 2^31 - 1. */
 int lseg_op_label_stats_plan(int K_or_bins, int* out2);
+/* Which schedule the inference forward runs for a request, and whether it refuses it before any launch: host only, no handle, no device.
+ * n requests; request i reads in13 + 13 i = {wanted outputs, K, group_k, ragged, arch_option, out_c, quarter-resolution width, debug,
+ * strict (split precision), the commuted head is packed for out_c, LSEG_CORR_FULLRES set, LSEG_CORR_GENERIC set, LSEG_NO_UPSAMPLE4X set} with
+ * wanted = bit 0 logits, 1 uint8 masks, 2 labels, 3 score, 4 low-resolution logits, 5 runner-up (label2 or score2), 6 lse, 7 held
+ * features, 8 loss, 9 the loss's target; and writes out6 + 6 i = {refusal status (0 | LSEG_ERR_INVALID | LSEG_ERR_UNSUPPORTED; the
+ * refusals that read the engine's state -- finalised, tokens set, B, train mode, the label list lengths, grouped K, uint8 masks beyond
+ * K = 256 -- are not in it), tail, source of the quarter-resolution label planes, commuted, corr_low, corr_fused}.
+ * tail: 0 held features, 1 streamed ragged labels, 2 streamed shared-set labels, 3 one-pass x4 upsample into the logits, 4 x2 upsample
+ * into the low-resolution output, 5 planes in memory from the quarter-resolution planes, 6 / 7 / 8 planes in memory from the (2h, 2w)
+ * feature map made by the commuted head + upsample_norm / the row-norm GEMM / head1 + l2norm.  planes (tails 3..5): 1 the dedicated
+ * correlation kernel, 2 per-image GEMMs, 3 the generic GEMM; 0 elsewhere.  The route of a refused request is unspecified. */
+int lseg_op_forward_route(const int32_t* in13, int n, int32_t* out6);
 int lseg_op_label_stats(const int16_t* d_label, const int64_t* d_target, int B, int H, int W, int K, int ignore_index,
                         const int32_t* d_offsets, const int32_t* d_class_map, int nclass, int64_t* d_counts, int64_t* d_flags,
                         int accumulate, void* stream);

@@ -95,28 +95,31 @@ int lseg_get_text_features(lseg_handle h, void* dev_out, void* stream) {
 
 int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out, uint8_t* dev_argmax_out, void* stream) {
     GUARD(h);
-    return h->e->forward(dev_x, B, dev_logits_out, dev_argmax_out, (hipStream_t)stream);
+    Engine::ForwardOut out;
+    out.logits = dev_logits_out; out.argmax = dev_argmax_out;
+    return h->e->forward(dev_x, B, out, (hipStream_t)stream);
 }
 
 int lseg_forward_labels(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, void* stream) {
     GUARD(h);
-    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
-    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out);
+    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");     // (to the engine an empty request is no error)
+    Engine::ForwardOut out;
+    out.label = dev_label_out; out.score = dev_score_out;
+    return h->e->forward(dev_x, B, out, (hipStream_t)stream);
 }
 
 int lseg_forward_labels_conf(lseg_handle h, const float* dev_x, int B, int16_t* dev_label_out, float* dev_score_out, int16_t* dev_label2_out,
                              float* dev_score2_out, float* dev_lse_out, void* stream) {
     GUARD(h);
     if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
-    const Engine::LabelConf conf{dev_label2_out, dev_score2_out, dev_lse_out};
-    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, dev_label_out, dev_score_out, nullptr, &conf);
+    Engine::ForwardOut out;
+    out.label = dev_label_out; out.score = dev_score_out; out.conf = Engine::LabelConf{dev_label2_out, dev_score2_out, dev_lse_out};
+    return h->e->forward(dev_x, B, out, (hipStream_t)stream);
 }
 
 int lseg_forward_labels_loss(lseg_handle h, const float* dev_x, int B, const int64_t* dev_target, int ignore_index, int16_t* dev_label_out,
                              float* dev_score_out, float* dev_lse_out, float* dev_nll_plane_out, double* dev_nll, int64_t* dev_counts, void* stream) {
     GUARD(h);
-    if (!dev_label_out) return set_error(LSEG_ERR_INVALID, "label output is NULL");
-    if (!dev_target) return set_error(LSEG_ERR_INVALID, "target is NULL");
     return h->e->forward_labels_loss(dev_x, B, dev_target, ignore_index, dev_label_out, dev_score_out, dev_lse_out, dev_nll_plane_out, dev_nll,
                                      dev_counts, (hipStream_t)stream);
 }
@@ -124,7 +127,9 @@ int lseg_forward_labels_loss(lseg_handle h, const float* dev_x, int B, const int
 int lseg_forward_lowres(lseg_handle h, const float* dev_x, int B, float* dev_low_out, void* stream) {
     GUARD(h);
     if (!dev_low_out) return set_error(LSEG_ERR_INVALID, "low-resolution logits output is NULL");
-    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, dev_low_out);
+    Engine::ForwardOut out;
+    out.low = dev_low_out;
+    return h->e->forward(dev_x, B, out, (hipStream_t)stream);
 }
 
 int lseg_features_bytes(lseg_handle h, int B, size_t* feat_bytes, size_t* scale_bytes) {
@@ -138,7 +143,9 @@ int lseg_forward_features(lseg_handle h, const float* dev_x, int B, void* dev_fe
     GUARD(h);
     if (!dev_feat_out || !dev_scale_out) return set_error(LSEG_ERR_INVALID, "held-feature output is NULL");
     const Engine::HeldOut held{dev_feat_out, dev_scale_out};
-    return h->e->forward(dev_x, B, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, &held);
+    Engine::ForwardOut out;
+    out.held = &held;
+    return h->e->forward(dev_x, B, out, (hipStream_t)stream);
 }
 
 int lseg_score_features(lseg_handle h, const void* dev_feat, const float* dev_scale, int B, int row0, int rows, float* dev_low_out, void* stream) {
@@ -713,6 +720,23 @@ int lseg_op_episode_stats(const float* d_scores, const int64_t* d_target, const 
     if (r) return r;
     return launch_episode_stats(d_scores, d_target, d_ignore, B, H, W, up, ignore_index, d_class_id, nclass, d_inter_buf, d_union_buf, d_areas,
                                 d_nll, d_flags, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+// forward_route.h: the route table of Engine::forward for n requests (host only, no engine, no device)
+int lseg_op_forward_route(const int32_t* in13, int n, int32_t* out6) {
+    if (!in13 || !out6 || n < 1) return set_error(LSEG_ERR_INVALID, "forward_route: NULL pointer or n < 1");
+    for (int i = 0; i < n; ++i, in13 += 13, out6 += 6) {
+        RouteIn r;
+        const int w = in13[0];
+        r.logits = w & 1; r.argmax = w & 2; r.label = w & 4; r.score = w & 8; r.low = w & 16; r.runner_up = w & 32; r.lse = w & 64;
+        r.held = w & 128; r.loss = w & 256; r.target = w & 512;
+        r.K = in13[1]; r.group_k = in13[2]; r.ragged = in13[3]; r.arch_option = in13[4]; r.out_c = in13[5]; r.lw0 = in13[6];
+        r.debug = in13[7]; r.strict = in13[8]; r.headc_packed = in13[9]; r.corr_full = in13[10]; r.corr_generic = in13[11]; r.no_4x = in13[12];
+        const Route t = forward_route(r);
+        out6[0] = refusal_status(forward_refusal(r));
+        out6[1] = t.tail; out6[2] = t.planes; out6[3] = t.commuted; out6[4] = t.corr_low; out6[5] = t.corr_fused;
+    }
+    return LSEG_OK;
 }
 
 // label_stats.hip: every check of these launchers comes before the device is touched (a refusal needs no device)

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ops.h"
+#include "forward_route.h"
 #include "../../include/lseg_hip.h"
 
 namespace lseg {
@@ -97,19 +98,26 @@ public:
     int set_text_features(const void* dev_feat_f16, int K, hipStream_t st);
     bool text_external_ = false;   // the text features were handed in (lseg_set_text_features): forward never runs the text tower
     int encode_text(hipStream_t st);
-    // label_out / score_out (int16 / fp32 [B,img_h,img_w], lseg_forward_labels): masks for any K <= 32767; with no other output wanted the
-    // labels are streamed (corr_argmax.hip): no (2h, 2w) or full-resolution label plane is written
-    // low_out (fp32 [B,Kout,img_h/2,img_w/2], lseg_forward_lowres): the logits output_conv would upsample, in the caller's buffer
-    // conf (lseg_forward_labels_conf; needs label_out): the runner-up and the log-sum-exp over the labels beside the arg-max, each optional
-    struct LabelConf { int16_t* label2; float* score2; float* lse; };
-    // held (lseg_forward_features): the forward stops behind the scale plane and copies what the correlation reads -- g16pad_ and
-    // nscale_ -- into the caller's buffers; no text is read, the gram is pixel_gram's whatever K is set
+    struct LabelConf { int16_t* label2 = nullptr; float* score2 = nullptr; float* lse = nullptr; };
     struct HeldOut { void* feat; float* scale; };
-    // loss (lseg_forward_labels_loss; needs label_out, excludes conf's runner-up): the cross-entropy beside the arg-max -- conf->lse is its
-    // lse output, the rest is ops.h' CorrLoss; streamed where the labels stream, seg_labels16 on the planes in memory elsewhere
-    int forward(const float* x, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out = nullptr,
-                float* score_out = nullptr, float* low_out = nullptr, const LabelConf* conf = nullptr, const HeldOut* held = nullptr,
-                const CorrLoss* loss = nullptr);
+    // What one forward is asked for: every member optional, filled by name.  forward_route (forward_route.h) maps the request to the
+    // schedule that runs, check_request refuses what none serves.
+    struct ForwardOut {
+        float* logits = nullptr;          // fp32 [B,Kout,img_h,img_w] (lseg_forward)
+        uint8_t* argmax = nullptr;        // uint8 [B,img_h,img_w] masks, K <= 256 (lseg_forward)
+        // label / score (int16 / fp32 [B,img_h,img_w], lseg_forward_labels): masks for any K <= 32767; with no other output wanted the
+        // labels are streamed (corr_argmax.hip): no (2h, 2w) or full-resolution label plane is written.  score needs label
+        int16_t* label = nullptr; float* score = nullptr;
+        float* low = nullptr;             // fp32 [B,Kout,img_h/2,img_w/2] (lseg_forward_lowres): the logits output_conv would upsample
+        LabelConf conf;                   // lseg_forward_labels_conf; needs label: the runner-up and the log-sum-exp beside the arg-max
+        // lseg_forward_features: the forward stops behind the scale plane and copies what the correlation reads -- g16pad_ and nscale_ --
+        // into the caller's buffers; no text is read, the gram is pixel_gram's whatever K is set
+        const HeldOut* held = nullptr;
+        // lseg_forward_labels_loss; needs label, excludes conf's runner-up and every other output: the cross-entropy beside the arg-max --
+        // conf.lse is its lse output, the rest is ops.h' CorrLoss; streamed where the labels stream, seg_labels16 on the planes elsewhere
+        const CorrLoss* loss = nullptr;
+    };
+    int forward(const float* x, int B, const ForwardOut& out, hipStream_t st);
     // lseg_forward_labels_loss: the labels forward with the loss, then (dev_counts given) lseg_op_label_stats on the label map it wrote.
     // The planes nobody asked for (lse, tlogit), the reduction's partials and label_stats' flag words live in loss_ws_, made on first use
     int forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out, float* lse_out,
@@ -187,8 +195,16 @@ private:
     int text_join(hipStream_t st);
     int check_grouping(int B);
     int check_ragged_train();                        // ... and of a train-mode forward / lseg_set_train while they are set
-    int check_ragged(int B, bool labels_only);       // the refusals of a forward while ragged groups are set
     int check_held(const char* what);                // the refusals of lseg_forward_features / lseg_score_features: where corr_low does not hold
+    // ---- Engine::forward: the request as plain values and its refusals before any launch (forward_request.hip), the stages of its tails
+    RouteIn route_in(const ForwardOut& out) const;
+    int check_request(const float* x, int B, const ForwardOut& out, const RouteIn& r);
+    int image_tower(const float* x_in, int B, hipStream_t st);                 // ViT blocks + reassemble, or ResNet-101 + layerN_rn -> rn_[0..3]
+    int scale_plane(int B, bool corr_fused, hipStream_t st);                   // g16pad_, gram_ (corr_fused: rpl_ too), nscale_, overflow sentinel
+    int label_planes(int B, FwdPlanes src, hipStream_t st);                    // rpl_ = the label planes at quarter resolution; low_ pending
+    int feature_planes(FwdTail tail, int B, hipStream_t st);                   // a16_ at (2h, 2w) by one of the three feature paths, then low_
+    int head_blocks(int B, int kout, const float** low, hipStream_t st);       // arch_option 1 / 2 on low_; *low = the planes the outputs read
+    int planes_outputs(const ForwardOut& out, const float* low, int B, int kout, hipStream_t st);
     std::vector<int32_t> groups_;
     char* loss_ws_ = nullptr;                        // forward_labels_loss: {lse, tlogit} fp32 [max_batch,img_h,img_w], partials, flags
     int* d_goff_ = nullptr;                          // [max_batch + 1] prefix sum of groups_, written by the ragged launch

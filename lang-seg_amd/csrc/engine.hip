@@ -690,53 +690,6 @@ int Engine::set_text_groups(const int32_t* host_counts, int B) {
     return 0;
 }
 
-// nothing but the streamed labels exists for ragged groups: every other request is refused before a kernel runs, nothing falls back
-int Engine::check_ragged(int B, bool labels_only) {
-    if (groups_.empty()) return 0;
-    if ((int)groups_.size() != B) return set_error(LSEG_ERR_INVALID, "ragged label sets: set for %d images, forward called with B=%d", (int)groups_.size(), B);
-    long total = 0;
-    for (int k : groups_) total += k;
-    if (total != K_) return set_error(LSEG_ERR_INVALID, "ragged label sets: %d token rows != %ld labels over the %d images", K_, total, B);
-    if (train_mode) return check_ragged_train();      // the fused-loss route (train.hip); forward_train refuses a logits output
-    if (!labels_only)
-        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no logits: only lseg_forward_labels / lseg_forward_labels_conf run with them");
-    const lseg_config& c = cfg;
-    const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
-    if (!commuted || getenv("LSEG_CORR_FULLRES") || (lw_[0] % 2) != 0 || getenv("LSEG_CORR_GENERIC") || c.arch_option != 0 || c.out_c != 512)
-        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets need the streamed kernel: the commuted schedule (no debug taps, no split precision), "
-                                               "out_c 512 (is %d), arch_option 0 (is %d), no LSEG_CORR_GENERIC / LSEG_CORR_FULLRES", c.out_c, c.arch_option);
-    return 0;
-}
-
-// ragged label sets in train mode: the fused-loss route on the plain head only.  Refused before any kernel runs: the arch_option 1/2 head
-// blocks (their planes are rectangular) and the ResNet-101 decoder-training mode (never run with ragged sets: refused rather than left
-// untested).  Deterministic reductions (flags bit 3) need nothing new: the ragged loss kernels hold no fp32 atomic -- the counts are
-// integers and the gradient reads only the valid-pixel count, so the rows are bit-reproducible; the loss VALUE is a double atomic sum,
-// order-dependent in its last bits exactly as seg_stats_kernel's is
-int Engine::check_ragged_train() {
-    if (cfg.arch_option != 0) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode need arch_option 0 (is %d): the head blocks "
-                                                                      "work on rectangular [B,K,h,w] planes", cfg.arch_option);
-    if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode are not implemented for the ResNet-101 tower (decoder training)");
-    if (!corr_ragged_supported(cfg.out_c)) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode need out_c %% 64 == 0 and <= 1024 (is %d)", cfg.out_c);
-    return 0;
-}
-
-// held features exist only where the forward's corr_low holds (the correlation commuted below the x2 upsample reads g16pad_ and nscale_ and
-// nothing else) and for one label set shared by the batch: everything else is refused before a kernel runs, nothing falls back
-int Engine::check_held(const char* what) {
-    const lseg_config& c = cfg;
-    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "%s is an inference feature (train mode is on)", what);
-    if (group_k > 0 || ragged()) return set_error(LSEG_ERR_UNSUPPORTED, "%s: per-image label sets have no held-feature form (one label set shared by the batch)", what);
-    const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
-    // (no bound on out_c: pixel_gram and the generic GEMM take every width the engine accepts -- the 512 of the streamed labels is the
-    // width of THEIR kernel, which nothing here runs)
-    if (!commuted || getenv("LSEG_CORR_FULLRES") || (lw_[0] % 2) != 0 || c.arch_option != 0)
-        return set_error(LSEG_ERR_UNSUPPORTED, "%s needs the commuted correlation: the commuted schedule (no debug taps, no split precision), "
-                                               "arch_option 0 (is %d), an even quarter-resolution width (is %d), no LSEG_CORR_FULLRES",
-                         what, c.arch_option, lw_[0]);
-    return 0;
-}
-
 void Engine::features_bytes(int B, size_t* feat_bytes, size_t* scale_bytes) const {
     if (feat_bytes) *feat_bytes = (size_t)B * (lh_[0] + 2) * (lw_[0] + 2) * cfg.out_c * sizeof(uint16_t);
     if (scale_bytes) *scale_bytes = (size_t)B * 4 * lh_[0] * lw_[0] * sizeof(float);
@@ -1044,39 +997,12 @@ int Engine::split_residual(GemmArgs& g, int M, int N, int K) {
     return ns;
 }
 
-int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out, hipStream_t st, int16_t* label_out, float* score_out,
-                    float* low_out, const LabelConf* conf, const HeldOut* held, const CorrLoss* loss) {
-    const LabelConf cf = conf ? *conf : LabelConf{nullptr, nullptr, nullptr};
-    const CorrOut out16{label_out, score_out, cf.label2, cf.score2, cf.lse, nullptr};   // the int16 masks and what rides with them
-    if ((cf.label2 || cf.score2 || cf.lse) && !label_out) return set_error(LSEG_ERR_INVALID, "the confidence outputs need the label output");
-    if (loss && (!label_out || !loss->target || cf.label2 || cf.score2 || logits || argmax_out || low_out || held))
-        return set_error(LSEG_ERR_INVALID, "the loss outputs need the label output and a target, and come with no other output");
-    if (!finalized_) return set_error(LSEG_ERR_STATE, "parameters not finalised (call lseg_finalize_params)");
-    if (K_ < 1 && !held) return set_error(LSEG_ERR_STATE, "no text tokens set (call lseg_set_text_tokens)");
-    if (B < 1 || B > cfg.max_batch) return set_error(LSEG_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cfg.max_batch);
-    if (!x_in) return set_error(LSEG_ERR_INVALID, "x is NULL");
-    if (held) TRY(check_held("lseg_forward_features"));      // (groupings and train mode are refused there: nothing below meets them)
-    if (score_out && !label_out) return set_error(LSEG_ERR_INVALID, "a score output needs the label output");
-    if (label_out && !ragged() && (group_k > 0 ? group_k : K_) > 32767) return set_error(LSEG_ERR_UNSUPPORTED, "int16 labels need K <= 32767 (K=%d)", K_);
-    TRY(check_ragged(B, label_out && !logits && !argmax_out && !low_out));
-    LSEG_HIP_TRY(hipSetDevice(device));
-    labels_only_ = false;
-    if (train_mode) {                    // net.train(): activations saved for lseg_backward, BatchNorm on batch statistics
-        if (label_out) return set_error(LSEG_ERR_UNSUPPORTED, "label output is an inference feature (train mode is on)");
-        if (argmax_out) return set_error(LSEG_ERR_UNSUPPORTED, "argmax output is an inference feature (train mode is on)");
-        if (low_out) return set_error(LSEG_ERR_UNSUPPORTED, "low-resolution logits output is an inference feature (train mode is on)");
-        return forward_train(x_in, B, logits, st);
-    }
-    if (eval_stale_) TRY(finalize(st));  // optimizer steps refresh only the train-mode packs: fold BatchNorm / the commuted head again
+// ---- the stages of the inference forward (Engine::forward below strings them together by the route) ------------------------------------
+// The image tower up to scratch.layerN_rn: rn_[0..3] (and their ReLU copies)
+int Engine::image_tower(const float* x_in, int B, hipStream_t st) {
     const lseg_config& c = cfg;
     const int D = c.dim, H = c.heads, M = B * ntok_;
-    last_B_ = B;
-    low_pending_ = false;
-    hipEvent_t fwd0 = prof_begin(PF_FWD, st);
     const double ntok2 = (double)ntok_ * ntok_;
-
-    if (!held) TRY(text_fork(st));       // ---- text tower (lseg_net.py:181-183) on the side stream; held features read no text
-
     GemmArgs g;
     if (resnet_) {
         // ---- torchvision ResNet-101 layer1..4 (lseg_net_zs.py:325-333) straight into L_[0..3], then scratch.layerN_rn ---------------
@@ -1160,112 +1086,63 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         }
     }
 
-    // ---- refinenet4..1 (lseg_net.py:176-179) ---------------------------------------------------------------
-    // Fast path of the head (everything but the debug taps / the split-precision mode): the two 1x1 convs after refinenet1's
-    // upsample -- out_conv and head1 -- commute with it and run as ONE GEMM at the quarter resolution (elementwise.hip "commuted head")
-    const bool commuted = !debug && !strict_ && headc_.n == c.out_c;
-    for (int r = 4; r >= 1; --r) TRY(refine(r, B, st, commuted && r == 1));
+    return 0;
+}
 
-    if (!held) {
-        TRY(text_join(st));              // before the correlation
-        TRY(check_grouping(B));
+// corr_low, every tail: the commuted head into g16pad_, the cell gram and the scale plane nscale_ with the overflow sentinel behind it.
+// corr_fused: the dedicated kernel (corr.hip) -- T resident in LDS, g streamed once, label planes (rpl_) and cell dot products from the
+// same registers; per-image label sets (zero-shot), other widths and label sets that do not fit the LDS take pixel_gram (+ label_planes)
+int Engine::scale_plane(int B, bool corr_fused, hipStream_t st) {
+    const lseg_config& c = cfg;
+    const int hp = lh_[0] + 2, wp = lw_[0] + 2;
+    GemmArgs g = lin_args(t2_[0], headc_, B * hp * wp, g16pad_, DT_F16);      // every row of the padded map (border rows are never read)
+    TRY(igemm(g, st));
+    // "correlation" family = the dedicated kernel only (label planes + cell dot products; algorithmic BYTES in the flops slot): the generic
+    // pair is not bracketed, so no event is taken that would never be paired (the pool is sized per family and forward)
+    hipEvent_t pc = corr_fused ? prof_begin(PF_CORR, st) : nullptr;
+    if (corr_fused) TRY(launch_corr_planes(g16pad_, tnorm_, rpl_, gram_, B, K_, lh_[0], lw_[0], c.out_c, st));
+    else TRY(launch_pixel_gram(g16pad_, gram_, B, lh_[0], lw_[0], c.out_c, st));
+    if (corr_fused) prof_end(PF_CORR, pc, (double)B * hp * wp * c.out_c * 2.0 + (double)B * K_ * lh_[0] * lw_[0] * 4.0 + (double)B * lh_[0] * lw_[0] * 20.0 +
+                                          (double)K_ * c.out_c * 2.0, st);
+    TRY(launch_norm_scale_plane(gram_, nscale_, B, lh_[0], lw_[0], logit_scale(), st, ovf_dev_));
+    // the sentinel travels to pinned host memory behind the forward; Engine::overflow_seen reads it once the event has passed (no sync)
+    (void)overflow_seen(false);                      // harvest the previous forward's copy before its event is recorded again
+    LSEG_HIP_TRY(hipMemcpyAsync(ovf_host_, ovf_dev_, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LSEG_HIP_TRY(hipEventRecord(ev_ovf_, st));
+    ovf_pending_ = true;
+    return 0;
+}
+
+// corr_low, the tails with planes: R = rpl_ [B, kout, h + 2, w + 2], the unscaled dot products t_k . g (PLANES_FUSED: scale_plane's kernel
+// wrote them).  low_ -- their scaled x2 upsample -- is left pending: materialize_low makes it where someone needs it in memory
+int Engine::label_planes(int B, FwdPlanes src, hipStream_t st) {
+    const lseg_config& c = cfg;
+    const int hp = lh_[0] + 2, wp = lw_[0] + 2;
+    if (src == PLANES_GROUPED) {
+        // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [k, out_c] x [out_c, hp*wp]
+        for (int b = 0; b < B; ++b)
+            TRY(correlate_planes(tnorm_ + (size_t)b * group_k * c.out_c, g16pad_ + (size_t)b * hp * wp * c.out_c, group_k, hp * wp, hp * wp,
+                                 rpl_ + (size_t)b * group_k * hp * wp, 0, st));
+    } else if (src == PLANES_GENERIC) {
+        // round_mid 0: R holds the unscaled dot products t_k . g as they are; the scale plane comes in with the upsample
+        TRY(correlate_planes(tnorm_, g16pad_, K_, B * hp * wp, hp * wp, rpl_, 0, st));
     }
+    const int kk = group_k > 0 ? group_k : K_;
+    low_pending_ = true; low_planes_ = B * kk; low_k_ = kk;
+    return 0;
+}
 
-    // ---- head1 + normalise + correlation (lseg_net.py:185-196) ------------------------------------------------
+// not corr_low: head1 + normalise (lseg_net.py:185-196) into a16_ at (2h, 2w) by the tail's feature path, then the correlation into low_
+int Engine::feature_planes(FwdTail tail, int B, hipStream_t st) {
+    const lseg_config& c = cfg;
     const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp = B * hw1;
-    // ... and so does the correlation: t_k . up(g)_P = up(t_k . g)_P, with ||up(g)_P|| from the dot products of g's 2x2 cells
-    // (elementwise.hip "commuted correlation"): the pixel x text GEMM runs on 4x fewer pixels and the 240x240x512 feature map never exists
-    static const bool corr_full = getenv("LSEG_CORR_FULLRES") != nullptr;           // A/B switch (tools): the correlation at (2h, 2w)
-    const bool corr_low = commuted && !corr_full && (lw_[0] % 2) == 0;
-    if (corr_low) {
-        const int hp = lh_[0] + 2, wp = lw_[0] + 2;
-        g = lin_args(t2_[0], headc_, B * hp * wp, g16pad_, DT_F16);      // every row of the padded map (border rows are never read)
-        TRY(igemm(g, st));
-        // the dedicated kernel (corr.hip): T resident in LDS, g streamed once, label planes and cell dot products from the same registers;
-        // per-image label sets (zero-shot), other widths and label sets that do not fit the LDS take the generic GEMM + pixel_gram pair
-        static const bool corr_generic = getenv("LSEG_CORR_GENERIC") != nullptr;    // A/B switch (tools, tests): the round-4 pair
-        const bool corr_fused = !held && !corr_generic && group_k == 0 && !ragged() && corr_planes_supported(K_, c.out_c);
-        // "correlation" family = the dedicated kernel only (label planes + cell dot products; algorithmic BYTES in the flops slot): the generic
-        // pair is not bracketed, so no event is taken that would never be paired (the pool is sized per family and forward)
-        hipEvent_t pc = corr_fused ? prof_begin(PF_CORR, st) : nullptr;
-        if (corr_fused) TRY(launch_corr_planes(g16pad_, tnorm_, rpl_, gram_, B, K_, lh_[0], lw_[0], c.out_c, st));
-        else TRY(launch_pixel_gram(g16pad_, gram_, B, lh_[0], lw_[0], c.out_c, st));
-        if (corr_fused) prof_end(PF_CORR, pc, (double)B * hp * wp * c.out_c * 2.0 + (double)B * K_ * lh_[0] * lw_[0] * 4.0 + (double)B * lh_[0] * lw_[0] * 20.0 +
-                                              (double)K_ * c.out_c * 2.0, st);
-        TRY(launch_norm_scale_plane(gram_, nscale_, B, lh_[0], lw_[0], logit_scale(), st, ovf_dev_));
-        // the sentinel travels to pinned host memory behind the forward; Engine::overflow_seen reads it once the event has passed (no sync)
-        (void)overflow_seen(false);                      // harvest the previous forward's copy before its event is recorded again
-        LSEG_HIP_TRY(hipMemcpyAsync(ovf_host_, ovf_dev_, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        LSEG_HIP_TRY(hipEventRecord(ev_ovf_, st));
-        ovf_pending_ = true;
-        if (held) {
-            // what the correlation reads, handed to the caller: any label panel can be scored from it later (score_features).  The gram
-            // above is pixel_gram's for every K, so the scale plane is the one lseg_forward_lowres uses on its generic route (K > 157)
-            size_t fb = 0, sb = 0;
-            features_bytes(B, &fb, &sb);
-            LSEG_HIP_TRY(hipMemcpyAsync(held->feat, g16pad_, fb, hipMemcpyDeviceToDevice, st));
-            LSEG_HIP_TRY(hipMemcpyAsync(held->scale, nscale_, sb, hipMemcpyDeviceToDevice, st));
-            labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;       // the state of a streamed forward: no low-resolution logits exist
-            prof_end(PF_FWD, fwd0, 0.0, st);
-            return 0;
-        }
-        // masks only, any K: the labels stream past a running (best, arg) pair per output pixel (corr_argmax.hip) -- no (2h, 2w) logits, no
-        // full-resolution planes.  The scale plane must be the logits path's bit for bit, so the gram comes from where it comes there: for
-        // K <= 157 from corr_planes_kernel (which also writes its quarter-resolution planes into rpl_, 8.9 MB per image at K = 150, that
-        // nothing reads here: the two grams differ in the last bits and the score would no longer equal logits.max), above from pixel_gram
-        if (ragged()) {
-            // per-image label sets of any size (check_ragged let only the streamed labels through): the scale plane from pixel_gram, as for
-            // K > 157 above -- corr_planes has no per-image form; low_ is the workspace of the label parts, sized from the largest list
-            const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
-            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, out16, B, 0, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, loss, groups_.data(), d_goff_));
-            labels_only_ = true; last_low_ = nullptr; last_kout_ = 0;
-            prof_end(PF_FWD, fwd0, 0.0, st);
-            return 0;
-        }
-        if (label_out && !logits && !argmax_out && !corr_generic && group_k == 0 && c.arch_option == 0 && corr_argmax_supported(K_, c.out_c)) {
-            // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
-            const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);
-            TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, out16, B, K_, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, loss));
-            labels_only_ = true; last_low_ = nullptr; last_kout_ = K_;
-            prof_end(PF_FWD, fwd0, 0.0, st);
-            return 0;
-        }
-        if (corr_fused) {
-        } else if (group_k > 0) {
-            // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [k, out_c] x [out_c, hp*wp]
-            for (int b = 0; b < B; ++b)
-                TRY(correlate_planes(tnorm_ + (size_t)b * group_k * c.out_c, g16pad_ + (size_t)b * hp * wp * c.out_c, group_k, hp * wp, hp * wp,
-                                     rpl_ + (size_t)b * group_k * hp * wp, 0, st));
-        } else {
-            // round_mid 0: R holds the unscaled dot products t_k . g as they are; the scale plane comes in with the upsample
-            TRY(correlate_planes(tnorm_, g16pad_, K_, B * hp * wp, hp * wp, rpl_, 0, st));
-        }
-        // R -> logits.  When only the full-resolution logits are wanted the two x2 upsamples run as one pass and the (2h, 2w) logits
-        // stay in LDS; masks, head blocks, the "lowres" tap and lseg_forward_stats need them in memory (made on demand below).
-        const int kk = group_k > 0 ? group_k : K_;
-        low_pending_ = true; low_planes_ = B * kk; low_k_ = kk;
-        static const bool no_4x = getenv("LSEG_NO_UPSAMPLE4X") != nullptr;          // A/B switch (tools)
-        if (logits && !argmax_out && c.arch_option == 0 && !no_4x) {
-            TRY(launch_upsample4x_planes_scaled(rpl_, nscale_, logits, B * kk, kk, lh_[0], lw_[0], st));
-            last_low_ = low_; last_kout_ = kk;
-            prof_end(PF_FWD, fwd0, 0.0, st);
-            return 0;
-        }
-        // lseg_forward_lowres with nothing else wanted: the (2h, 2w) logits go straight into the caller's buffer; low_ stays pending, as
-        // after the one-pass x4 upsample (forward_stats / episode_stats / the "lowres" tap make it on demand from the same R and scale plane)
-        if (low_out && !logits && !argmax_out && !label_out && c.arch_option == 0) {
-            TRY(launch_upsample2x_planes_scaled(rpl_, nscale_, low_out, B * kk, kk, lh_[0], lw_[0], st));
-            last_low_ = low_; last_kout_ = kk;
-            prof_end(PF_FWD, fwd0, 0.0, st);
-            return 0;
-        }
-        TRY(materialize_low(st));
-    } else if (commuted) {
+    GemmArgs g;
+    if (tail == TAIL_FEAT_COMMUTED) {
         // g = Wc t2 + bc on every row of the padded map (border rows are never read), fp32; then x2 bilinear + L2-norm + fp16 casts
         g = lin_args(t2_[0], headc_, B * (lh_[0] + 2) * (lw_[0] + 2), gpad_, DT_F32);
         TRY(igemm(g, st));
         TRY(launch_upsample_norm_f16(gpad_, a16_, B, lh_[0], lw_[0], c.out_c, logit_scale(), st));
-    } else if (c.out_c == 512 && !debug && !strict_) {
+    } else if (tail == TAIL_FEAT_ROWNORM) {
         // fused: head1 + fp32 L2-norm + the two fp16 roundings in one epilogue (rows are complete inside
         // a workgroup); the 118 MB/image fp32 feature map is never written
         g = lin_args(path_[0], head1_, Mp, a16_, DT_F16);
@@ -1276,10 +1153,7 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
         TRY(igemm(g, st));
         TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale(), st));
     }
-    const int Kout = group_k > 0 ? group_k : K_;            // label planes per image
-    if (corr_low) {
-        // low_ already holds the (2h, 2w) logits
-    } else if (group_k > 0) {
+    if (group_k > 0) {
         // lseg_net_zs.py:198-208: image b against its own k text rows -- B small GEMMs [hw1,out_c] x [out_c,k]
         for (int b = 0; b < B; ++b) {
             gemm_args_init(g);
@@ -1291,28 +1165,136 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
     } else {
         TRY(correlate_planes(tnorm_, a16_, K_, Mp, hw1, low_, 1, st));
     }
-    float* low = low_;
-    if (c.arch_option == 1 || c.arch_option == 2) {                    // lseg_net.py:198-201
+    return 0;
+}
+
+// the planes in memory: the arch_option 1 / 2 head blocks (lseg_net.py:198-201) on low_, which stays intact (the "lowres" tap)
+int Engine::head_blocks(int B, int kout, const float** low, hipStream_t st) {
+    const lseg_config& c = cfg;
+    *low = low_;
+    if (c.arch_option == 1 || c.arch_option == 2) {
         const int bott = c.arch_option == 1;
-        float* src = low_; float* dst = low2_;           // low_ stays intact (the "lowres" tap)
+        float* src = low_; float* dst = low2_;
         for (int d = 0; d < c.block_depth - 1; ++d) {
-            TRY(launch_head_block(src, dst, hb_w_, hb_b_, B, Kout, h1, w1, bott, c.activation, 1, st));
+            TRY(launch_head_block(src, dst, hb_w_, hb_b_, B, kout, 2 * lh_[0], 2 * lw_[0], bott, c.activation, 1, st));
             src = dst; dst = (dst == low2_) ? low3_ : low2_;
         }
-        TRY(launch_head_block(src, dst, hb_w_, hb_b_, B, Kout, h1, w1, bott, c.activation, 0, st));
-        low = dst;
+        TRY(launch_head_block(src, dst, hb_w_, hb_b_, B, kout, 2 * lh_[0], 2 * lw_[0], bott, c.activation, 0, st));
+        *low = dst;
     }
+    return 0;
+}
+
+// the int16 masks and what rides with them
+static CorrOut corr_out(const Engine::ForwardOut& o) { return CorrOut{o.label, o.score, o.conf.label2, o.conf.score2, o.conf.lse, nullptr}; }
+
+// ... and every output from them
+int Engine::planes_outputs(const ForwardOut& out, const float* low, int B, int kout, hipStream_t st) {
+    const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
+    // (after the planes are in memory, not in check_request: the refused call leaves them to forward_stats / the "lowres" tap, as it always did)
+    if (out.argmax && kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", kout);
     // masks = argmax over the labels of the x2-upsampled logits (what every caller of the reference computes from the full tensor:
     // torch.max(pred, 1), lsegmentation_module.py:114-117), read through the bilinear on the fly: no 138 MB / image logits needed
-    last_low_ = low; last_kout_ = Kout;
-    if (argmax_out && Kout > 256) return set_error(LSEG_ERR_UNSUPPORTED, "uint8 masks need K <= 256 (K=%d)", Kout);
-    if (argmax_out) TRY(launch_seg_stats_ex(low, nullptr, B, Kout, 4 * hw1, -1, nullptr, nullptr, argmax_out, 1, h1, w1, st));
+    if (out.argmax) TRY(launch_seg_stats_ex(low, nullptr, B, kout, 4 * hw1, -1, nullptr, nullptr, out.argmax, 1, h1, w1, st));
     // the int16 form, on the planes in memory (with the runner-up and the log-sum-exp when lseg_forward_labels_conf asks for them)
-    if (label_out) TRY(launch_seg_labels16(low, B, Kout, h1, w1, out16, loss, st));
+    if (out.label) TRY(launch_seg_labels16(low, B, kout, h1, w1, corr_out(out), out.loss, st));
     // ---- scratch.output_conv: bilinear x2, align_corners=True (lseg_net.py:203) ----------------------------------
-    if (logits) TRY(launch_upsample2x_planes(low, logits, B * Kout, h1, w1, st));
+    if (out.logits) TRY(launch_upsample2x_planes(low, out.logits, B * kout, h1, w1, st));
     // every other schedule (head blocks, the full-resolution correlation, debug / split-precision) has them in engine memory: a copy
-    if (low_out) LSEG_HIP_TRY(hipMemcpyAsync(low_out, low, (size_t)B * Kout * hw1 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (out.low) LSEG_HIP_TRY(hipMemcpyAsync(out.low, low, (size_t)B * kout * hw1 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int Engine::forward(const float* x_in, int B, const ForwardOut& out, hipStream_t st) {
+    const RouteIn rin = route_in(out);
+    TRY(check_request(x_in, B, out, rin));
+    LSEG_HIP_TRY(hipSetDevice(device));
+    labels_only_ = false;
+    if (train_mode) return forward_train(x_in, B, out.logits, st);
+    if (eval_stale_) TRY(finalize(st));  // optimizer steps refresh only the train-mode packs: fold BatchNorm / the commuted head again
+    const lseg_config& c = cfg;
+    const Route rt = forward_route(rin);
+    const bool held = rt.tail == TAIL_HELD;                 // (check_request refused a held request anywhere else)
+    last_B_ = B;
+    low_pending_ = false;
+    hipEvent_t fwd0 = prof_begin(PF_FWD, st);
+
+    if (!held) TRY(text_fork(st));       // ---- text tower (lseg_net.py:181-183) on the side stream; held features read no text
+    TRY(image_tower(x_in, B, st));
+    // ---- refinenet4..1 (lseg_net.py:176-179) ---------------------------------------------------------------
+    // commuted, the fast path of the head: the two 1x1 convs after refinenet1's upsample -- out_conv and head1 -- commute with it and run
+    // as ONE GEMM at the quarter resolution (elementwise.hip "commuted head")
+    for (int r = 4; r >= 1; --r) TRY(refine(r, B, st, rt.commuted && r == 1));
+    if (!held) {
+        TRY(text_join(st));              // before the correlation
+        TRY(check_grouping(B));          // (here, not in check_request: a forked text tower is joined before the call fails, as it always was)
+    }
+
+    // ---- head1 + normalise + correlation (lseg_net.py:185-196) ------------------------------------------------
+    // corr_low: the correlation commutes with the upsample too: t_k . up(g)_P = up(t_k . g)_P, with ||up(g)_P|| from the dot products of
+    // g's 2x2 cells (elementwise.hip "commuted correlation"): the pixel x text GEMM runs on 4x fewer pixels and the 240x240x512 feature map
+    // never exists
+    if (rt.corr_low) TRY(scale_plane(B, rt.corr_fused, st));
+    const int kout = group_k > 0 ? group_k : K_;            // label planes per image
+    const size_t ws_bytes = (size_t)c.max_batch * c.max_labels * 4 * lh_[0] * lw_[0] * sizeof(float);     // low_ as the streamed kernel's workspace
+    const float* low = nullptr;          // the (2h, 2w) logits this forward leaves to forward_stats / episode_stats / the "lowres" tap
+    int last_k = kout;
+    bool in_memory = false;              // ... and whether the outputs are still to be made from them
+    switch (rt.tail) {
+    case TAIL_HELD: {
+        // what the correlation reads, handed to the caller: any label panel can be scored from it later (score_features).  The gram
+        // is pixel_gram's for every K, so the scale plane is the one lseg_forward_lowres uses on its generic route (K > 157)
+        size_t fb = 0, sb = 0;
+        features_bytes(B, &fb, &sb);
+        LSEG_HIP_TRY(hipMemcpyAsync(out.held->feat, g16pad_, fb, hipMemcpyDeviceToDevice, st));
+        LSEG_HIP_TRY(hipMemcpyAsync(out.held->scale, nscale_, sb, hipMemcpyDeviceToDevice, st));
+        last_k = 0;                      // the state of a streamed forward: no low-resolution logits exist
+        break;
+    }
+    // masks only, any K: the labels stream past a running (best, arg) pair per output pixel (corr_argmax.hip) -- no (2h, 2w) logits, no
+    // full-resolution planes.  The scale plane must be the logits path's bit for bit, so the gram comes from where it comes there: for
+    // K <= 157 from corr_planes_kernel (which also writes its quarter-resolution planes into rpl_, 8.9 MB per image at K = 150, that
+    // nothing reads here: the two grams differ in the last bits and the score would no longer equal logits.max), above from pixel_gram
+    case TAIL_STREAM_RAGGED:
+        // per-image label sets of any size: the scale plane from pixel_gram, as for K > 157 above -- corr_planes has no per-image form;
+        // low_ is the workspace of the label parts, sized from the largest list
+        TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, corr_out(out), B, 0, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, out.loss, groups_.data(), d_goff_));
+        last_k = 0;
+        break;
+    case TAIL_STREAM_SHARED:
+        // (low_ holds no planes of this forward: it is the workspace of the kernel's label splits)
+        TRY(launch_corr_argmax(g16pad_, tnorm_, nscale_, corr_out(out), B, K_, lh_[0], lw_[0], c.out_c, st, low_, ws_bytes, out.loss));
+        last_k = K_;
+        break;
+    // R -> logits.  When only the full-resolution logits are wanted the two x2 upsamples run as one pass and the (2h, 2w) logits
+    // stay in LDS; masks, head blocks, the "lowres" tap and lseg_forward_stats need them in memory (materialize_low, here or on demand)
+    case TAIL_X4_LOGITS:
+        TRY(label_planes(B, rt.planes, st));
+        TRY(launch_upsample4x_planes_scaled(rpl_, nscale_, out.logits, B * kout, kout, lh_[0], lw_[0], st));
+        low = low_;
+        break;
+    case TAIL_X2_LOW_OUT:
+        // lseg_forward_lowres with nothing else wanted: the (2h, 2w) logits go straight into the caller's buffer; low_ stays pending, as
+        // after the one-pass x4 upsample
+        TRY(label_planes(B, rt.planes, st));
+        TRY(launch_upsample2x_planes_scaled(rpl_, nscale_, out.low, B * kout, kout, lh_[0], lw_[0], st));
+        low = low_;
+        break;
+    case TAIL_PLANES:
+        TRY(label_planes(B, rt.planes, st));
+        TRY(materialize_low(st));
+        in_memory = true;
+        break;
+    case TAIL_FEAT_COMMUTED: case TAIL_FEAT_ROWNORM: case TAIL_FEAT_HEAD1:
+        TRY(feature_planes(rt.tail, B, st));
+        in_memory = true;
+        break;
+    }
+    if (in_memory) TRY(head_blocks(B, kout, &low, st));
+    // ---- the one exit: what the next forward_stats / episode_stats / profile finds
+    labels_only_ = low == nullptr;       // held features, streamed labels: low_ holds no planes of this forward
+    last_low_ = low; last_kout_ = last_k;
+    if (in_memory) TRY(planes_outputs(out, low, B, kout, st));
     prof_end(PF_FWD, fwd0, 0.0, st);
     return 0;
 }
@@ -1321,8 +1303,8 @@ int Engine::forward(const float* x_in, int B, float* logits, uint8_t* argmax_out
 // seg_labels16's loss form on the planes in memory), then the counters of lseg_op_label_stats from the label map just written
 int Engine::forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out,
                                 float* lse_out, float* nll_plane_out, double* nll, int64_t* counts, hipStream_t st) {
-    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_forward_labels_loss is an inference feature (train mode is on: lseg_train_loss has the loss)");
     if (!label_out || !target) return set_error(LSEG_ERR_INVALID, "forward_labels_loss: NULL label output or target");
+    if (train_mode) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_forward_labels_loss is an inference feature (train mode is on: lseg_train_loss has the loss)");
     const size_t plane = (((size_t)cfg.max_batch * cfg.img_h * cfg.img_w * sizeof(float)) + 255) / 256 * 256;
     const size_t part = corr_loss_partial_bytes_max();       // any B <= max_batch: the most workgroups the reduction ever takes
     if (!loss_ws_) {
@@ -1333,8 +1315,9 @@ int Engine::forward_labels_loss(const float* x, int B, const int64_t* target, in
     const bool red = nll || nll_plane_out;
     const CorrLoss loss{target, ignore_index, red ? reinterpret_cast<float*>(loss_ws_ + plane) : nullptr, nll_plane_out, nll,
                         reinterpret_cast<double*>(loss_ws_ + 2 * plane)};
-    const LabelConf conf{nullptr, nullptr, red || lse_out ? lse : nullptr};
-    TRY(forward(x, B, nullptr, nullptr, st, label_out, score_out, nullptr, &conf, nullptr, &loss));
+    ForwardOut out;
+    out.label = label_out; out.score = score_out; out.conf.lse = red || lse_out ? lse : nullptr; out.loss = &loss;
+    TRY(forward(x, B, out, st));
     if (!counts) return 0;
     int64_t* flags = reinterpret_cast<int64_t*>(loss_ws_ + 2 * plane + part);
     int kmax = 0;

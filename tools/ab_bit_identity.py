@@ -1,6 +1,7 @@
 """Bit identity of two builds of liblseg_hip.so: sha256 of every output tensor of a fixed list of small cases that together reach each
 GEMM descriptor and stage the forwards, the text tower and the backward share (csrc/engine.h builders, Engine::patch_embed /
-reassemble / out_conv / correlate_planes).  A host-side restructuring of the schedule must leave every line unchanged.
+reassemble / out_conv / correlate_planes) and every output tail of Engine::forward (csrc/forward_route.h).  A host-side restructuring
+of the schedule must leave every line unchanged.
 
     python tools/ab_bit_identity.py --lib OLD/liblseg_hip.so --out old.txt
     python tools/ab_bit_identity.py --out new.txt          # the in-tree build
@@ -77,6 +78,64 @@ def run_train(case, backbone, S, B, K, group=0, freeze=False, **kw):
     eng.close()
 
 
+def run_routes(case, backbone, S, B, K, ragged=None, want=("lowres", "conf", "loss", "features"), **kw):
+    """the output tails of Engine::forward that run_eval does not reach (csrc/forward_route.h), each as its own forward of one engine"""
+    import torch
+    eng, _, x = engine(backbone, S, B, K, "fp16", **kw)
+    target = torch.randint(-1, K, (B, S, S), generator=torch.Generator().manual_seed(11)).cuda()
+
+    def emit_dict(name, d):
+        for k in sorted(d):
+            emit(case, f"{name}.{k}", d[k])
+
+    if "logits" in want:
+        emit(case, "logits", eng.forward(x))
+    if "lowres" in want:
+        emit(case, "forward_lowres", eng.forward_lowres(x))
+    if "labels" in want:
+        lab, score = eng.forward_labels(x, want_score=True)
+        emit(case, "labels", lab)
+        emit(case, "score", score)
+    if "masks" in want:                                         # K > 256: the int16 fallback of want_argmax
+        emit(case, "masks", eng.forward(x, want_logits=False, want_argmax=True))
+    if "conf" in want:
+        emit_dict("conf", eng.forward_labels_conf(x))
+    if "loss" in want:
+        emit_dict("loss", eng.forward_labels_loss(x, target))
+        emit_dict("loss_plane", eng.forward_labels_loss(x, target, plane=True))
+    if "features" in want:
+        feat, scale = eng.forward_features(x)
+        emit(case, "feat", feat)
+        emit(case, "scale", scale)
+        half = K // 2
+        emit(case, "score_features.0", eng.score_features(feat, scale, 0, half))
+        emit(case, "score_features.1", eng.score_features(feat, scale, half, K - half))
+    if "stats" in want:                                         # after a logits-only forward: the (2h, 2w) logits are made on demand
+        eng.forward(x)
+        st = eng.forward_stats(target)
+        emit(case, "forward_stats", torch.cat([torch.tensor([st["correct"], st["labeled"], st["nll_count"]]), st["area_inter"], st["area_pred"],
+                                               st["area_lab"]]))
+        emit(case, "forward_stats.nll", torch.tensor([st["nll_sum"]], dtype=torch.float64))
+        if K == 2:
+            eng.forward(x)
+            emit_dict("episode_stats", eng.episode_stats(target.clamp(min=0), ignore_index=-100))
+    if ragged:                                                  # per-image label lists over the same K rows
+        eng.set_tokens(eng_tokens(eng, K), group_sizes=ragged)
+        tr = torch.stack([torch.randint(-1, k, (S, S), generator=torch.Generator().manual_seed(13 + b)) for b, k in enumerate(ragged)]).cuda()
+        lab, score = eng.forward_labels(x, want_score=True)
+        emit(case, "ragged.labels", lab)
+        emit(case, "ragged.score", score)
+        emit_dict("ragged.conf", eng.forward_labels_conf(x))
+        emit_dict("ragged.loss", eng.forward_labels_loss(x, tr))
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def eng_tokens(eng, K):
+    from lseg_hip.synth import synthetic_tokens
+    return synthetic_tokens([LABELS[i % len(LABELS)] for i in range(K)], eng.cfg.text.vocab, eng.cfg.text.ctx)
+
+
 ALL3, TWO = ("fp16", "bf16", "strict"), ("fp16", "bf16")
 CASES = {
     # ConvT / identity / conv-s2 resamples, split-K slabs at B = 1, the commuted head, the one-pass x4 upsample, the streamed labels
@@ -100,8 +159,19 @@ CASES = {
     # real width: the 256-wide tile choices, split_residual
     "vitl16_b1": lambda c: run_eval(c, "clip_vitl16_384", 96, 1, 5, TWO),
     "vitl16_train": lambda c: run_train(c, "clip_vitl16_384", 96, 1, 5),
+    # ---- the tails of Engine::forward beyond logits / masks / labels (forward_route.h).  out_c 128 (tiny16): pixel_gram + the generic GEMM
+    "tiny16_routes": lambda c: run_routes(c, "tiny16", 64, 2, 5, want=("lowres", "conf", "loss", "features", "stats")),
+    "tiny16_episode": lambda c: run_routes(c, "tiny16", 64, 2, 2, want=("stats",)),
+    "tiny16_arch1_routes": lambda c: run_routes(c, "tiny16", 64, 2, 5, want=("labels", "lowres"), arch_option=1, block_depth=2),
+    "tiny16_no_upsample4x": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO),                     # the parent sets LSEG_NO_UPSAMPLE4X=1
+    "tiny16_corr_fullres": lambda c: run_eval(c, "tiny16", 64, 2, 5, TWO),                      # the parent sets LSEG_CORR_FULLRES=1
+    # out_c 512: the dedicated correlation kernel (K <= 157), the streamed labels with confidence and loss, shared set and ragged lists
+    "vitl16_routes": lambda c: run_routes(c, "clip_vitl16_384", 96, 2, 5, ragged=[2, 3]),
+    "vitl16_k160": lambda c: run_routes(c, "clip_vitl16_384", 96, 1, 160, want=("logits", "lowres", "labels")),     # past corr_planes' LDS
+    "vitl16_k300": lambda c: run_routes(c, "clip_vitl16_384", 96, 1, 300, want=("labels", "masks")),               # past uint8
 }
-CHILD_ENV = {"tiny16_corr_generic": {"LSEG_CORR_GENERIC": "1"}}
+CHILD_ENV = {"tiny16_corr_generic": {"LSEG_CORR_GENERIC": "1"}, "tiny16_no_upsample4x": {"LSEG_NO_UPSAMPLE4X": "1"},
+             "tiny16_corr_fullres": {"LSEG_CORR_FULLRES": "1"}}
 
 
 def main():
@@ -128,8 +198,8 @@ def main():
             print(f"unknown case '{name}'", file=sys.stderr)
             return 2
         env = dict(os.environ, LSEG_SYNTHETIC_TOKENS="1", **CHILD_ENV.get(name, {}))
-        if a.lib:
-            env["LSEG_HIP_LIB"] = os.path.abspath(a.lib)
+        if a.lib:                                              # (an older build may lack entry points declared since: none is called here)
+            env.update(LSEG_HIP_LIB=os.path.abspath(a.lib), LSEG_HIP_ALLOW_MISSING="1")
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], env=env, stdout=subprocess.PIPE, text=True,
                                timeout=a.timeout)
