@@ -645,6 +645,16 @@ int lseg_op_label_stats_plan(int K_or_bins, int* out2);
  * feature map made by the commuted head + upsample_norm / the row-norm GEMM / head1 + l2norm.  planes (tails 3..5): 1 the dedicated
  * correlation kernel, 2 per-image GEMMs, 3 the generic GEMM; 0 elsewhere.  The route of a refused request is unspecified. */
 int lseg_op_forward_route(const int32_t* in13, int n, int32_t* out6);
+/* How the label head of the training step runs for a configuration, and whether the train-mode forward refuses it: host only, no handle,
+ * no device.  n rows; row i reads in11 + 11 i = {group_k, ragged lists set, longest list, K, head blocks (0: none), arch_option,
+ * lseg_config.flags bit 1 set, image dtype (LSEG_F16 | LSEG_BF16), out_c, a logits output wanted, LSEG_CORR_RAGGED_GEMM set} and writes
+ * out8 + 8 i = {refusal status (0 | LSEG_ERR_UNSUPPORTED; the refusals that read the engine's state are not in it), mode, label planes
+ * per image, row pitch of d(low) (up64 of the longest list | 8 | up64(K)), dtype of the d(low) rows, a transposed dgrad operand is made,
+ * head blocks run, which refusal}.  refusal, the first that holds: 1 either grouping with arch_option != 0, 2 ragged lists with a logits
+ * output, 3 group_k outside 1..8 or out_c not a multiple of 8 in [8, 1024]; 0 none.
+ * mode: 0 one label set shared by the batch, 1 group_k labels per image, 2 ragged lists on per-image GEMMs, 3 ragged lists on the
+ * one-launch kernels. */
+int lseg_op_train_head_plan(const int32_t* in11, int n, int32_t* out8);
 int lseg_op_label_stats(const int16_t* d_label, const int64_t* d_target, int B, int H, int W, int K, int ignore_index,
                         const int32_t* d_offsets, const int32_t* d_class_map, int nclass, int64_t* d_counts, int64_t* d_flags,
                         int accumulate, void* stream);

@@ -739,6 +739,21 @@ int lseg_op_forward_route(const int32_t* in13, int n, int32_t* out6) {
     return LSEG_OK;
 }
 
+// train_head.h: the plan of the training step's label head for n configurations (host only, no engine, no device)
+int lseg_op_train_head_plan(const int32_t* in11, int n, int32_t* out8) {
+    if (!in11 || !out8 || n < 1) return set_error(LSEG_ERR_INVALID, "train_head_plan: NULL pointer or n < 1");
+    for (int i = 0; i < n; ++i, in11 += 11, out8 += 8) {
+        TrainHeadIn r;
+        r.group_k = in11[0]; r.ragged = in11[1]; r.kmax = in11[2]; r.K = in11[3]; r.hb_n = in11[4]; r.arch_option = in11[5];
+        r.unrounded = in11[6]; r.img_dt = in11[7]; r.out_c = in11[8]; r.logits = in11[9]; r.ragged_gemm = in11[10];
+        const TrainHead p = train_head_plan(r);
+        out8[0] = p.refusal == TRAIN_REFUSE_NONE ? 0 : LSEG_ERR_UNSUPPORTED;
+        out8[1] = p.mode; out8[2] = p.kout; out8[3] = p.Kp; out8[4] = p.hdt; out8[5] = p.dgrad_operand; out8[6] = p.head_blocks;
+        out8[7] = p.refusal;
+    }
+    return LSEG_OK;
+}
+
 // label_stats.hip: every check of these launchers comes before the device is touched (a refusal needs no device)
 int lseg_op_label_stats_plan(int K_or_bins, int* out2) { return label_stats_plan(K_or_bins, out2); }
 int lseg_op_label_stats(const int16_t* d_label, const int64_t* d_target, int B, int H, int W, int K, int ignore_index, const int32_t* d_offsets,

@@ -7,6 +7,7 @@
 
 #include "ops.h"
 #include "forward_route.h"
+#include "train_head.h"
 #include "../../include/lseg_hip.h"
 
 namespace lseg {
@@ -146,8 +147,6 @@ public:
     int grad_ptr(const char* key, float** out, size_t* n);
     int backward(const float* dlogits, const int64_t* target, int ignore_index, int accumulate, double* dev_loss2, hipStream_t st,
                  const float* dev_grad_scale = nullptr);
-    int head_blocks_backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
-                             const float* dev_grad_scale, int hdt, int Kp);
     int train_loss(const int64_t* target, int ignore_index, double* dev_loss2, int64_t* dev_counts2, hipStream_t st);
     int sgd_momentum(const char* key, float** out, size_t* n);
     int sgd_mark_initialized(bool on) { sgd_first_ = !on; return 0; }
@@ -199,6 +198,11 @@ private:
     // ---- Engine::forward: the request as plain values and its refusals before any launch (forward_request.hip), the stages of its tails
     RouteIn route_in(const ForwardOut& out) const;
     int check_request(const float* x, int B, const ForwardOut& out, const RouteIn& r);
+    // ... and of the training step: forward_train, train_loss and backward refuse here, before any state changes
+    TrainHeadIn train_head_in(bool logits) const;
+    int check_train_forward(int B, const TrainHead& plan);
+    int check_train_loss(const int64_t* target);
+    int check_backward(const float* dlogits, const int64_t* target, const float* dev_grad_scale);
     int image_tower(const float* x_in, int B, hipStream_t st);                 // ViT blocks + reassemble, or ResNet-101 + layerN_rn -> rn_[0..3]
     int scale_plane(int B, bool corr_fused, hipStream_t st);                   // g16pad_, gram_ (corr_fused: rpl_ too), nscale_, overflow sentinel
     int label_planes(int B, FwdPlanes src, hipStream_t st);                    // rpl_ = the label planes at quarter resolution; low_ pending
@@ -215,6 +219,14 @@ private:
     int train_alloc();
     int finalize_train(hipStream_t st);
     int forward_train(const float* x, int B, float* logits, hipStream_t st);
+    // the label head of the training step, each stage a switch over train_head_.mode (train_head.h)
+    int train_correlate(const TrainHead& plan, int B, hipStream_t st);                          // a16_ -> low_, the dgrad operand where the plan has one
+    int ensure_loss(const int64_t* target, int ignore_index, hipStream_t st, bool force = false);      // nll_, counts_, lse_px_ of this forward and target, once
+    int publish_loss(double* dev_loss2, int64_t* dev_counts2, hipStream_t st);
+    int loss_rows(const TrainHead& plan, const float* dlogits, const int64_t* target, int ignore_index, double* dev_loss2,
+                  const float* dev_grad_scale, hipStream_t st);                 // drows_ = d(low) rows [B*hw1, Kp], or the head blocks' planes in low2_
+    int head_blocks_backward(const TrainHead& plan, int acc, hipStream_t st);                   // gradient planes in low2_ -> drows_, {dW, db}
+    int train_correlate_backward(const TrainHead& plan, hipStream_t st);                        // drows_ -> df_
     int rcu_train(const uint16_t* in, const uint16_t* in_relu, Rcu& U, const uint16_t* res2, uint16_t* out, uint16_t* out_relu, int B, int H, int W,
                   hipStream_t st);
     int rcu_backward(const uint16_t* dout, const uint16_t* in, Rcu& U, uint16_t* din, int lev, int B, int H, int W, int acc, hipStream_t st);
@@ -326,11 +338,10 @@ private:
     bool train_alloc_ = false, train_fwd_valid_ = false;
     const int64_t* loss_target_ = nullptr; int loss_ignore_ = 0;      // train_loss() already ran seg_stats for this forward and this target
     int train_B_ = 0;
-    int train_G_ = 0;             // labels per image of the last train-mode forward (0: one label set shared by the batch)
-    // ragged per-image label sets of the last train-mode forward (empty: none): host prefix sums [B + 1] (d_goff_ holds them on the
-    // device), the largest count, and the per-image transposed text panels [out_c, up64(k_b)] of the correlation backward, concatenated
+    TrainHead train_head_;        // how the label head of the last train-mode forward ran: the plan train_loss and backward follow
+    // ragged per-image label sets of the last train-mode forward (train_head_.ragged()): host prefix sums [B + 1] (d_goff_ holds them
+    // on the device) and the per-image transposed text panels [out_c, up64(k_b)] of the correlation backward, concatenated
     std::vector<int> train_rag_;
-    int train_rag_kmax_ = 0;
     uint16_t* tnT_rag_ = nullptr;
     std::vector<BlockSave> sv_;
     float* xlast_ = nullptr;               // output of the last block (= xin of a virtual block `depth`)

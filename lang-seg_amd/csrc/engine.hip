@@ -1338,7 +1338,7 @@ int Engine::materialize_low(hipStream_t st) {
 int Engine::forward_stats(const int64_t* target, int ignore_index, int64_t* counts, double* nll, hipStream_t st) {
     if (labels_only_) return set_error(LSEG_ERR_STATE, "the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
     if (!last_low_ || last_B_ < 1) return set_error(LSEG_ERR_STATE, "no forward has run");
-    if (!train_rag_.empty()) return set_error(LSEG_ERR_STATE, "the last forward was a train-mode forward with ragged label sets: its planes are not rectangular (lseg_train_loss reads them)");
+    if (train_head_.ragged()) return set_error(LSEG_ERR_STATE, "the last forward was a train-mode forward with ragged label sets: its planes are not rectangular (lseg_train_loss reads them)");
     if (!target || !counts || !nll) return set_error(LSEG_ERR_INVALID, "forward_stats: NULL pointer");
     LSEG_HIP_TRY(hipSetDevice(device));
     TRY(materialize_low(st));
@@ -1356,8 +1356,8 @@ int Engine::episode_stats(const int64_t* target, const uint8_t* ignore, int igno
     int B = 0, kout = 0;
     if (train_mode) {
         if (!train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: no forward has run (train mode is on: it needs a train-mode lseg_forward)");
-        if (!train_rag_.empty()) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last train-mode forward had ragged label sets");
-        low = train_out_; B = train_B_; kout = train_G_ > 0 ? train_G_ : K_;
+        if (train_head_.ragged()) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last train-mode forward had ragged label sets");
+        low = train_out_; B = train_B_; kout = train_head_.kout;
     } else {
         if (labels_only_) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: the last forward was a labels-only forward (lseg_forward_labels streamed the masks): no low-resolution logits exist");
         if (!last_low_ || last_B_ < 1) return set_error(LSEG_ERR_STATE, "lseg_episode_stats: no forward has run");
@@ -1413,7 +1413,7 @@ int Engine::get_intermediate(const char* name, float* out, size_t cap, size_t* n
         TRY(materialize_low(st));
         const int hw1 = 4 * lh_[0] * lw_[0];
         need_n = (size_t)B * (group_k > 0 ? group_k : K_) * hw1;
-        if (!train_rag_.empty()) need_n = (size_t)K_ * hw1;      // ragged training: the images' planes concatenated, K_ in all
+        if (train_head_.ragged()) need_n = (size_t)K_ * hw1;      // ragged training: the images' planes concatenated, K_ in all
         if (cap < need_n) return set_error(LSEG_ERR_INVALID, "buffer too small: %zu < %zu", cap, need_n);
         LSEG_HIP_TRY(hipMemcpyAsync(out, low_, need_n * sizeof(float), hipMemcpyDeviceToDevice, st));
     } else {

@@ -1,8 +1,10 @@
 // forward_request.hip -- what Engine::forward may be asked for: the request as the plain values of forward_route.h, and every refusal that
 // is decided before a launch, in one order, with its message.  (Two refusals stay in the forward, engine.hip: check_grouping behind
-// the text join, and the uint8 masks with K > 256 behind the planes in memory.)
+// the text join, and the uint8 masks with K > 256 behind the planes in memory.)  The same for the training step: the plan's inputs
+// (train_head.h) and the refusals of forward_train, train_loss and backward.
 #include "engine.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace lseg {
@@ -68,6 +70,46 @@ int Engine::check_ragged_train() {
                                                                       "work on rectangular [B,K,h,w] planes", cfg.arch_option);
     if (resnet_) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode are not implemented for the ResNet-101 tower (decoder training)");
     if (!corr_ragged_supported(cfg.out_c)) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets in train mode need out_c %% 64 == 0 and <= 1024 (is %d)", cfg.out_c);
+    return 0;
+}
+
+// ---- the training step (train.hip): the plan's inputs, and every refusal of forward_train / train_loss / backward before any state changes
+TrainHeadIn Engine::train_head_in(bool logits) const {
+    TrainHeadIn in;
+    in.group_k = group_k; in.ragged = ragged();
+    for (int k : groups_) in.kmax = std::max(in.kmax, (int)k);
+    in.K = K_; in.hb_n = hb_n_; in.arch_option = cfg.arch_option; in.unrounded = cfg.flags & 2; in.img_dt = img_dt_; in.out_c = cfg.out_c;
+    in.logits = logits; in.ragged_gemm = corr_ragged_use_gemm();
+    return in;
+}
+
+int Engine::check_train_forward(int B, const TrainHead& plan) {
+    if (!train_alloc_) return set_error(LSEG_ERR_STATE, "train mode was not enabled (lseg_set_train)");
+    TRY(check_grouping(B));
+    // (per-image label sets with head blocks: check_grouping above reports the grouped kind, check_request the ragged kind through this)
+    if (plan.refusal == TRAIN_REFUSE_HEAD_BLOCKS) return check_ragged_train();
+    // ragged per-image label sets: only the fused loss reads their planes (check_request refused everything else before this point)
+    if (plan.refusal == TRAIN_REFUSE_RAGGED_LOGITS)
+        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits in train mode either: pass no logits output "
+                                               "and take the loss from lseg_train_loss / lseg_backward with a target");
+    if (plan.refusal == TRAIN_REFUSE_GROUP_SIZE)
+        return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
+                         CORR_GROUP_MAX, group_k);
+    return 0;
+}
+
+int Engine::check_train_loss(const int64_t* target) {
+    if (!train_mode || !train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_train_loss needs a train-mode lseg_forward first");
+    if (!target) return set_error(LSEG_ERR_INVALID, "lseg_train_loss: target is NULL");
+    return 0;
+}
+
+int Engine::check_backward(const float* dlogits, const int64_t* target, const float* dev_grad_scale) {
+    if (!train_mode || !train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_backward needs a train-mode lseg_forward first");
+    if (dlogits && dev_grad_scale) return set_error(LSEG_ERR_INVALID, "lseg_backward: a gradient scale only applies to the fused loss (target given)");
+    if (!dlogits && !target) return set_error(LSEG_ERR_INVALID, "lseg_backward: give d(logits) or a target mask");
+    if (train_head_.ragged() && dlogits)
+        return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits: lseg_backward takes a target, not d(logits)");
     return 0;
 }
 

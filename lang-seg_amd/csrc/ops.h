@@ -5,6 +5,8 @@
 
 namespace lseg {
 
+inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }       // a count rounded up to the GEMM's K-step
+
 int launch_attention(const void* q, const void* k, const void* vt, void* out, int B, int H, int ntok,
                      int npad, int dtype, int causal, float scale, hipStream_t stream);
 

@@ -442,8 +442,6 @@ int launch_ragged_ce_bwd_rows(const float* low, const int64_t* target, const flo
 }
 
 // ---- the per-image correlation around the loss kernels, on the generic GEMM (the engine's route and lseg_op_corr_ragged_*) -----------
-static inline size_t rt_up64(size_t v) { return (v + 63) / 64 * 64; }
-
 bool corr_ragged_supported(int C) { return C >= 64 && C % 64 == 0 && C <= 1024; }
 
 // out8 = {GEMM launches of the stage-one forward (B), launches of the stage-one backward (B GEMMs + one L2-norm backward), columns of the
@@ -458,8 +456,8 @@ int corr_ragged_plan(const int32_t* host_counts, int B, int hw, int C, int* out6
     if (const int r = ragged_prefix(host_counts, B, prefix.data(), kmax)) return r;
     if ((double)B * hw * C >= 2.0e9) return set_error(LSEG_ERR_UNSUPPORTED, "corr_ragged_plan: B*hw*C exceeds 2^31");
     size_t cols = 0;
-    for (int b = 0; b < B; ++b) cols += rt_up64(host_counts[b]);
-    out6[0] = B; out6[1] = B + 1; out6[2] = (int)cols; out6[3] = (int)rt_up64(kmax); out6[4] = prefix[B]; out6[5] = B * hw * C;
+    for (int b = 0; b < B; ++b) cols += up64(host_counts[b]);
+    out6[0] = B; out6[1] = B + 1; out6[2] = (int)cols; out6[3] = (int)up64(kmax); out6[4] = prefix[B]; out6[5] = B * hw * C;
     out6[6] = B * ((hw + RT_FWD_ROWS - 1) / RT_FWD_ROWS); out6[7] = B * ((hw + RT_BWD_ROWS - 1) / RT_BWD_ROWS);
     return 0;
 }
@@ -525,11 +523,11 @@ int launch_corr_ragged_fwd(const void* a16, const void* tnorm, float* low, const
 int launch_corr_ragged_panels(const void* tsrc, void* tnT, const int* host_prefix, int B, int C, hipStream_t st) {
     if (!tsrc || !tnT || !host_prefix) return set_error(LSEG_ERR_INVALID, "corr_ragged_panels: NULL pointer");
     size_t cols = 0;
-    for (int b = 0; b < B; ++b) cols += rt_up64(host_prefix[b + 1] - host_prefix[b]);
+    for (int b = 0; b < B; ++b) cols += up64(host_prefix[b + 1] - host_prefix[b]);
     LSEG_HIP_TRY(hipMemsetAsync(tnT, 0, cols * C * 2, st));
     cols = 0;
     for (int b = 0; b < B; ++b) {
-        const int kb = host_prefix[b + 1] - host_prefix[b], Kpb = (int)rt_up64(kb);
+        const int kb = host_prefix[b + 1] - host_prefix[b], Kpb = (int)up64(kb);
         if (const int r = launch_transpose16((const uint16_t*)tsrc + (size_t)host_prefix[b] * C, (uint16_t*)tnT + cols * C, kb, C, C, Kpb, st)) return r;
         cols += Kpb;
     }
@@ -546,7 +544,7 @@ int launch_corr_ragged_bwd(const void* rows, int rows_dtype, int ldk, const void
     if (ldk < 64 || ldk % 64 != 0) return set_error(LSEG_ERR_INVALID, "corr_ragged_bwd: ldk=%d must be a multiple of 64", ldk);
     size_t cols = 0;
     for (int b = 0; b < B; ++b) {
-        const int Kpb = (int)rt_up64(host_prefix[b + 1] - host_prefix[b]);
+        const int Kpb = (int)up64(host_prefix[b + 1] - host_prefix[b]);
         if (Kpb > ldk) return set_error(LSEG_ERR_INVALID, "corr_ragged_bwd: ldk=%d < up64 of image %d's count", ldk, b);
         GemmArgs g;
         gemm_args_init(g);

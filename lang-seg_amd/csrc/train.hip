@@ -41,8 +41,6 @@ namespace lseg {
                                    (size_t)(count) * sizeof(type));                               \
     } while (0)
 
-static inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
-
 int Engine::set_train(bool on) {
     if (on) {
         if (ragged()) TRY(check_ragged_train());
@@ -59,7 +57,7 @@ int Engine::set_train(bool on) {
     }
     train_mode = on;
     train_fwd_valid_ = false;
-    if (!train_rag_.empty()) { train_rag_.clear(); last_low_ = nullptr; }     // the concatenated planes of a ragged forward are no rectangular [B,K,h,w]
+    if (train_head_.ragged()) { train_rag_.clear(); train_head_ = TrainHead{}; last_low_ = nullptr; }     // a ragged forward's planes are no [B,K,h,w]
     return 0;
 }
 
@@ -475,15 +473,8 @@ int Engine::rcu_train(const uint16_t* in, const uint16_t* in_relu, Rcu& U, const
 int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t st) {
     const lseg_config& c = cfg;
     const int D = c.dim, H = c.heads, F = c.features, M = B * ntok_;
-    if (!train_alloc_) return set_error(LSEG_ERR_STATE, "train mode was not enabled (lseg_set_train)");
-    TRY(check_grouping(B));
-    // ragged per-image label sets: only the fused loss reads their planes (check_ragged refused everything else before this point)
-    const bool rag = ragged();
-    if (rag && logits) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits in train mode either: pass no logits output "
-                                                              "and take the loss from lseg_train_loss / lseg_backward with a target");
-    if (group_k > 0 && !corr_group_supported(group_k, c.out_c))
-        return set_error(LSEG_ERR_UNSUPPORTED, "train mode with per-image label sets supports 1..%d labels per image (got %d) and out_c %% 8 == 0",
-                         CORR_GROUP_MAX, group_k);
+    const TrainHead plan = train_head_plan(train_head_in(logits != nullptr));
+    TRY(check_train_forward(B, plan));
     train_fwd_valid_ = false;
     loss_target_ = nullptr;
     last_B_ = B;
@@ -536,44 +527,10 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     g = lin_args(path_[0], head1_, Mp, feat_, DT_F32);
     TRY(launch_gemm(g, img_dt_, st));
     TRY(launch_l2norm_scale_f16(feat_, a16_, Mp, c.out_c, logit_scale(), st));
-    const int kout = group_k > 0 ? group_k : K_;             // label planes per image
-    train_rag_.clear();
-    if (rag) {
-        // image b against its own groups_[b] text rows, on the generic GEMM with the shared path's rounding points (round_mid = 1: one fp16
-        // rounding per logit): the planes are concatenated in low_, image b's at prefix[b] * hw1.  The dgrad operands are per-image
-        // transposed text panels padded to the GEMM's K-step, zero in the pad columns.
-        std::vector<int> prefix((size_t)B + 1, 0);
-        int kmax = 0;
-        TRY(ragged_prefix(groups_.data(), B, prefix.data(), kmax));
-        TRY(launch_ragged_offsets(d_goff_, prefix.data(), B + 1, st));
-        if (corr_ragged_use_gemm()) {                     // stage one (LSEG_CORR_RAGGED_GEMM): per-image GEMMs, transposed panels for the dgrad
-            TRY(launch_corr_ragged_fwd(a16_, tnorm_, low_, prefix.data(), B, hw1, c.out_c, st));
-            const uint16_t* tsrc = tnorm_;
-            if (cfg.flags & 2) {
-                TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
-                tsrc = tn16_;
-            }
-            TRY(launch_corr_ragged_panels(tsrc, tnT_rag_, prefix.data(), B, c.out_c, st));
-        } else {                                          // stage two: one launch, planes bit-equal to stage one; the backward reads tnorm_ itself
-            TRY(launch_corr_ragged_fwd_fused(a16_, tnorm_, low_, d_goff_, B, hw1, c.out_c, st));
-        }
-        train_rag_ = prefix;
-        train_rag_kmax_ = kmax;
-    } else if (group_k > 0) {
-        // per-image correlation (corr_group.hip): the same rounding points as the GEMM below; the grouped backward reads tnorm_ itself,
-        // so there is no transposed dgrad operand to make
-        TRY(launch_corr_group_fwd(a16_, tnorm_, low_, B, hw1, group_k, c.out_c, st));
-    } else {
-        TRY(correlate_planes(tnorm_, a16_, K_, Mp, hw1, low_, 1, st));
-        // the text features as the dgrad operand of the correlation: bf16, transposed, K padded to the GEMM's K-step
-        const int Kp = (int)up64(K_);
-        if (cfg.flags & 2) {
-            TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
-            TRY(launch_transpose16(tn16_, tnT_, K_, c.out_c, c.out_c, Kp, st));
-        } else {
-            TRY(launch_transpose16(tnorm_, tnT_, K_, c.out_c, c.out_c, Kp, st));      // fp16 as it is: the reference's dgrad is a half x half product
-        }
-    }
+    train_rag_.clear(); train_head_ = TrainHead{};       // no plan holds until the correlation has run
+    TRY(train_correlate(plan, B, st));
+    train_head_ = plan;
+    const int kout = plan.kout;
     // arch_option 1/2 head blocks (lseg_net.py:198-201) with every block's output and the bottleneck's arg-max labels kept
     const float* out = low_;
     for (int j = 0; j < hb_n_; ++j) {
@@ -586,9 +543,56 @@ int Engine::forward_train(const float* x_in, int B, float* logits, hipStream_t s
     if (logits) TRY(launch_upsample2x_planes(out, logits, B * kout, h1, w1, st));
     last_low_ = out; last_kout_ = kout;
     train_out_ = out;
-    train_B_ = B; train_G_ = group_k;
+    train_B_ = B;
     train_fwd_valid_ = true;
     TRY(zero_end(zero_fwd_));
+    return 0;
+}
+
+// the correlation of the train-mode forward, a16_ [B*hw1, out_c] against the text rows -> low_, and its backward's dgrad operand if any
+int Engine::train_correlate(const TrainHead& plan, int B, hipStream_t st) {
+    const lseg_config& c = cfg;
+    const int hw1 = 4 * lh_[0] * lw_[0], Mp = B * hw1;
+    switch (plan.mode) {
+    case TRAIN_RAGGED_GEMM: case TRAIN_RAGGED_FUSED: {
+        // image b against its own groups_[b] text rows, on the generic GEMM with the shared path's rounding points (round_mid = 1: one fp16
+        // rounding per logit): the planes are concatenated in low_, image b's at prefix[b] * hw1.  The dgrad operands are per-image
+        // transposed text panels padded to the GEMM's K-step, zero in the pad columns.
+        std::vector<int> prefix((size_t)B + 1, 0);
+        int kmax = 0;
+        TRY(ragged_prefix(groups_.data(), B, prefix.data(), kmax));
+        if (kmax != plan.kmax) return set_error(LSEG_ERR_STATE, "ragged label sets: the plan's longest list %d != %d over the %d images", plan.kmax, kmax, B);
+        TRY(launch_ragged_offsets(d_goff_, prefix.data(), B + 1, st));
+        if (plan.mode == TRAIN_RAGGED_GEMM) {             // stage one (LSEG_CORR_RAGGED_GEMM): per-image GEMMs, transposed panels for the dgrad
+            TRY(launch_corr_ragged_fwd(a16_, tnorm_, low_, prefix.data(), B, hw1, c.out_c, st));
+            const uint16_t* tsrc = tnorm_;
+            if (plan.hdt != DT_F16) {
+                TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
+                tsrc = tn16_;
+            }
+            TRY(launch_corr_ragged_panels(tsrc, tnT_rag_, prefix.data(), B, c.out_c, st));
+        } else {                                          // stage two: one launch, planes bit-equal to stage one; the backward reads tnorm_ itself
+            TRY(launch_corr_ragged_fwd_fused(a16_, tnorm_, low_, d_goff_, B, hw1, c.out_c, st));
+        }
+        train_rag_ = prefix;
+        break;
+    }
+    case TRAIN_GROUPED:
+        // per-image correlation (corr_group.hip): the same rounding points as the GEMM below; the grouped backward reads tnorm_ itself,
+        // so there is no transposed dgrad operand to make
+        TRY(launch_corr_group_fwd(a16_, tnorm_, low_, B, hw1, plan.kout, c.out_c, st));
+        break;
+    case TRAIN_SHARED:
+        TRY(correlate_planes(tnorm_, a16_, K_, Mp, hw1, low_, 1, st));
+        // the text features as the dgrad operand of the correlation: bf16, transposed, K padded to the GEMM's K-step
+        if (plan.hdt != DT_F16) {
+            TRY(launch_convert(tnorm_, DT_F16, tn16_, DT_BF16, (size_t)K_ * c.out_c, st));
+            TRY(launch_transpose16(tn16_, tnT_, K_, c.out_c, c.out_c, plan.Kp, st));
+        } else {
+            TRY(launch_transpose16(tnorm_, tnT_, K_, c.out_c, c.out_c, plan.Kp, st));      // fp16 as it is: the reference's dgrad is a half x half product
+        }
+        break;
+    }
     return 0;
 }
 
@@ -870,47 +874,67 @@ int Engine::block_backward(int i, int B, int acc, hipStream_t st) {
     return 0;
 }
 
-// lseg_backward: gradients of mean CE(ignore_index) (target given) or of <dlogits, logits> (dlogits given) w.r.t. every
-// pretrained.* / scratch.* parameter the forward touched
+// one pass for the loss pieces nll_, the counts and the per-pixel log-sum-exp -- unless lseg_train_loss left them for this forward and target
+int Engine::ensure_loss(const int64_t* target, int ignore_index, hipStream_t st, bool force) {
+    if (!force && loss_target_ == target && loss_ignore_ == ignore_index) return 0;
+    const int B = train_B_, h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
+    if (train_head_.ragged()) return launch_ragged_ce_fwd(low_, target, d_goff_, B, h1, w1, ignore_index, counts_, nll_, lse_px_, st);
+    return launch_seg_stats_ex(train_out_, target, B, train_head_.kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_);
+}
+
+int Engine::publish_loss(double* dev_loss2, int64_t* dev_counts2, hipStream_t st) {
+    if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (dev_counts2) LSEG_HIP_TRY(hipMemcpyAsync(dev_counts2, counts_, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
 // The value of the criterion on the last train-mode forward (lsegmentation_module.py:72), without the backward: mean CE pieces
 // {sum of -log p[target], valid pixels} and, optionally, the pixel-accuracy counts {correct, labeled} (train_accuracy, :77-79).
 // The per-pixel log-sum-exp it leaves behind is reused by a following lseg_backward on the same target.
 int Engine::train_loss(const int64_t* target, int ignore_index, double* dev_loss2, int64_t* dev_counts2, hipStream_t st) {
-    if (!train_mode || !train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_train_loss needs a train-mode lseg_forward first");
-    if (!target) return set_error(LSEG_ERR_INVALID, "lseg_train_loss: target is NULL");
+    TRY(check_train_loss(target));
     LSEG_HIP_TRY(hipSetDevice(device));
-    const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
-    const int kout = train_G_ > 0 ? train_G_ : K_;
-    if (!train_rag_.empty()) TRY(launch_ragged_ce_fwd(low_, target, d_goff_, train_B_, h1, w1, ignore_index, counts_, nll_, lse_px_, st));
-    else TRY(launch_seg_stats_ex(train_out_, target, train_B_, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
-    if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (dev_counts2) LSEG_HIP_TRY(hipMemcpyAsync(dev_counts2, counts_, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    TRY(ensure_loss(target, ignore_index, st, true));       // the pass always runs here: only a following backward reuses it
+    TRY(publish_loss(dev_loss2, dev_counts2, st));
     loss_target_ = target; loss_ignore_ = ignore_index;
     return 0;
 }
 
-// arch_option 1/2 head blocks (head_train.hip): the loss gradient as fp32 planes d(out) (fused CE or the d(logits) hand-over), then the
-// blocks from the last to the first; block 0 writes d(correlation output) as the fp16 (flags bit 1: bf16) rows the correlation backward
-// reads -- the `.float()` of lseg_net.py:196 under autograd.  The shared weight / bias gradients sum over the n blocks.
-int Engine::head_blocks_backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
-                                 const float* dev_grad_scale, int hdt, int Kp) {
-    const lseg_config& c = cfg;
-    const int B = train_B_, K = K_, h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1;
-    const int bott = c.arch_option == 1;
-    float* gbuf[2] = {low2_, low3_};          // the inference path's head-block temporaries serve as gradient planes
-    float* dW = grad("scratch.head_block.depthwise.depthwise.weight", 9);
-    float* db = grad("scratch.head_block.depthwise.depthwise.bias", 1);
-    if (!dW || !db) return LSEG_ERR_INVALID;
-    if (!dlogits) {
-        if (!(loss_target_ == target && loss_ignore_ == ignore_index))
-            TRY(launch_seg_stats_ex(train_out_, target, B, K, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
-        TRY(launch_upsample_ce_backward_planes(train_out_, target, lse_px_, nll_, gbuf[0], bott ? hb_ks_[0] : nullptr, B, K, h1, w1, ignore_index,
+// loss + x2 upsample^T: the correlation's dY rows drows_ [B*hw1, Kp] (head blocks: fp32 planes in low2_), from the fused CE or d(logits).
+// The reference back-propagates through `logit_scale * image_features.half() @ text_features.t()` (lseg_net.py:194) in HALF precision:
+// d(logits) is cast to fp16 (the `.float()` of :196 under autograd), dA = d(logits) @ text_features is an fp16 tensor (fp32
+// accumulation), and so is logit_scale * dA.  With d(logits) ~ 1 / (valid pixels) these values live in fp16's SUBNORMAL range (step
+// 2^-24 = 6e-8): a softmax probability below ~3e-8 * N contributes nothing.  The rows, the GEMM and the scale reproduce exactly
+// that (fp16 rows, fp16 x fp16 MFMA with fp32 accumulation, fp16 output, fp16 rounding of the scaled value) unless flags bit 1 asks
+// for the un-rounded gradient (plan.hdt).
+int Engine::loss_rows(const TrainHead& plan, const float* dlogits, const int64_t* target, int ignore_index, double* dev_loss2,
+                      const float* dev_grad_scale, hipStream_t st) {
+    const int B = train_B_, kout = plan.kout, Kp = plan.Kp, h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, bott = cfg.arch_option == 1;
+    if (!dlogits) TRY(ensure_loss(target, ignore_index, st));
+    if (plan.ragged())        // each image over its own planes; one row pitch for the batch, columns past the image's count written as zeros
+        TRY(launch_ragged_ce_bwd_rows(low_, target, lse_px_, nll_, drows_, d_goff_, B, h1, w1, Kp, ignore_index, plan.hdt, st, dev_grad_scale));
+    else if (plan.head_blocks && !dlogits)      // arch_option 1/2: fp32 planes d(out) in low2_ for head_blocks_backward
+        TRY(launch_upsample_ce_backward_planes(train_out_, target, lse_px_, nll_, low2_, bott ? hb_ks_[0] : nullptr, B, kout, h1, w1, ignore_index,
                                                st, dev_grad_scale));
-        if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else {
-        TRY(launch_upsample2x_planes_backward_planes(dlogits, gbuf[0], B, K, h1, w1, st));
-        if (bott) TRY(launch_head_bwd_prep(gbuf[0], nullptr, nullptr, nullptr, hb_ks_[0], nullptr, B, K, hw1, c.activation, 0, st));
+    else if (plan.head_blocks) {
+        TRY(launch_upsample2x_planes_backward_planes(dlogits, low2_, B, kout, h1, w1, st));
+        if (bott) TRY(launch_head_bwd_prep(low2_, nullptr, nullptr, nullptr, hb_ks_[0], nullptr, B, kout, hw1, cfg.activation, 0, st));
+    } else if (!dlogits)      // CrossEntropyLoss(ignore_index) on output_conv(low): the rows from the loss pass's log-sum-exp
+        TRY(launch_upsample_ce_backward_rows(low_, target, lse_px_, nll_, drows_, B, kout, h1, w1, Kp, ignore_index, plan.hdt, st, dev_grad_scale));
+    else {                    // autograd hand-over: d(logits) [B,K,2h,2w] given
+        LSEG_HIP_TRY(hipMemsetAsync(drows_, 0, (size_t)B * hw1 * Kp * 2, st));
+        TRY(launch_upsample2x_planes_backward_rows(dlogits, drows_, B, kout, h1, w1, Kp, plan.hdt, st));
     }
+    return dlogits ? 0 : publish_loss(dev_loss2, nullptr, st);
+}
+
+// arch_option 1/2 head blocks (head_train.hip) from the last to the first, on the gradient planes loss_rows left in low2_; block 0 writes
+// d(correlation output) as the rows the correlation backward reads.  The shared weight / bias gradients sum over the n blocks.
+int Engine::head_blocks_backward(const TrainHead& plan, int acc, hipStream_t st) {
+    const int B = train_B_, K = plan.kout, h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, bott = cfg.arch_option == 1;
+    float* gbuf[2] = {low2_, low3_};          // the inference path's head-block temporaries serve as gradient planes
+    float *dW = grad("scratch.head_block.depthwise.depthwise.weight", 9), *db = grad("scratch.head_block.depthwise.depthwise.bias", 1);
+    if (!dW || !db) return LSEG_ERR_INVALID;
     const size_t rows = head_block_bwd_partials(B, h1, w1);
     int cur = 0;
     for (int j = hb_n_ - 1; j >= 0; --j) {
@@ -918,116 +942,94 @@ int Engine::head_blocks_backward(const float* dlogits, const int64_t* target, in
         const int* ks = bott ? hb_kstar_ + (size_t)j * B * hw1 : nullptr;
         float* part = hb_part_ + (size_t)j * rows * 10;
         if (j > 0)
-            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, gbuf[cur ^ 1], DT_F32, 0, c.activation,
+            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, gbuf[cur ^ 1], DT_F32, 0, cfg.activation,
                                            bott ? hb_ks_[cur ^ 1] : nullptr, part, B, K, h1, w1, bott, st));
         else
-            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, drows_, hdt, Kp, -1, nullptr, part, B, K, h1, w1,
-                                           bott, st));
+            TRY(launch_head_block_backward(gbuf[cur], bott ? hb_ks_[cur] : nullptr, ks, x, hb_w_, drows_, plan.hdt, plan.Kp, -1, nullptr, part, B, K, h1,
+                                           w1, bott, st));
         cur ^= 1;
     }
     return launch_head_dw_reduce(hb_part_, (int)(rows * hb_n_), dW, db, acc, st);
 }
 
-int Engine::backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
-                     const float* dev_grad_scale) {
-    if (!train_mode || !train_fwd_valid_) return set_error(LSEG_ERR_STATE, "lseg_backward needs a train-mode lseg_forward first");
-    if (dlogits && dev_grad_scale) return set_error(LSEG_ERR_INVALID, "lseg_backward: a gradient scale only applies to the fused loss (target given)");
-    if (!dlogits && !target) return set_error(LSEG_ERR_INVALID, "lseg_backward: give d(logits) or a target mask");
-    LSEG_HIP_TRY(hipSetDevice(device));
-    const lseg_config& c = cfg;
-    const int B = train_B_, D = c.dim, F = c.features, M = B * ntok_, Mr = B * np_;
-    const int h1 = 2 * lh_[0], w1 = 2 * lw_[0], hw1 = h1 * w1, Mp1 = B * hw1;
-    // label planes per image and the row pitch of d(low): per-image sets (G <= 8) hand the grouped kernel one 16-byte row per pixel
-    const bool rag = !train_rag_.empty();
-    if (rag && dlogits) return set_error(LSEG_ERR_UNSUPPORTED, "ragged label sets have no [B,K,H,W] logits: lseg_backward takes a target, not d(logits)");
-    const int G = train_G_, kout = G > 0 ? G : K_, Kp = rag ? (int)up64(train_rag_kmax_) : G > 0 ? 8 : (int)up64(K_);
-    if (!acc) TRY(zero_begin(zero_bwd_, st));
-    // The reference back-propagates through `logit_scale * image_features.half() @ text_features.t()` (lseg_net.py:194) in HALF precision:
-    // d(logits) is cast to fp16 (the `.float()` of :196 under autograd), dA = d(logits) @ text_features is an fp16 tensor (fp32
-    // accumulation), and so is logit_scale * dA.  With d(logits) ~ 1 / (valid pixels) these values live in fp16's SUBNORMAL range (step
-    // 2^-24 = 6e-8): a softmax probability below ~3e-8 * N contributes nothing.  The rows, the GEMM and the scale below reproduce exactly
-    // that (fp16 rows, fp16 x fp16 MFMA with fp32 accumulation, fp16 output, fp16 rounding of the scaled value) unless flags bit 1 asks
-    // for the un-rounded gradient.
-    const int hdt = (cfg.flags & 2) ? img_dt_ : DT_F16;
-    // ---- loss + x2 upsample^T: the correlation's dY rows ---------------------------------------------------------------------
-    if (rag) {                // each image over its own planes; one row pitch for the batch, columns past the image's count written as zeros
-        if (!(loss_target_ == target && loss_ignore_ == ignore_index))
-            TRY(launch_ragged_ce_fwd(low_, target, d_goff_, B, h1, w1, ignore_index, counts_, nll_, lse_px_, st));
-        TRY(launch_ragged_ce_bwd_rows(low_, target, lse_px_, nll_, drows_, d_goff_, B, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
-        if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else if (hb_n_ > 0) TRY(head_blocks_backward(dlogits, target, ignore_index, acc, dev_loss2, st, dev_grad_scale, hdt, Kp));
-    else if (!dlogits) {      // CrossEntropyLoss(ignore_index) on output_conv(low): one pass for the loss and the per-pixel log-sum-exp, one for the rows
-        if (!(loss_target_ == target && loss_ignore_ == ignore_index))      // else: lseg_train_loss left nll_ / lse_px_ of this forward and target
-            TRY(launch_seg_stats_ex(train_out_, target, B, kout, 4 * hw1, ignore_index, counts_, nll_, nullptr, 1, h1, w1, st, lse_px_));
-        TRY(launch_upsample_ce_backward_rows(low_, target, lse_px_, nll_, drows_, B, kout, h1, w1, Kp, ignore_index, hdt, st, dev_grad_scale));
-        if (dev_loss2) LSEG_HIP_TRY(hipMemcpyAsync(dev_loss2, nll_, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else {             // autograd hand-over: d(logits) [B,K,2h,2w] given
-        LSEG_HIP_TRY(hipMemsetAsync(drows_, 0, (size_t)Mp1 * Kp * 2, st));
-        TRY(launch_upsample2x_planes_backward_rows(dlogits, drows_, B, kout, h1, w1, Kp, hdt, st));
-    }
-    // ---- head: correlation, L2-norm, head1 -------------------------------------------------------------------------------------
-    if (rag) {
-        // dA_b = d(logits)_b . T_b per image on its transposed text panel (K = up64(k_b): the columns beyond are zeros and are not read),
-        // then the scale and L2-norm backward over all rows at once
-        if (corr_ragged_use_gemm())
-            TRY(launch_corr_ragged_bwd(drows_, hdt, Kp, tnT_rag_, zeros_, feat_, da_, df_, img_dt_, train_rag_.data(), B, hw1, c.out_c, logit_scale(), st));
-        else
-            TRY(launch_corr_ragged_bwd_fused(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, d_goff_, train_rag_kmax_, B, hw1, c.out_c, logit_scale(), st));
-    } else if (G > 0) {
+// correlation, scale and L2-norm backward: drows_ -> df_ = d(head1 output)
+int Engine::train_correlate_backward(const TrainHead& plan, hipStream_t st) {
+    const int B = train_B_, Kp = plan.Kp, hdt = plan.hdt, hw1 = 4 * lh_[0] * lw_[0], Mp1 = B * hw1, C = cfg.out_c;
+    switch (plan.mode) {
+    // dA_b = d(logits)_b . T_b per image (GEMM: on its transposed panel, K = up64(k_b), the columns beyond are zeros), scale and L2-norm backward
+    case TRAIN_RAGGED_GEMM:
+        return launch_corr_ragged_bwd(drows_, hdt, Kp, tnT_rag_, zeros_, feat_, da_, df_, img_dt_, train_rag_.data(), B, hw1, C, logit_scale(), st);
+    case TRAIN_RAGGED_FUSED:
+        return launch_corr_ragged_bwd_fused(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, d_goff_, plan.kmax, B, hw1, C, logit_scale(), st);
+    case TRAIN_GROUPED:
         // per-image label sets: dA from the image's own G text rows, the scale and the L2-norm backward in one pass (corr_group.hip)
-        TRY(launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, G, c.out_c, logit_scale(), st));
-    } else {
-        const Lin tT{tnT_, zeros_, c.out_c, Kp};                      // dA = d(logits) . T on the transposed text features, bias of zeros
+        return launch_corr_group_bwd(drows_, hdt, Kp, tnorm_, feat_, df_, img_dt_, B, hw1, plan.kout, C, logit_scale(), st);
+    case TRAIN_SHARED: {
+        const Lin tT{tnT_, zeros_, C, Kp};                      // dA = d(logits) . T on the transposed text features, bias of zeros
         GemmArgs g = lin_args(drows_, tT, Mp1, da_, hdt);
         TRY(launch_gemm(g, hdt, st));
-        TRY(launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, c.out_c, logit_scale(), st));
+        return launch_l2norm_scale_backward(da_, hdt, feat_, df_, img_dt_, Mp1, C, logit_scale(), st);
     }
+    }
+    return 0;
+}
+
+// lseg_backward: gradients of mean CE(ignore_index) (target given) or of <dlogits, logits> (dlogits given) w.r.t. every
+// pretrained.* / scratch.* parameter the forward touched
+int Engine::backward(const float* dlogits, const int64_t* target, int ignore_index, int acc, double* dev_loss2, hipStream_t st,
+                     const float* dev_grad_scale) {
+    TRY(check_backward(dlogits, target, dev_grad_scale));
+    LSEG_HIP_TRY(hipSetDevice(device));
+    const lseg_config& c = cfg;
+    const TrainHead& plan = train_head_;
+    const int B = train_B_, D = c.dim, F = c.features, M = B * ntok_, Mr = B * np_, Mp1 = B * 4 * lh_[0] * lw_[0];
+    if (!acc) TRY(zero_begin(zero_bwd_, st));
+    // ---- loss + x2 upsample^T, then the head: correlation, L2-norm, head1 --------------------------------------------------------
+    TRY(loss_rows(plan, dlogits, target, ignore_index, dev_loss2, dev_grad_scale, st));
+    if (plan.head_blocks) TRY(head_blocks_backward(plan, acc, st));
+    TRY(train_correlate_backward(plan, st));
     TRY(lin_bwd(df_, Mp1, c.out_c, F, path_[0], head1_.wt, dpath0_, grad("scratch.head1.weight", (size_t)c.out_c * F),
                 grad("scratch.head1.bias", c.out_c), acc, st));
-    // ---- refinenet1..4, reassemble -------------------------------------------------------------------------------------------
+    // ---- refinenet1..4, then the encoder's tail ----------------------------------------------------------------------------------
     for (int r = 1; r <= 4; ++r) TRY(refine_backward(r, B, acc, st));
     if (resnet_) {            // the backward stops at the four tower outputs: scratch.* is the whole trainable set, one bucket
         bucket_done(0, st);
-        if (!acc) TRY(zero_end(zero_bwd_));
-        return 0;
-    }
-    for (int l = 0; l < 4; ++l) TRY(reassemble_backward(l, B, acc, st));
-    bucket_done(0, st);
-    if (frozen_) {
-        // ---- frozen encoder: the four readouts' own gradients, every bucket announced once in the usual order, nothing else ----------
-        for (int i = c.depth - 1; i >= 0; --i) {
-            for (int l = 0; l < 4; ++l)
-                if (c.hooks[l] == i) TRY(readout_backward(l, B, acc, st));
-            bucket_done(1 + (c.depth - 1 - i), st);
+    } else {
+        for (int l = 0; l < 4; ++l) TRY(reassemble_backward(l, B, acc, st));
+        bucket_done(0, st);
+        if (frozen_) {        // the four readouts' own gradients, every bucket announced once in the usual order, nothing else
+            for (int i = c.depth - 1; i >= 0; --i) {
+                for (int l = 0; l < 4; ++l)
+                    if (c.hooks[l] == i) TRY(readout_backward(l, B, acc, st));
+                bucket_done(1 + (c.depth - 1 - i), st);
+            }
+        } else {              // ViT blocks, readouts joining at their hooks
+            LSEG_HIP_TRY(hipMemsetAsync(gx_, 0, (size_t)M * D * sizeof(float), st));
+            g16_valid_ = false;
+            for (int i = c.depth - 1; i >= 0; --i) {
+                for (int l = 0; l < 4; ++l)
+                    if (c.hooks[l] == i) TRY(readout_backward(l, B, acc, st));
+                TRY(block_backward(i, B, acc, st));
+                if (i > 0) bucket_done(1 + (c.depth - 1 - i), st);
+            }
+            // embedding: patch_embed wgrad, cls_token, pos_embed (through the bilinear resize)
+            const std::string vm = "pretrained.model.";
+            const int PK = 3 * c.patch * c.patch;
+            TRY(launch_embed_bwd(gx_, dtok_, dpos_, B, ntok_, D, img_dt_, st));
+            TRY(lin_bwd(dtok_, Mr, D, PK, patchA_, nullptr, nullptr, grad(vm + "patch_embed.proj.weight", (size_t)D * PK),
+                        grad(vm + "patch_embed.proj.bias", D), acc, st));
+            const size_t npos = (size_t)(1 + c.pos_grid * c.pos_grid) * D;
+            float* gpos = grad(vm + "pos_embed", npos);
+            float* gcls = grad(vm + "cls_token", D);
+            if (!gpos || !gcls) return LSEG_ERR_INVALID;
+            if (!acc) {
+                LSEG_HIP_TRY(hipMemsetAsync(gpos, 0, npos * sizeof(float), st));
+                LSEG_HIP_TRY(hipMemsetAsync(gcls, 0, D * sizeof(float), st));
+            }
+            TRY(launch_pos_resize_bwd(dpos_, gpos, gcls, c.pos_grid, gh_, gw_, D, st));
+            bucket_done(c.depth, st);
         }
-        if (!acc) TRY(zero_end(zero_bwd_));
-        return 0;
     }
-    // ---- ViT blocks, readouts joining at their hooks --------------------------------------------------------------------------
-    LSEG_HIP_TRY(hipMemsetAsync(gx_, 0, (size_t)M * D * sizeof(float), st));
-    g16_valid_ = false;
-    for (int i = c.depth - 1; i >= 0; --i) {
-        for (int l = 0; l < 4; ++l)
-            if (c.hooks[l] == i) TRY(readout_backward(l, B, acc, st));
-        TRY(block_backward(i, B, acc, st));
-        if (i > 0) bucket_done(1 + (c.depth - 1 - i), st);
-    }
-    // ---- embedding: patch_embed wgrad, cls_token, pos_embed (through the bilinear resize) ---------------------------------------
-    const std::string vm = "pretrained.model.";
-    const int PK = 3 * c.patch * c.patch;
-    TRY(launch_embed_bwd(gx_, dtok_, dpos_, B, ntok_, D, img_dt_, st));
-    TRY(lin_bwd(dtok_, Mr, D, PK, patchA_, nullptr, nullptr, grad(vm + "patch_embed.proj.weight", (size_t)D * PK),
-                grad(vm + "patch_embed.proj.bias", D), acc, st));
-    const size_t npos = (size_t)(1 + c.pos_grid * c.pos_grid) * D;
-    float* gpos = grad(vm + "pos_embed", npos);
-    float* gcls = grad(vm + "cls_token", D);
-    if (!gpos || !gcls) return LSEG_ERR_INVALID;
-    if (!acc) {
-        LSEG_HIP_TRY(hipMemsetAsync(gpos, 0, npos * sizeof(float), st));
-        LSEG_HIP_TRY(hipMemsetAsync(gcls, 0, D * sizeof(float), st));
-    }
-    TRY(launch_pos_resize_bwd(dpos_, gpos, gcls, c.pos_grid, gh_, gw_, D, st));
-    bucket_done(c.depth, st);
     if (!acc) TRY(zero_end(zero_bwd_));
     return 0;
 }

@@ -167,6 +167,7 @@ SIGNATURES = {
     "lseg_op_episode_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lseg_op_label_stats_plan": (_i, [_i, _vp]),
     "lseg_op_forward_route": (_i, [_vp, _i, _vp]),
+    "lseg_op_train_head_plan": (_i, [_vp, _i, _vp]),
     "lseg_op_label_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "lseg_op_stats_fold_lowres": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "lseg_op_stats_finish_ws_bytes": (_sz, [_i, _i, _i]),

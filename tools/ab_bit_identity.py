@@ -1,7 +1,9 @@
 """Bit identity of two builds of liblseg_hip.so: sha256 of every output tensor of a fixed list of small cases that together reach each
 GEMM descriptor and stage the forwards, the text tower and the backward share (csrc/engine.h builders, Engine::patch_embed /
-reassemble / out_conv / correlate_planes) and every output tail of Engine::forward (csrc/forward_route.h).  A host-side restructuring
-of the schedule must leave every line unchanged.
+reassemble / out_conv / correlate_planes), every output tail of Engine::forward (csrc/forward_route.h) and every mode and stage of the
+training step's label head (csrc/train_head.h) with the three encoder tails of the backward.  A host-side restructuring of the schedule
+must leave every line unchanged.  (The loss VALUES are double atomic sums, whose last bits may depend on the order the workgroups arrive
+in: run the older library twice and leave out the lines that differ between its own runs -- profiles/train_refactor.txt: none did.)
 
     python tools/ab_bit_identity.py --lib OLD/liblseg_hip.so --out old.txt
     python tools/ab_bit_identity.py --out new.txt          # the in-tree build
@@ -25,20 +27,20 @@ LABELS = ["wall", "sky", "tree", "floor", "other", "road", "grass"]
 def emit(case, name, t):
     import torch
     t = t.detach().contiguous().cpu()
-    raw = t.view(torch.uint8).numpy().tobytes() if t.numel() else b""
+    raw = t.reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b""
     print(f"{case} {name} {str(t.dtype).replace('torch.', '')}{list(t.shape)} {hashlib.sha256(raw).hexdigest()}", flush=True)
 
 
-def engine(backbone, S, B, K, dtype, group=0, **kw):
+def engine(backbone, S, B, K, dtype, group=0, width=None, **kw):
     from lseg_hip.config import get_config
     from lseg_hip.engine import HipEngine
     from lseg_hip.synth import synthetic_state_dict, synthetic_tokens, synthetic_images
     cfg = get_config(backbone, arch_option=kw.pop("arch_option", 0), block_depth=kw.pop("block_depth", 0))
     sd = {k: v.cuda() for k, v in synthetic_state_dict(cfg, seed=7).items()}
-    eng = HipEngine(cfg, S, S, max_batch=B, max_labels=K, image_dtype=dtype, deterministic=True, **kw)
+    eng = HipEngine(cfg, S, width or S, max_batch=B, max_labels=K, image_dtype=dtype, deterministic=True, **kw)
     eng.load_state_dict(sd)
     eng.set_tokens(synthetic_tokens([LABELS[i % len(LABELS)] for i in range(K)], cfg.text.vocab, cfg.text.ctx), labels_per_image=group)
-    return eng, sd, synthetic_images(B, S, S, seed=7).cuda()
+    return eng, sd, synthetic_images(B, S, width or S, seed=7).cuda()
 
 
 def run_eval(case, backbone, S, B, K, dtypes, group=0, debug=False, text_features=False, **kw):
@@ -68,13 +70,69 @@ def run_train(case, backbone, S, B, K, group=0, freeze=False, **kw):
     eng, sd, x = engine(backbone, S, B, K, "bf16", group, **kw)
     eng.enable_training(sd, freeze_encoder=freeze)
     kout = group if group else K
-    target = torch.randint(0, kout, (B, S, S), generator=torch.Generator().manual_seed(11)).cuda()
+    target = torch.randint(0, kout, (B, S, kw.get("width") or S), generator=torch.Generator().manual_seed(11)).cuda()
     emit(case, "logits", eng.forward(x))
     eng.backward(target=target, ignore_index=-100)
     torch.cuda.synchronize()
     emit(case, "loss_pair", eng._loss)
     for k in sorted(eng.grads):
         emit(case, f"grad.{k}", eng.grads[k])
+    eng.close()
+
+
+def emit_step(case, eng, name="", loss=True):
+    import torch
+    torch.cuda.synchronize()
+    if loss:
+        emit(case, f"{name}loss_pair", eng._loss)
+    for k in sorted(eng.grads):
+        emit(case, f"{name}grad.{k}", eng.grads[k])
+
+
+def run_train_paths(case, path, backbone="tiny16", S=64, B=2, K=5, group=0, ragged=None, **kw):
+    """the paths of the training step run_train does not reach: per-image label lists, the d(logits) hand-over, lseg_train_loss before
+    the backward (same target: its pass is reused; another target: it is not), accumulation, the scaled fused loss"""
+    import torch
+    eng, sd, x = engine(backbone, S, B, K, "bf16", group, **kw)
+    eng.enable_training(sd)
+    W = kw.get("width") or S
+    kout = group if group else K
+    gen = torch.Generator().manual_seed(11)
+    if ragged:
+        eng.set_tokens(eng_tokens(eng, K), group_sizes=ragged)
+        target = torch.stack([torch.randint(-1, k, (S, W), generator=torch.Generator().manual_seed(13 + b)) for b, k in enumerate(ragged)]).cuda()
+    else:
+        target = torch.randint(-1, kout, (B, S, W), generator=gen).cuda()
+    if path == "ragged":
+        eng.forward(x, want_logits=False)
+        emit(case, "train_loss", eng.train_loss(target))
+        eng.backward(target=target)
+        emit_step(case, eng)
+    elif path == "handover":
+        logits = eng.forward(x)
+        emit(case, "logits", logits)
+        eng.backward(dlogits=torch.randn(logits.shape, generator=gen).cuda() * 1e-4)
+        emit_step(case, eng, loss=False)
+    elif path == "loss_reuse":
+        other = torch.randint(-1, kout, (B, S, W), generator=gen).cuda()
+        for name, second in (("same.", target), ("other.", other)):
+            emit(case, f"{name}logits", eng.forward(x))
+            loss, counts = eng.train_loss(target, want_counts=True)
+            emit(case, f"{name}train_loss", loss)
+            emit(case, f"{name}train_counts", counts)
+            eng.backward(target=second)
+            emit_step(case, eng, name)
+    elif path == "accumulate":
+        for name, acc in (("first.", False), ("second.", True)):
+            emit(case, f"{name}logits", eng.forward(x))
+            eng.backward(target=target, accumulate=acc)
+            emit_step(case, eng, name)
+    elif path == "grad_scale":
+        emit(case, "logits", eng.forward(x))
+        eng.backward(target=target, grad_scale=torch.tensor(0.5, device="cuda"))
+        emit_step(case, eng, loss=False)
+    else:
+        raise ValueError(path)
     eng.close()
 
 
@@ -170,7 +228,22 @@ CASES = {
     "vitl16_k160": lambda c: run_routes(c, "clip_vitl16_384", 96, 1, 160, want=("logits", "lowres", "labels")),     # past corr_planes' LDS
     "vitl16_k300": lambda c: run_routes(c, "clip_vitl16_384", 96, 1, 300, want=("labels", "masks")),               # past uint8
 }
-CHILD_ENV = {"tiny16_corr_generic": {"LSEG_CORR_GENERIC": "1"}, "tiny16_no_upsample4x": {"LSEG_NO_UPSAMPLE4X": "1"},
+CASES.update({
+    # ---- the training step's label head (csrc/train_head.h) and the exits of the backward beyond run_train's.  tiny16: out_c 128
+    "tiny16_train_ragged": lambda c: run_train_paths(c, "ragged", ragged=[2, 3]),
+    "tiny16_train_ragged_gemm": lambda c: run_train_paths(c, "ragged", ragged=[2, 3]),         # the parent sets LSEG_CORR_RAGGED_GEMM=1
+    "tiny16_train_handover": lambda c: run_train_paths(c, "handover"),
+    "tiny16_train_loss_reuse": lambda c: run_train_paths(c, "loss_reuse"),
+    "tiny16_train_accumulate": lambda c: run_train_paths(c, "accumulate"),
+    "tiny16_train_grad_scale": lambda c: run_train_paths(c, "grad_scale"),
+    "tiny16_train_arch2": lambda c: run_train(c, "tiny16", 64, 2, 5, arch_option=2, block_depth=2, head_block_training=True),
+    "tiny16_train_unrounded": lambda c: run_train(c, "tiny16", 64, 2, 5, exact_head_grad=True),
+    "tiny16_train_grouped_handover": lambda c: run_train_paths(c, "handover", K=6, group=3),
+    # the decoder above the ResNet-101 tower (flags bit 6): the backward stops at the tower outputs
+    "rn101_train_decoder": lambda c: run_train(c, "clip_resnet101", 64, 2, 4, group=2, width=96, train_resnet_decoder=True),
+})
+CHILD_ENV = {"tiny16_train_ragged_gemm": {"LSEG_CORR_RAGGED_GEMM": "1"},
+             "tiny16_corr_generic": {"LSEG_CORR_GENERIC": "1"}, "tiny16_no_upsample4x": {"LSEG_NO_UPSAMPLE4X": "1"},
              "tiny16_corr_fullres": {"LSEG_CORR_FULLRES": "1"}}
 
 
