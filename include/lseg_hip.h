@@ -202,6 +202,19 @@ int lseg_set_text_groups(lseg_handle h, const int32_t* host_counts, int B);
 int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out,
                  uint8_t* dev_argmax_out, void* stream);
 
+/* Decoded images in: the input format of EVERY forward entry (lseg_forward*, lseg_forward_lowres, lseg_forward_features, inference and
+ * train mode alike) is engine state.  Default: fp32 NCHW, normalised by the caller, as documented above.
+ * replaces: transforms.ToTensor() + transforms.Normalize(mean, std) (lseg_module.py:37-50) in front of LSeg.forward.
+ *   enabled != 0: dev_x of the forward entries is read as `const uint8_t*` [B,img_h,img_w,3] -- HWC, RGB, densely packed, 16-byte
+ *                 aligned -- and the first stage (the patch-embedding operand pack, or the ResNet-101 stem) computes
+ *                 (float(v) / 255 - mean[c]) / std[c] per value in fp32, torch's operations in torch's order, each correctly rounded.
+ *                 Every output is bit-identical to the same entry fed the tensor ToTensor + Normalize produce on the host.
+ *   enabled == 0: fp32 NCHW again; host_mean3 / host_std3 are not read (may be NULL).
+ * The pointer's type is not checked (it cannot be): the caller states the format here and passes matching memory.
+ * Errors: a NULL or non-finite mean / std, std[c] == 0: LSEG_ERR_INVALID (checked before the handle).  image_dtype LSEG_F16_SPLIT
+ * (its first stage reads fp32 only) and a ViT patch size that is no multiple of 16: LSEG_ERR_UNSUPPORTED; the format stays as it was. */
+int lseg_set_input_u8(lseg_handle h, int enabled, const float* host_mean3, const float* host_std3);
+
 /* Masks for any K <= 32767 without the logits in memory.
  * replaces: LSeg.forward (lseg_net.py:160-205) through the correlation of lseg_net.py:194-203 AND the caller's torch.max(pred, 1)
  *   (lsegmentation_module.py:114-117) -- the [B,K,img_h,img_w] logits (922 MB per image at K = 1000) are neither written nor read.
@@ -476,6 +489,18 @@ int lseg_op_bn_apply_res(const void* d_x_pad, void* d_y_pad, const float* d_stat
                          const float* d_res_stats, const float* d_res_gamma, const float* d_res_beta, int B, int H, int W, int C, float eps,
                          int relu, int dtype, void* stream);
 int lseg_op_rn_stem(const float* d_x, const float* d_w, const float* d_bias, void* d_out, int B, int H, int W, int dtype, void* stream);
+/* lseg_op_rn_stem from a uint8 [B,H,W,3] image (csrc/input_u8.hip): the normalisation of lseg_set_input_u8 fused into the read; the
+ * output equals lseg_op_rn_stem's on the torch-normalised fp32 tensor bit for bit.  Pointers 16-byte aligned, H and W even.  Arguments
+ * are checked before the device is touched. */
+int lseg_op_rn_stem_u8(const uint8_t* d_x, const float* d_w, const float* d_bias, void* d_out, int B, int H, int W, int dtype,
+                       const float* host_mean3, const float* host_std3, void* stream);
+/* The patch-embedding GEMM's operand rows (lseg_vit.py:179, the conv as an im2col gather): d_A 16-bit [B*(H/P)*(W/P), 3*P*P], column
+ * k = c*P*P + i*P + j, from the fp32 NCHW image (P % 8 == 0) or, _u8, from a uint8 [B,H,W,3] image with the normalisation of
+ * lseg_set_input_u8 fused in (P % 16 == 0; bit-equal to the fp32 form on the torch-normalised tensor).  dtype LSEG_BF16 | LSEG_F16,
+ * pointers 16-byte aligned, H and W multiples of P.  Arguments are checked before the device is touched. */
+int lseg_op_patch_rows(const float* d_x, void* d_A, int B, int H, int W, int P, int dtype, void* stream);
+int lseg_op_patch_rows_u8(const uint8_t* d_x, void* d_A, int B, int H, int W, int P, int dtype, const float* host_mean3,
+                          const float* host_std3, void* stream);
 int lseg_op_rn_maxpool(const void* d_in, void* d_out, int B, int H, int W, int C, int dtype, void* stream);
 int lseg_op_conv(const void* d_in, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_out, int B, int H, int W,
                  int Cin, int Cout, int ksize, int stride, int relu_out, int relu_after_res, int dtype, void* stream);
@@ -780,6 +805,13 @@ int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int heigh
 int lseg_op_eval_accumulate(const float* d_outs, float* d_map, int K, int height, int width, int ph, int pw, int crop, int stride,
                             int h_grids, int w_grids, int flip, void* stream);
 int lseg_op_eval_resize(const float* d_src, float* d_dst, int P, int Hi, int Wi, int Ho, int Wo, int accumulate, void* stream);
+/* The crops of one scale straight from ONE decoded image: d_img uint8 [src_h, src_w, 3] (HWC) -> d_crops fp32
+ * [(1+flip)*n, 3, crop, crop].  One kernel (csrc/input_u8.hip) in the reference's order -- normalise ((v / 255 - mean) / std, as
+ * lseg_set_input_u8), bilinear align_corners=True resize to (height, width), pad with host_pad3, cut, mirror -- with the arithmetic of
+ * lseg_op_eval_resize: bit-equal to lseg_op_eval_resize + lseg_op_eval_make_crops on the torch-normalised fp32 image. */
+int lseg_op_eval_make_crops_u8(const uint8_t* d_img, float* d_crops, int src_h, int src_w, int height, int width, int crop, int stride,
+                               int h_grids, int w_grids, int flip, const float* host_pad3, const float* host_mean3, const float* host_std3,
+                               void* stream);
 /* lseg_op_eval_accumulate on the logits lseg_forward_lowres leaves: d_low fp32 [(1+flip)*n, K, crop/2, crop/2] is read through
  * output_conv's x2 bilinear (align_corners=True) on the fly, so the [(1+flip)*n, K, crop, crop] stack never exists.  Defined as -- and
  * bit-identical to -- lseg_op_eval_accumulate(lseg_op_upsample2x_planes(d_low)): per covering box in (idh,idw) order

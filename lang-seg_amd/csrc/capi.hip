@@ -93,6 +93,16 @@ int lseg_get_text_features(lseg_handle h, void* dev_out, void* stream) {
     return h->e->get_text_features(dev_out, (hipStream_t)stream);
 }
 
+int lseg_set_input_u8(lseg_handle h, int enabled, const float* host_mean3, const float* host_std3) {
+    NormU8 n = {};
+    if (enabled) {                       // the values are checked before the handle: a bad std is LSEG_ERR_INVALID with or without a device
+        int r = norm_u8_check("lseg_set_input_u8", host_mean3, host_std3, &n);
+        if (r) return r;
+    }
+    GUARD(h);
+    return h->e->set_input_u8(enabled != 0, n);
+}
+
 int lseg_forward(lseg_handle h, const float* dev_x, int B, float* dev_logits_out, uint8_t* dev_argmax_out, void* stream) {
     GUARD(h);
     Engine::ForwardOut out;
@@ -477,6 +487,41 @@ int lseg_op_rn_stem(const float* x, const float* w, const float* bias, void* out
     int dt;
     if ((r = op_dt(dtype, &dt))) return r;
     return launch_rn_stem(x, w, bias, out, B, H, W, dt, (hipStream_t)stream);
+}
+
+// the uint8 first stages (input_u8.hip): the argument checks come before the device is looked for
+int lseg_op_rn_stem_u8(const uint8_t* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, const float* host_mean3,
+                       const float* host_std3, void* stream) {
+    int r, dt;
+    NormU8 n;
+    if ((r = norm_u8_check("rn_stem_u8", host_mean3, host_std3, &n))) return r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if ((r = rn_stem_u8_check(x, w, bias, out, B, H, W, dt))) return r;
+    if ((r = require_device())) return r;
+    return launch_rn_stem_u8(x, w, bias, out, B, H, W, dt, n, (hipStream_t)stream);
+}
+
+int lseg_op_patch_rows(const float* x, void* A, int B, int H, int W, int P, int dtype, void* stream) {
+    int r, dt;
+    if (!x || !A) return set_error(LSEG_ERR_INVALID, "patch_rows: NULL pointer");
+    if ((r = op_dt(dtype, &dt))) return r;
+    if (dt == DT_F32) return set_error(LSEG_ERR_INVALID, "patch_rows: dtype %d", dtype);
+    if (B < 1 || H < 1 || W < 1 || P < 1 || H % P || W % P) return set_error(LSEG_ERR_INVALID, "patch_rows: B=%d H=%d W=%d P=%d (H, W multiples of P)", B, H, W, P);
+    if (P % 8) return set_error(LSEG_ERR_UNSUPPORTED, "patch_rows: P=%d must be a multiple of 8", P);
+    if (((uintptr_t)x | (uintptr_t)A) & 15) return set_error(LSEG_ERR_INVALID, "patch_rows: pointers must be 16-byte aligned");
+    if ((r = require_device())) return r;
+    return launch_im2col_patch(x, A, B, H, W, P, dt, (hipStream_t)stream);
+}
+
+int lseg_op_patch_rows_u8(const uint8_t* x, void* A, int B, int H, int W, int P, int dtype, const float* host_mean3, const float* host_std3,
+                          void* stream) {
+    int r, dt;
+    NormU8 n;
+    if ((r = norm_u8_check("patch_rows_u8", host_mean3, host_std3, &n))) return r;
+    if ((r = op_dt(dtype, &dt))) return r;
+    if ((r = im2col_patch_u8_check(x, A, B, H, W, P, dt))) return r;
+    if ((r = require_device())) return r;
+    return launch_im2col_patch_u8(x, A, B, H, W, P, dt, n, (hipStream_t)stream);
 }
 
 int lseg_op_rn_maxpool(const void* in, void* out, int B, int H, int W, int C, int dtype, void* stream) {
@@ -957,6 +1002,20 @@ int lseg_op_eval_make_crops(const float* d_img, float* d_crops, int C, int heigh
     if (C < 1 || C > 3 || height < 1 || width < 1 || crop < 1 || stride < 1 || h_grids < 1 || w_grids < 1)
         return set_error(LSEG_ERR_INVALID, "eval_make_crops: bad geometry");
     return launch_eval_make_crops(d_img, d_crops, C, height, width, crop, stride, h_grids, w_grids, flip ? 1 : 0, host_pad3, (hipStream_t)stream);
+}
+int lseg_op_eval_make_crops_u8(const uint8_t* d_img, float* d_crops, int src_h, int src_w, int height, int width, int crop, int stride, int h_grids,
+                               int w_grids, int flip, const float* host_pad3, const float* host_mean3, const float* host_std3, void* stream) {
+    NormU8 n;
+    int r = norm_u8_check("eval_make_crops_u8", host_mean3, host_std3, &n);
+    if (r) return r;
+    if (!d_img || !d_crops || !host_pad3) return set_error(LSEG_ERR_INVALID, "eval_make_crops_u8: NULL pointer");
+    if (src_h < 1 || src_w < 1 || height < 1 || width < 1 || crop < 1 || stride < 1 || h_grids < 1 || w_grids < 1 ||
+        (long long)h_grids * w_grids > 0x3fffffff)
+        return set_error(LSEG_ERR_INVALID, "eval_make_crops_u8: bad geometry");
+    if ((uintptr_t)d_crops & 3) return set_error(LSEG_ERR_INVALID, "eval_make_crops_u8: the crops must be 4-byte aligned");
+    if ((r = require_device())) return r;
+    return launch_eval_make_crops_u8(d_img, d_crops, src_h, src_w, height, width, crop, stride, h_grids, w_grids, flip ? 1 : 0, host_pad3, n,
+                                     (hipStream_t)stream);
 }
 // the geometry contract of the accumulate and finalize entries, checked before the device is touched: a [K, height, width] map inside the
 // padded (ph, pw) image that the h_grids x w_grids boxes cover; lowres: the logits are crop/2 x crop/2 planes

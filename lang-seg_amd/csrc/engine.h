@@ -119,6 +119,10 @@ public:
         const CorrLoss* loss = nullptr;
     };
     int forward(const float* x, int B, const ForwardOut& out, hipStream_t st);
+    // lseg_set_input_u8: the image pointer of every forward entry (inference and train mode) is uint8 [B, img_h, img_w, 3] and the first
+    // stage normalises it (input_u8.hip); off = fp32 NCHW, the default.  The pointer keeps its `const float*` type through the schedule:
+    // only the first stage (patch_embed, the ResNet stem) dereferences it, and that is where the format is looked at
+    int set_input_u8(bool on, const NormU8& norm);        // norm: validated by the caller (norm_u8_check), read only when on
     // lseg_forward_labels_loss: the labels forward with the loss, then (dev_counts given) lseg_op_label_stats on the label map it wrote.
     // The planes nobody asked for (lse, tlogit), the reduction's partials and label_stats' flag words live in loss_ws_, made on first use
     int forward_labels_loss(const float* x, int B, const int64_t* target, int ignore_index, int16_t* label_out, float* score_out, float* lse_out,
@@ -257,6 +261,8 @@ private:
     // derived geometry
     int gh_, gw_, np_, ntok_, npad_, img_dt_;
     int rows_alloc_ = 0;                        // allocated rows of x_ / ln_ / att_ / mlp_: max_batch * ntok rounded up to 256 (gemm_asm.hip)
+    bool in_u8_ = false; NormU8 in_norm_ = {};  // input format (set_input_u8)
+    int image_stem(const float* x, const float* w, const float* bias, int B, int relu, hipStream_t st);      // ResNet stem in the input's format
     bool strict_ = false;                       // split-precision mode (lseg_config.image_dtype == LSEG_F16_SPLIT)
     std::map<const void*, size_t> plane_;       // 16-bit buffer -> element offset of its lo plane
     size_t pl(const void* p) const { auto it = plane_.find(p); return it == plane_.end() ? 0 : it->second; }

@@ -393,8 +393,13 @@ int Engine::pack_resnet(hipStream_t st) {
 // where the DPT neck reads it.  Every block of a stage writes L_[l]: block 0 from its downsample branch, blocks 1.. IN PLACE
 // (relu(bn3(conv3(t)) + x) with x = L_[l] itself -- each output element is read as the residual by the lane that then overwrites it;
 // the conv1 that reads x ran before).  No host synchronisation, no layout copies.
+int Engine::image_stem(const float* x, const float* w, const float* bias, int B, int relu, hipStream_t st) {
+    if (in_u8_) TRY(rn_stem_u8_check(x, w, bias, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_));       // (the caller's pointer: its alignment)
+    if (in_u8_) return launch_rn_stem_u8((const uint8_t*)x, w, bias, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, in_norm_, st, relu);
+    return launch_rn_stem(x, w, bias, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, st, relu);
+}
 int Engine::resnet_forward(const float* x, int B, hipStream_t st) {
-    TRY(launch_rn_stem(x, rs_stem_w_, rs_stem_b_, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, st));
+    TRY(image_stem(x, rs_stem_w_, rs_stem_b_, B, 1, st));
     TRY(launch_rn_maxpool(rs_stem_, rs_pool_, B, cfg.img_h / 2, cfg.img_w / 2, 64, img_dt_, st));
     const uint16_t* in = rs_pool_;
     int h = lh_[0], w = lw_[0];
@@ -822,6 +827,10 @@ int Engine::out_conv(int l, int B, hipStream_t st) {
 int Engine::patch_embed(const float* x_in, float* x, int B, hipStream_t st) {
     const lseg_config& c = cfg;
     if (strict_) TRY(launch_im2col_split(x_in, patchA_, pl(patchA_), B, c.img_h, c.img_w, c.patch, st));
+    else if (in_u8_) {
+        TRY(im2col_patch_u8_check(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_));                    // (the caller's pointer: its alignment)
+        TRY(launch_im2col_patch_u8((const uint8_t*)x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, in_norm_, st));
+    }
     else TRY(launch_im2col_patch(x_in, patchA_, B, c.img_h, c.img_w, c.patch, img_dt_, st));
     GemmArgs g = lin_args(patchA_, patch_, B * np_, x, DT_F32);
     to_periodic_rows(g, pos_, DT_F32, c.dim, np_, ntok_, 1);

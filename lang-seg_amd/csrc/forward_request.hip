@@ -60,6 +60,16 @@ int Engine::check_request(const float* x, int B, const ForwardOut& out, const Ro
     return 0;
 }
 
+// The input format of every forward entry.  The split-precision mode has a first stage of its own (strict.hip: the image as (hi, lo) fp16
+// planes) with no uint8 form: refused, nothing falls back.  The patch rows need patch % 16 == 0 (a lane owns 16 pixels of a patch row)
+int Engine::set_input_u8(bool on, const NormU8& n) {
+    if (!on) { in_u8_ = false; return 0; }
+    if (strict_) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_set_input_u8: the split-precision mode (image_dtype LSEG_F16_SPLIT) reads fp32 images only");
+    if (!resnet_ && cfg.patch % 16) return set_error(LSEG_ERR_UNSUPPORTED, "lseg_set_input_u8: patch=%d must be a multiple of 16", cfg.patch);
+    in_norm_ = n; in_u8_ = true;
+    return 0;
+}
+
 // ragged label sets in train mode: the fused-loss route on the plain head only.  Refused before any kernel runs: the arch_option 1/2 head
 // blocks (their planes are rectangular) and the ResNet-101 decoder-training mode (never run with ragged sets: refused rather than left
 // untested).  Deterministic reductions (flags bit 3) need nothing new: the ragged loss kernels hold no fp32 atomic -- the counts are

@@ -311,4 +311,20 @@ int launch_pack_conv1x1(const float* w, const float* bn_w, const float* bn_b, co
 int launch_pack_rn_stem(const float* w, const float* bn_w, const float* bn_b, const float* bn_m, const float* bn_v, float bn_eps,
                         float* wp, float* bias_out, hipStream_t st);
 
+// ---- input_u8.hip: decoded images in -- uint8 [B, H, W, 3] (HWC, RGB, dense), ToTensor + Normalize(mean, std) fused into the first stage:
+// v -> (float(v) / 255 - mean[c]) / std[c] in fp32, torch's order and rounding.  Each launch writes what its fp32 counterpart
+// (launch_im2col_patch, launch_rn_stem, launch_eval_resize + launch_eval_make_crops) writes for the torch-normalised tensor, bit for bit
+struct NormU8 { float mean[3], std[3]; };
+int norm_u8_check(const char* what, const float* mean, const float* std, NormU8* out);      // NULL, non-finite, std == 0: LSEG_ERR_INVALID
+// the argument contract of the two launches below (alignment, geometry, dtype), without a device.  The launches themselves do not check:
+// their callers do, once -- the op-level C entries before they look for a device, the engine's first stage on the caller's image pointer
+int im2col_patch_u8_check(const void* x, const void* A, int B, int H, int W, int P, int dtype);
+int rn_stem_u8_check(const void* x, const void* w, const void* bias, const void* out, int B, int H, int W, int dtype);
+int launch_im2col_patch_u8(const uint8_t* x, void* A, int B, int H, int W, int P, int dtype, const NormU8& n, hipStream_t st);
+int launch_rn_stem_u8(const uint8_t* x, const float* w, const float* bias, void* out, int B, int H, int W, int dtype, const NormU8& n,
+                      hipStream_t st, int relu = 1);
+// img uint8 [Hi, Wi, 3] -> crops fp32 [(1 + flip) * h_grids * w_grids, 3, crop, crop] of the image resized to (height, width)
+int launch_eval_make_crops_u8(const uint8_t* img, float* crops, int Hi, int Wi, int height, int width, int crop, int stride, int h_grids,
+                              int w_grids, int flip, const float* pad3, const NormU8& n, hipStream_t st);
+
 }  // namespace lseg

@@ -401,7 +401,7 @@ int Engine::rn_bn(const uint16_t* x, uint16_t* y, RnBlock& k, int i, const uint1
 // blocks 1.. write relu(bn3(conv3 t) + x) over x = L_[l] as the inference path does.
 int Engine::resnet_forward_train(const float* x, int B, hipStream_t st) {
     const int H2 = cfg.img_h / 2, W2 = cfg.img_w / 2;
-    TRY(launch_rn_stem(x, rs_stem_wraw_, rs_stem_wraw_ + 147 * 64, rs_stem_, B, cfg.img_h, cfg.img_w, img_dt_, st, 0));
+    TRY(image_stem(x, rs_stem_wraw_, rs_stem_wraw_ + 147 * 64, B, 0, st));
     {
         const double cnt = (double)B * H2 * W2;
         TRY(launch_bn_stats(rs_stem_, rs_stem_st_, B, H2, W2, 64, img_dt_, st, ws_det_ ? 1 : zero_note(zero_fwd_, rs_stem_st_, 128) ? 1 : 0, ws_det_,

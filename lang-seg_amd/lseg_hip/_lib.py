@@ -87,6 +87,7 @@ SIGNATURES = {
     "lseg_set_text_groups": (_i, [_vp, _vp, _i]),
     "lseg_overflow_seen": (_i, [_vp, _i]),
     "lseg_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "lseg_set_input_u8": (_i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     "lseg_forward_labels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "lseg_forward_labels_conf": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lseg_forward_labels_loss": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -143,6 +144,9 @@ SIGNATURES = {
     "lseg_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_upsample2x_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "lseg_op_rn_stem": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lseg_op_rn_stem_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp]),
+    "lseg_op_patch_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_patch_rows_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp]),
     "lseg_op_rn_maxpool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_conv_ex": (_i, [C.POINTER(LSegConvCase), _vp]),
@@ -189,6 +193,7 @@ SIGNATURES = {
     "lseg_op_eval_accumulate_window_lowres": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_finalize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lseg_op_eval_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "lseg_op_eval_make_crops_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), C.POINTER(_f), _vp]),
     "lseg_op_eval_merge_labels": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "lseg_op_l2norm_scale_backward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "lseg_op_corr_group_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

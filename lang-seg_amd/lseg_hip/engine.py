@@ -100,6 +100,11 @@ def check_ragged_target(target, B: int, H: int, W: int):
         raise ValueError(f"ragged training target must be [B,H,W] = {(B, H, W)}, got {tuple(target.shape)}")
 
 
+def image_dims(x: torch.Tensor):
+    """(B, H, W) of an image batch in either input format: normalised float [B,3,H,W], or decoded uint8 [B,H,W,3] (set_input_u8)"""
+    return (x.shape[0], x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else (x.shape[0], x.shape[2], x.shape[3])
+
+
 class HipEngine:
     """One engine = one (backbone, H, W, max_batch, max_labels) plan on one GPU."""
 
@@ -141,6 +146,7 @@ class HipEngine:
         self.image_dtype = image_dtype
         self.grads: Dict[str, torch.Tensor] = {}
         self.frozen_encoder = False
+        self.input_u8 = None                               # (mean, std) while the uint8 input format is set (set_input_u8)
         self._cb_error: Optional[BaseException] = None     # first exception raised inside a ctypes callback (ctypes would swallow it)
 
     def close(self):
@@ -238,13 +244,46 @@ class HipEngine:
         _lib.check(self.lib.lseg_set_text_cache(self._h, int(enabled)))
 
     # ---- forward -----------------------------------------------------------------------------------------
+    def set_input_u8(self, enabled: bool = True, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
+        """The input format of every forward method (lseg_set_input_u8).  enabled: x is a decoded image batch, uint8 [B,H,W,3] (HWC, RGB,
+        contiguous) on the engine's device, and the first stage applies ToTensor + Normalize(mean, std) -- (v / 255 - mean) / std in fp32,
+        torch's operations and rounding, so every output equals the one for the tensor that transform gives.  Not enabled (the default
+        state): x is the normalised float32 [B,3,H,W] tensor.  LSEG_ERR_INVALID for a std of 0 or a non-finite value, LSEG_ERR_UNSUPPORTED
+        on a "strict" engine (its first stage reads fp32 only); the format then stays what it was.
+        The kernels read the batch in 16-byte chunks from its first byte: a batch whose storage does not start on a 16-byte boundary (a
+        slice such as u8[1:] of a larger batch can) is copied to a fresh allocation by the forward methods; the C entries refuse it."""
+        if not enabled:
+            _lib.check(self.lib.lseg_set_input_u8(self._h, 0, None, None))
+            self.input_u8 = None
+            return
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError(f"set_input_u8: mean and std are 3 values each (RGB), got {len(mean)} and {len(std)}")
+        _lib.check(self.lib.lseg_set_input_u8(self._h, 1, (C.c_float * 3)(*mean), (C.c_float * 3)(*std)))
+        self.input_u8 = (tuple(mean), tuple(std))
+
     def _check_input(self, x: torch.Tensor):
-        if x.device != self.device or x.dtype != torch.float32:
-            raise ValueError(f"x must be float32 on {self.device}, got {x.dtype} on {x.device}")
+        """The image batch against the engine's plan and input format.  A batch in the OTHER format than the one set is refused as
+        LSegError LSEG_ERR_INVALID (-1): the C entries cannot tell a uint8 pointer from a float one, so it is decided here."""
+        if x.dtype == torch.uint8:
+            if self.input_u8 is None:
+                raise _lib.LSegError(-1, "x is a uint8 image batch but the engine reads float32 [B,3,H,W]: call set_input_u8(True, mean, std) first")
+            if x.device != self.device:
+                raise ValueError(f"x must live on {self.device}, got {x.device}")
+            if x.dim() != 4 or tuple(x.shape[1:]) != (self.img_h, self.img_w, 3):
+                raise _lib.LSegError(-1, f"uint8 input is [B,H,W,3] (HWC) = [B,{self.img_h},{self.img_w},3] for this engine, got {tuple(x.shape)}")
+        else:
+            if self.input_u8 is not None:
+                raise _lib.LSegError(-1, f"the engine's input format is uint8 [B,H,W,3] (set_input_u8), got {x.dtype}: call set_input_u8(False) "
+                                         "for normalised float32 [B,3,H,W] input")
+            if x.device != self.device or x.dtype != torch.float32:
+                raise ValueError(f"x must be float32 on {self.device}, got {x.dtype} on {x.device}")
+            if x.dim() != 4 or tuple(x.shape[1:]) != (3, self.img_h, self.img_w):
+                raise ValueError(f"engine was planned for 3x{self.img_h}x{self.img_w}, got {'x'.join(str(d) for d in x.shape[1:])}")
         x = x.contiguous()
-        B, Cc, H, W = x.shape
-        if (Cc, H, W) != (3, self.img_h, self.img_w):
-            raise ValueError(f"engine was planned for 3x{self.img_h}x{self.img_w}, got {Cc}x{H}x{W}")
+        if x.dtype == torch.uint8 and x.data_ptr() % 16:        # the uint8 first stages load 16-byte chunks (lseg_set_input_u8)
+            x = x.clone()
+        B = x.shape[0]
         if self._group > 0 and self._K != B * self._group:
             raise ValueError(f"per-image label sets: {self._K} token rows != batch {B} x {self._group}")
         if self._groups is not None and len(self._groups) != B:
@@ -264,7 +303,7 @@ class HipEngine:
         """Masks for any K <= 32767 (lseg_forward_labels): int16 [B,H,W] = torch.max(logits, 1)[1] of the logits forward() would return,
         without those logits -- and, with want_score, fp32 [B,H,W] = torch.max(logits, 1)[0]."""
         x = self._check_input(x)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         lab = torch.empty((B, H, W), dtype=torch.int16, device=self.device)
         score = torch.empty((B, H, W), dtype=torch.float32, device=self.device) if want_score else None
         _lib.check(self.lib.lseg_forward_labels(
@@ -279,7 +318,7 @@ class HipEngine:
         torch.sort(logits, 1, descending=True, stable=True) (-1 / -inf with a single label); "lse" fp32 = torch.logsumexp(logits, 1).
         The winner's softmax probability is exp(score - lse), the top-2 margin score - score2."""
         x = self._check_input(x)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         out = {"label": torch.empty((B, H, W), dtype=torch.int16, device=self.device),
                "score": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
                "label2": torch.empty((B, H, W), dtype=torch.int16, device=self.device),
@@ -299,7 +338,7 @@ class HipEngine:
         "counts" int64 = label_stats' counters of "label" against the target ([2 + 3K]; ragged: [2 + 3 sum of the list lengths]); with
         plane=True also "nll_plane" fp32 [B,H,W], the per-pixel loss (0 where the pixel is not valid)."""
         x = self._check_input(x)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         if not torch.is_tensor(target) or tuple(target.shape) != (B, H, W) or target.dtype.is_floating_point:
             raise ValueError(f"forward_labels_loss: target must be an integer tensor [{B},{H},{W}]")
         t = target.detach().to(self.device, torch.int64).contiguous()
@@ -323,7 +362,7 @@ class HipEngine:
         bit-identical to forward(x); the [B,Kout,H,W] tensor is never written."""
         x = self._check_input(x)
         self._refuse_ragged(x)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         Kout = self._group if self._group > 0 else self._K
         low = torch.empty((B, Kout, H // 2, W // 2), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.lseg_forward_lowres(self._h, C.c_void_p(x.data_ptr()), B, C.c_void_p(low.data_ptr()),
@@ -336,7 +375,7 @@ class HipEngine:
         (lseg_forward_features) -- held by the caller, any slice of a label set is scored from them later (score_features).  No text is
         read.  Per-image label sets, train mode and the schedules without the commuted correlation raise LSEG_ERR_UNSUPPORTED."""
         x = self._check_input(x)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         fb, sb = C.c_size_t(), C.c_size_t()
         _lib.check(self.lib.lseg_features_bytes(self._h, B, C.byref(fb), C.byref(sb)))
         assert fb.value == B * (H // 4 + 2) * (W // 4 + 2) * self.cfg.out_c * 2 and sb.value == B * (H // 2) * (W // 2) * 4
@@ -366,7 +405,7 @@ class HipEngine:
         x = self._check_input(x)
         if not (self._groups is not None and self.training and not want_logits and not want_argmax):    # the ragged training step: loss only
             self._refuse_ragged(x)
-        B, Cc, H, W = x.shape
+        B, H, W = image_dims(x)
         Kout = self._group if self._group > 0 else self._K
         if want_argmax and not want_logits and Kout > 256:
             return self.forward_labels(x)                     # uint8 cannot hold the labels: the int16 masks (uint8 stays the K <= 256 form)

@@ -198,9 +198,16 @@ class BatchedMultiEval(torch.nn.Module):
             out = out[:n] + torch.flip(out[n:], dims=[3])
         return out
 
+    @staticmethod
+    def _one(img: torch.Tensor) -> torch.Tensor:
+        """one image of a list on the device, as forward takes it: float [3,h,w] -> [1,3,h,w]; a decoded uint8 [h,w,3] image as it is"""
+        return img.cuda() if img.dtype == torch.uint8 else img.unsqueeze(0).cuda()
+
     def parallel_forward(self, inputs: Sequence[torch.Tensor], label_set=None) -> List[torch.Tensor]:
-        """list of [3,h,w] images in, list of [1,nclass,h,w] score maps out (encoding_models.py:35-52)."""
-        return [self.forward(img.unsqueeze(0).cuda(), label_set) for img in inputs]
+        """list of [3,h,w] images in, list of [1,nclass,h,w] score maps out (encoding_models.py:35-52).  Here and in every method below
+        an image may also be a decoded one -- torch.uint8 [h,w,3] (HWC, RGB) -- instead of the normalised float tensor: the device kernels
+        then apply ToTensor + Normalize(module.mean, module.std) themselves and the results are the same bits."""
+        return [self.forward(self._one(img), label_set) for img in inputs]
 
     def _chunked(self, xs: torch.Tensor, label_set, lowres: bool) -> torch.Tensor:
         """The module's logits of a stack of crops, max_batch crops per forward."""
@@ -215,6 +222,37 @@ class BatchedMultiEval(torch.nn.Module):
     def _module_eval(self, xs: torch.Tensor, label_set) -> torch.Tensor:
         return self._chunked(xs, label_set, self.lowres)
 
+    @staticmethod
+    def _image_hw(image: torch.Tensor):
+        """(image as the kernels read it, h, w): a normalised float [1,3,h,w] image, or a decoded uint8 [h,w,3] / [1,h,w,3] one"""
+        if image.dtype == torch.uint8:
+            if image.dim() == 4 and image.shape[0] == 1:
+                image = image[0]
+            if image.dim() != 3 or image.shape[2] != 3:
+                raise ValueError(f"a uint8 image is [h,w,3] (HWC), got {tuple(image.shape)}")
+            return image.contiguous(), image.shape[0], image.shape[1]
+        batch, ch, h, w = image.shape
+        assert batch == 1 and image.dtype == torch.float32
+        return image.contiguous(), h, w
+
+    def _scale_crops(self, lib, image, h, w, g, pad, st):
+        """The crops (and mirrored twins) of scale geometry g, fp32 [twins * n_box, 3, crop, crop]: resize + make_crops for a float image,
+        the one fused kernel (normalise, resize, pad, cut: lseg_op_eval_make_crops_u8, the same bits) for a uint8 one."""
+        from . import _lib
+        P = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
+        crop, flip = self.crop_size, int(self.flip)
+        ch = 3 if image.dtype == torch.uint8 else image.shape[1]
+        crops = torch.empty(((2 if self.flip else 1) * g.n_box, ch, crop, crop), dtype=torch.float32, device=image.device)
+        if image.dtype == torch.uint8:
+            mean, std = ((C.c_float * 3)(*[float(v) for v in m]) for m in (self.module.mean, self.module.std))
+            _lib.check(lib.lseg_op_eval_make_crops_u8(P(image), P(crops), h, w, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip,
+                                                      pad, mean, std, st))
+            return crops
+        cur = image.new_empty((ch, g.height, g.width))
+        _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, g.height, g.width, 0, st))
+        _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip, pad, st))
+        return crops
+
     @torch.no_grad()
     def _forward_device(self, image: torch.Tensor, label_set=None) -> torch.Tensor:
         """The same schedule with the data movement in csrc/evaluator.hip (image on the GPU)."""
@@ -222,15 +260,14 @@ class BatchedMultiEval(torch.nn.Module):
         lib = _lib.load()
         P = lambda t: C.c_void_p(t.data_ptr())
         st = C.c_void_p(torch.cuda.current_stream(image.device).cuda_stream)
-        batch, ch, h, w = image.shape
-        assert batch == 1 and image.dtype == torch.float32
+        image, h, w = self._image_hw(image)
         nclass = self.nclass if label_set is None else len(label_set)
         crop = self.crop_size
         if self.module._up_kwargs != {"mode": "bilinear", "align_corners": True}:
             raise ValueError("the device evaluator implements the reference's bilinear / align_corners=True resize")
         pad = (C.c_float * 3)(*[float(v) for v in (-np.array(self.module.mean) / np.array(self.module.std))])
-        image = image.contiguous()
-        scores = image.new_zeros((1, nclass, h, w))
+        f32 = torch.empty(0, dtype=torch.float32, device=image.device)         # new_empty / new_zeros of the fp32 maps, whatever the image's dtype
+        scores = f32.new_zeros((1, nclass, h, w))
         flip, twins = int(self.flip), 2 if self.flip else 1
         side = crop // 2 if self.lowres else crop
         geo = [scale_geometry(h, w, scale, self.base_size, crop) for scale in self.scales]
@@ -245,11 +282,7 @@ class BatchedMultiEval(torch.nn.Module):
             net.reserve_batch(min(self.max_batch, largest), crop, crop, None if label_set is None else nclass, image.device)
 
         def make_crops(g):                   # a scale's crops exist from its step's turn on, not before
-            cur = image.new_empty((ch, g.height, g.width))
-            _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, g.height, g.width, 0, st))
-            crops = image.new_empty((twins * g.n_box, ch, crop, crop))
-            _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip, pad, st))
-            return crops
+            return self._scale_crops(lib, image, h, w, g, pad, st)
 
         def logits(xs):                      # crops are independent in the engine: the per-crop logits do not depend on the grouping
             outs = self._module_eval(xs, label_set).contiguous()
@@ -273,7 +306,7 @@ class BatchedMultiEval(torch.nn.Module):
                 for i in step.scales:
                     g = geo[i]
                     nc = twins * g.n_box
-                    smap = image.new_empty((nclass, g.height, g.width))
+                    smap = f32.new_empty((nclass, g.height, g.width))
                     _lib.check(accumulate(P(outs[o0:o0 + nc]), P(smap), *dims(g), flip, st))     # a contiguous slice: this scale's crops (+ twins)
                     add_resized(smap, g)
                     o0 += nc
@@ -281,7 +314,7 @@ class BatchedMultiEval(torch.nn.Module):
             else:                            # windows add into the scale's fp32 sum in box order, finalize divides: the same bits
                 g, crops = geo[step.scales[0]], stacks[0]
                 n = g.n_box
-                smap = image.new_zeros((nclass, g.height, g.width))
+                smap = f32.new_zeros((nclass, g.height, g.width))
                 for first, nb in step.windows:
                     xs = torch.cat([crops[first:first + nb], crops[n + first:n + first + nb]], dim=0) if self.flip else crops[first:first + nb]
                     outs = logits(xs)
@@ -311,7 +344,7 @@ class BatchedMultiEval(torch.nn.Module):
 
     def parallel_forward_labels(self, inputs: Sequence[torch.Tensor], label_set=None, confidence=False, panel=64) -> List[tuple]:
         """list of [3,h,w] images in, list of forward_labels results out."""
-        return [self.forward_labels(img.unsqueeze(0).cuda(), label_set, confidence, panel) for img in inputs]
+        return [self.forward_labels(self._one(img), label_set, confidence, panel) for img in inputs]
 
     def parallel_forward_metrics(self, inputs: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], label_set=None, panel=64) -> List[dict]:
         """list of [3,h,w] images and of their [h,w] integer masks in, one dict of pixAcc / IoU counts per image out
@@ -324,9 +357,10 @@ class BatchedMultiEval(torch.nn.Module):
         nclass = self.nclass if label_set is None else len(label_set)
         out = []
         for img, tgt in zip(inputs, targets):
-            if tuple(tgt.shape) != tuple(img.shape[1:]):
-                raise ValueError(f"parallel_forward_metrics: a mask of {tuple(tgt.shape)} for an image of {tuple(img.shape[1:])}")
-            label = self.forward_labels(img.unsqueeze(0).cuda(), label_set, False, panel)[0]
+            hw = tuple(img.shape[:2]) if img.dtype == torch.uint8 else tuple(img.shape[1:])
+            if tuple(tgt.shape) != hw:
+                raise ValueError(f"parallel_forward_metrics: a mask of {tuple(tgt.shape)} for an image of {hw}")
+            label = self.forward_labels(self._one(img), label_set, False, panel)[0]
             out.append(seg_stats_labels(label.unsqueeze(0), tgt.unsqueeze(0).to(label.device), nclass))
         return out
 
@@ -367,15 +401,14 @@ class BatchedMultiEval(torch.nn.Module):
         lib = _lib.load()
         P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         st = C.c_void_p(torch.cuda.current_stream(image.device).cuda_stream)
-        batch, ch, h, w = image.shape
-        assert batch == 1 and image.dtype == torch.float32
+        image, h, w = self._image_hw(image)
+        f32 = torch.empty(0, dtype=torch.float32, device=image.device)
         nclass = self.nclass if label_set is None else len(label_set)
         panels = plan_panels(nclass, panel)
         crop = self.crop_size
         if self.module._up_kwargs != {"mode": "bilinear", "align_corners": True}:
             raise ValueError("the device evaluator implements the reference's bilinear / align_corners=True resize")
         pad = (C.c_float * 3)(*[float(v) for v in (-np.array(self.module.mean) / np.array(self.module.std))])
-        image = image.contiguous()
         flip, twins = int(self.flip), 2 if self.flip else 1
         side = crop // 2
         geo = [scale_geometry(h, w, scale, self.base_size, crop) for scale in self.scales]
@@ -395,12 +428,7 @@ class BatchedMultiEval(torch.nn.Module):
         for step in steps:
             stacks = []
             for i in step.scales:
-                g = geo[i]
-                cur = image.new_empty((ch, g.height, g.width))
-                _lib.check(lib.lseg_op_eval_resize(P(image), P(cur), ch, h, w, g.height, g.width, 0, st))
-                crops = image.new_empty((twins * g.n_box, ch, crop, crop))
-                _lib.check(lib.lseg_op_eval_make_crops(P(cur), P(crops), ch, g.height, g.width, crop, g.stride, g.h_grids, g.w_grids, flip, pad, st))
-                stacks.append(crops)
+                stacks.append(self._scale_crops(lib, image, h, w, geo[i], pad, st))
             if step.windows is None:
                 held.append(hold(torch.cat(stacks, dim=0) if len(stacks) > 1 else stacks[0]))
             else:
@@ -416,11 +444,11 @@ class BatchedMultiEval(torch.nn.Module):
             return outs
 
         label = torch.empty((h, w), dtype=torch.int16, device=image.device)
-        score = image.new_empty((h, w))
+        score = f32.new_empty((h, w))
         label2 = torch.empty_like(label) if confidence else None
         score2, lse = (torch.empty_like(score), torch.empty_like(score)) if confidence else (None, None)
         for pi, (row0, rows) in enumerate(panels):
-            scores = image.new_zeros((rows, h, w))
+            scores = f32.new_zeros((rows, h, w))
             for step, hs in zip(steps, held):
                 if step.windows is None:
                     outs = logits(hs, row0, rows)
@@ -428,7 +456,7 @@ class BatchedMultiEval(torch.nn.Module):
                     for i in step.scales:
                         g = geo[i]
                         nc = twins * g.n_box
-                        smap = image.new_empty((rows, g.height, g.width))
+                        smap = f32.new_empty((rows, g.height, g.width))
                         _lib.check(lib.lseg_op_eval_accumulate_lowres(P(outs[o0:o0 + nc]), P(smap), rows, g.height, g.width, g.ph, g.pw, crop, g.stride,
                                                                       g.h_grids, g.w_grids, flip, st))
                         _lib.check(lib.lseg_op_eval_resize(P(smap), P(scores), rows, g.height, g.width, h, w, 1, st))
@@ -436,7 +464,7 @@ class BatchedMultiEval(torch.nn.Module):
                     del outs, smap
                 else:
                     g = geo[step.scales[0]]
-                    smap = image.new_zeros((rows, g.height, g.width))
+                    smap = f32.new_zeros((rows, g.height, g.width))
                     for (first, nb), hw in zip(step.windows, hs):
                         outs = logits(hw, row0, rows)
                         _lib.check(lib.lseg_op_eval_accumulate_window_lowres(P(outs), P(smap), rows, g.height, g.width, g.ph, g.pw, crop, g.stride,
@@ -454,6 +482,9 @@ class BatchedMultiEval(torch.nn.Module):
     @torch.no_grad()
     def _forward_torch(self, image: torch.Tensor, label_set=None) -> torch.Tensor:
         """The torch statement of the schedule (host tensors; the definition the device kernels are tested against)."""
+        if image.dtype == torch.uint8:
+            raise ValueError("a decoded uint8 [h,w,3] image is read by the device kernels only: move it to the GPU (image.cuda()), or "
+                             "normalise it to a float [1,3,h,w] tensor for the torch schedule")
         batch, _, h, w = image.shape
         assert batch == 1
         nclass = self.nclass if label_set is None else len(label_set)

@@ -505,7 +505,7 @@ class LSegmentationModule(_Base):
         net = self.net
         ignore = self.other_kwargs.get("ignore_index", -1)
         eng, keys, _ = net._train_inputs(img, "")
-        eng.forward(img.float(), want_logits=False)
+        eng.forward(net._input(eng, img), want_logits=False)
         ts = eng._ts
         try:
             loss = eng.backward(target=target.to(eng.device, torch.int64), ignore_index=ignore, accumulate=False)

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from lseg_hip.config import get_config
+from lseg_hip.engine import image_dims
 from lseg_hip.tokenizer import tokenize
 from .lseg_blocks import FeatureFusionBlock_custom, Interpolate, _make_encoder
 from .lseg_vit import _NoForward
@@ -285,6 +286,21 @@ class LSeg(BaseModel):
         self._stamp_epoch = getattr(self, "_stamp_epoch", 0) + 1
         return super().load_state_dict(*a, **k)
 
+    # ToTensor + Normalize of the reference's transform (lseg_module.py:37-50), applied by the engine's first stage to uint8 input
+    input_mean, input_std = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+
+    def _input(self, eng, x):
+        """x as the engine takes it, the engine's input format switched to x's for this call: a decoded uint8 [B,H,W,3] batch goes in as
+        it is (HipEngine.set_input_u8 with input_mean / input_std), anything else as the normalised float32 [B,3,H,W] tensor."""
+        if x.dtype == torch.uint8:
+            want = (tuple(float(v) for v in self.input_mean), tuple(float(v) for v in self.input_std))
+            if eng.input_u8 != want:
+                eng.set_input_u8(True, *want)
+            return x
+        if eng.input_u8 is not None:
+            eng.set_input_u8(False)
+        return x.float()
+
     def forward_metrics(self, x, target, labelset="", ignore_index=-1, panel=None, streamed=False):
         """evaluate(x, target) of the Lightning module without the full-resolution logits (lseg_forward_stats).
         streamed=True: the same dict -- counts and nll_* keys -- from the streamed label route (lseg_forward_labels_loss): no logits at any
@@ -318,8 +334,8 @@ class LSeg(BaseModel):
 
     def _forward_metrics_streamed(self, x, target, labelset, ignore_index):
         from lseg_hip.metrics import _counts_dict
-        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != (x.shape[0], x.shape[2], x.shape[3]):
-            raise ValueError(f"forward_metrics: target must be [B,H,W] = {(x.shape[0], x.shape[2], x.shape[3])}")
+        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != image_dims(x):
+            raise ValueError(f"forward_metrics: target must be [B,H,W] = {image_dims(x)}")
         groups, flat = None, labelset
         if isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset):
             groups = [len(ls) for ls in labelset]
@@ -329,7 +345,7 @@ class LSeg(BaseModel):
         text = self.text if flat == "" else tokenize(flat, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet.forward_metrics needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         was = self.training
         self.eval()
         try:
@@ -339,7 +355,7 @@ class LSeg(BaseModel):
                     eng.set_train(False)
                 self._set_tokens(eng, text, flat, groups)
                 self._last_engine = eng
-                r = eng.forward_labels_loss(x.float(), target.to(x.device), ignore_index)
+                r = eng.forward_labels_loss(self._input(eng, x), target.to(x.device), ignore_index)
                 if self._range_guard(eng, x.device):                            # fell back to bf16: run again on a bf16 engine
                     return self._forward_metrics_streamed(x, target, labelset, ignore_index)
         finally:
@@ -363,7 +379,7 @@ class LSeg(BaseModel):
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)       # once, for all panels
         K = text.shape[0]
         panels = plan_panels(K, panel)
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         with torch.no_grad():
             stats = PanelStats(target.to(x.device), K, ignore_index)
             if tuple(stats.target.shape) != (B, H, W):
@@ -402,8 +418,8 @@ class LSeg(BaseModel):
         list entry its id in a vocabulary of nclass classes (B lists shaped like labelset, or one flat list): the areas then have nclass
         entries, and per-image lists drawn from one vocabulary add up to per-class IoU."""
         from lseg_hip.metrics import _counts_dict
-        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != (x.shape[0], x.shape[2], x.shape[3]):
-            raise ValueError(f"label_metrics: target must be [B,H,W] = {(x.shape[0], x.shape[2], x.shape[3])}")
+        if not torch.is_tensor(target) or target.dim() != 3 or tuple(target.shape) != image_dims(x):
+            raise ValueError(f"label_metrics: target must be [B,H,W] = {image_dims(x)}")
         ragged = isinstance(labelset, (list, tuple)) and len(labelset) > 0 and all(isinstance(ls, (list, tuple)) for ls in labelset)
         if class_ids is not None:
             if not ragged:
@@ -438,7 +454,7 @@ class LSeg(BaseModel):
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet.predict_labels needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         was = self.training
         self.eval()
         try:
@@ -448,7 +464,7 @@ class LSeg(BaseModel):
                     eng.set_train(False)
                 self._set_tokens(eng, text, labelset, groups)
                 self._last_engine = eng
-                r = eng.forward_labels_conf(x.float()) if confidence else eng.forward_labels(x.float())
+                r = eng.forward_labels_conf(self._input(eng, x)) if confidence else eng.forward_labels(self._input(eng, x))
                 if self._range_guard(eng, x.device):                            # fell back to bf16: run again on a bf16 engine
                     if groups is not None:
                         labelset = [labelset[sum(groups[:b]):sum(groups[:b + 1])] for b in range(len(groups))]
@@ -555,7 +571,7 @@ class LSeg(BaseModel):
         text = self.text if labelset == "" else tokenize(labelset, self.cfg.text.ctx, self.cfg.text.vocab)
         if not x.is_cuda:
             raise RuntimeError("LSegNet needs CUDA/HIP tensors (no CPU path, like the reference: lseg_vit.py:224)")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         eng = self._train_engine(B, H, W, text.shape[0], x.device)
         self._set_tokens(eng, text, labelset, groups)
         if eng._nbt:
@@ -584,10 +600,10 @@ class LSeg(BaseModel):
             cap = getattr(self, "max_labels", None)
             if cap is not None and (max(groups) > cap or sum(groups) > cap):
                 raise ValueError(f"per-image label lists: sizes {groups} exceed max_labels={cap}")
-            check_ragged_target(target, x.shape[0], x.shape[2], x.shape[3])
+            check_ragged_target(target, *image_dims(x))
             labelset = [lab for ls in labelset for lab in ls]               # encoded once per occurrence, image 0's labels first
         eng, keys, params = self._train_inputs(x, labelset, groups)
-        return _EngineLossFn.apply(x.float(), target, self, eng, keys, int(ignore_index), *params)
+        return _EngineLossFn.apply(self._input(eng, x), target, self, eng, keys, int(ignore_index), *params)
 
     def _range_guard(self, eng, device):
         """fp16 MFMA operands saturate at 65504 where the reference's fp32 tower cannot (lseg_vit.py:196-197).  Checked on the first
@@ -643,16 +659,16 @@ class LSeg(BaseModel):
             raise RuntimeError("LSegNet.forward needs a CUDA/HIP tensor: like the reference (clip.load(device="
                                "'cuda'), lseg_vit.py:224) this network has no CPU path, and the HIP engine has no "
                                "PyTorch fallback")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         if self.training and torch.is_grad_enabled():              # net.train() under autograd: training_step (:66-81)
             eng, keys, params = self._train_inputs(x, labelset)
-            return _EngineTrainFn.apply(x.float(), self, eng, keys, *params)
+            return _EngineTrainFn.apply(self._input(eng, x), self, eng, keys, *params)
         eng = self._engine(B, H, W, text.shape[0], x.device)
         if eng.training:
             eng.set_train(False)
         self._set_tokens(eng, text, labelset)
         self._last_engine = eng
-        out = eng.forward(x.float(), want_logits=_want_logits)
+        out = eng.forward(self._input(eng, x), want_logits=_want_logits)
         if self._range_guard(eng, x.device):
             return self.forward(x, labelset, _want_logits)              # fell back to bf16: run again on a bf16 engine
         return out
@@ -666,13 +682,13 @@ class LSeg(BaseModel):
             raise RuntimeError("LSegNet.forward_lowres needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("LSegNet.forward_lowres is an inference path: call it under net.eval() or torch.no_grad()")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         eng = self._engine(B, H, W, text.shape[0], x.device)
         if eng.training:
             eng.set_train(False)
         self._set_tokens(eng, text, labelset)
         self._last_engine = eng
-        out = eng.forward_lowres(x.float())
+        out = eng.forward_lowres(self._input(eng, x))
         if self._range_guard(eng, x.device):
             return self.forward_lowres(x, labelset)                     # fell back to bf16: run again on a bf16 engine
         return out
@@ -685,7 +701,7 @@ class LSeg(BaseModel):
             raise RuntimeError("LSegNet.hold_features needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("LSegNet.hold_features is an inference path: call it under net.eval() or torch.no_grad()")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         eng = self._engine(B, H, W, 1, x.device)
         if eng.training:
             eng.set_train(False)
@@ -693,7 +709,7 @@ class LSeg(BaseModel):
             eng.clear_grouping()
             eng._tok = None
         self._last_engine = eng
-        feat, scale = eng.forward_features(x.float())
+        feat, scale = eng.forward_features(self._input(eng, x))
         if self._range_guard(eng, x.device):
             return self.hold_features(x)                                # fell back to bf16: run again on a bf16 engine
         return HeldFeatures(feat, scale, B, (H, W), eng._stamp)

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from lseg_hip.config import get_config
+from lseg_hip.engine import image_dims
 from lseg_hip.tokenizer import tokenize
 from .lseg_blocks import Interpolate, _make_encoder
 from .lseg_net import BaseModel, default_image_dtype, LSeg as _LSegShared, _make_fusion_block, _new_shared, _EngineTrainFn, _EngineLossFn
@@ -67,18 +68,18 @@ class LSeg(_LSegShared):
         ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
         if not x.is_cuda:
             raise RuntimeError("LSegNetZS.forward needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         if len(ids) != B:
             raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
         if self.training and torch.is_grad_enabled():                         # training_step (lsegmentation_module_zs.py:86-155)
             eng, keys, params = self._train_inputs(x, ids)
-            return _EngineTrainFn.apply(x.float(), self, eng, keys, *params)
+            return _EngineTrainFn.apply(self._input(eng, x), self, eng, keys, *params)
         text = torch.cat([self.texts[c] for c in ids], dim=0)                 # [2B, ctx]; :178
         eng = self._engine(B, H, W, text.shape[0], x.device)
         if eng.training:
             eng.set_train(False)
         self._set_group_tokens(eng, text, ids)
-        out = eng.forward(x.float())                                          # [B, 2, H, W]
+        out = eng.forward(self._input(eng, x))                                          # [B, 2, H, W]
         if self._range_guard(eng, x.device):
             return self.forward(x, class_info)                                # fp16 overflowed: again on bf16 operands (loud)
         return out
@@ -93,7 +94,7 @@ class LSeg(_LSegShared):
         ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
         if not x.is_cuda:
             raise RuntimeError("LSegNetZS.evaluate_episode needs a CUDA/HIP tensor (no CPU path, no PyTorch fallback)")
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         if len(ids) != B:
             raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
         text = torch.cat([self.texts[c] for c in ids], dim=0)
@@ -101,7 +102,7 @@ class LSeg(_LSegShared):
         if eng.training:
             eng.set_train(False)
         self._set_group_tokens(eng, text, ids)
-        out = eng.forward(x.float(), want_logits=bool(want_logits))            # None without logits: only the low planes stay
+        out = eng.forward(self._input(eng, x), want_logits=bool(want_logits))            # None without logits: only the low planes stay
         if self._range_guard(eng, x.device):
             return self.evaluate_episode(x, class_info, target, ignore, meter, want_logits)    # fp16 overflowed: again on bf16 operands
         r = eng.episode_stats(target.reshape(B, H, W), None if ignore is None else ignore.reshape(B, H, W),
@@ -123,7 +124,7 @@ class LSeg(_LSegShared):
         if not x.is_cuda:
             raise RuntimeError("LSegNetZS needs CUDA/HIP tensors (no CPU path)")
         ids = [int(c) for c in (class_info.tolist() if torch.is_tensor(class_info) else class_info)]
-        B, _, H, W = x.shape
+        B, H, W = image_dims(x)
         if len(ids) != B:
             raise ValueError(f"class_info has {len(ids)} entries for a batch of {B}")
         text = torch.cat([self.texts[c] for c in ids], dim=0)
@@ -142,7 +143,7 @@ class LSeg(_LSegShared):
             raise RuntimeError("forward_loss is the training-step path: call it under net.train() with grad enabled")
         eng, keys, params = self._train_inputs(x, class_info)
         self._last_train_engine = eng                    # holds this step's train-mode logits: LSegmentationModuleZS's train_average_meter
-        return _EngineLossFn.apply(x.float(), target, self, eng, keys, int(ignore_index), *params)
+        return _EngineLossFn.apply(self._input(eng, x), target, self, eng, keys, int(ignore_index), *params)
 
 
 class LSegNetZS(LSeg):
